@@ -132,6 +132,43 @@ def step_inventory():
             "idle_gpu_ms_per_step": round(sum(i for _, i in per) / len(per), 3), "source": STEP_INVENTORY}
 
 
+# 3DGS learning-rate ratios (configs/base/gaussian2d.yaml-style groups) scaled by 1e-2: same optimizer work per step, but the seeded
+# scene stays statistically the one the committed profiles describe over any --steps
+LR_OF = {"means3D": 1.6e-6, "shs": 2.5e-5, "opacities": 5e-4, "scales": 5e-5, "rotations": 1e-5, "specular": 2.5e-5, "roughness": 2.5e-5}
+DUMP_BUDGET_BYTES = 60_000_000          # array data of one --dump-outputs; with the .npy headers the directory stays below 64 MB
+
+
+def flatten_outputs(prefix, obj, arrays):
+    """Nested dict / tuple of a step's results -> {"prefix.key.sub": tensor} (non-tensor entries are skipped)."""
+    if isinstance(obj, torch.Tensor):
+        arrays[prefix] = obj
+    elif isinstance(obj, dict):
+        for k, v in obj.items():
+            flatten_outputs("%s.%s" % (prefix, k), v, arrays)
+    elif isinstance(obj, (tuple, list)):
+        for i, v in enumerate(obj):
+            flatten_outputs("%s.%d" % (prefix, i), v, arrays)
+
+
+def dump_outputs(dirname, arrays):
+    """Write every tensor of `arrays` as dirname/<name>.npy in float32.  Each array may take an equal share of DUMP_BUDGET_BYTES; a larger one
+    is replaced by a sample of its flattened elements at sorted indices drawn by numpy.random.default_rng(0) -- the same indices for the same
+    element count on every run, so dumps of two builds run with the same arguments compare element for element.  Returns the bytes written."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    cap = DUMP_BUDGET_BYTES // 4 // max(1, len(arrays))
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), cap, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.to(torch.float32).cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        total += a.nbytes
+    return total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -181,8 +218,17 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--live-scopes", default="two", choices=["two", "all", "none"], help="which of the library's HIP-event scopes record INSIDE the timed regions: the two kernels that took most of the warm-up "
                     "(default; the others are timed in a separate pass after the regions), all of them (0.17 ms per EnvGS step of barrier packets), or none (diagnostic: no per-kernel times)")
-    ap.add_argument("--repeats", type=int, default=10, help="the timed region of EXACTLY --steps steps (barrier + synchronize on both sides) is run this many times "
-                    "back to back; ms_per_step / value are the MEDIAN region, ms_per_step_spread has min / max (VERDICT r4: 20 steps = 0.17 s was a thin sample)")
+    ap.add_argument("--repeats", type=int, default=1, help="the timed region of EXACTLY --steps steps (barrier + synchronize on both sides) is run this many times "
+                    "back to back; ms_per_step / value are the MEDIAN region, ms_per_step_spread has min / max.  The default, 1, keeps the number of timed steps "
+                    "equal to --steps (callers size later runs by steps x ms_per_step); profiling runs ask for more regions explicitly")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed regions, run the timed path's step once more on the last timed "
+                    "step's view, from the seeded parameters and a fresh optimizer state, and write what it computed -- its forward outputs, the parameters' "
+                    "gradients and the parameters after the optimizer step -- as DIR/<name>.npy (float32, at most 64 MB in all: an array beyond its share "
+                    "is a fixed seeded sample, see dump_outputs()); its inputs are identical on every run with the same arguments, so two builds can be "
+                    "compared file by file.  Not the last timed step itself: the trajectory of the timed steps differs from run to run (float atomics in "
+                    "the backward, amplified by Adam), so a difference between builds that only shows after several steps -- Adam moments beyond the "
+                    "first update, the environment structure refitted to moved surfels -- does not reach the dump.  The trained parameters and optimizer "
+                    "state are put back afterwards, so the passes after it start where the timed steps ended")
     ap.add_argument("--no-reference-caller", action="store_true", help="skip the extra few steps that time the unchanged-EasyVolcap-caller form of the step (config.reference_caller_ms_per_step)")
     ap.add_argument("--step-times", type=int, default=0, help="diagnostics: after the timed region, run this many extra steps one by one (synchronised) and print their wall times and the allocator statistics to stderr")
     ap.add_argument("--stage-counts", action="store_true", help="diagnostics: after the timed region, one more step with every traced call's counters (rays, hits found / composited, entries) printed to stderr")
@@ -312,11 +358,9 @@ def main():
     n_acc = {"N": 0, "steps": 0}
     last_rays = [None, None]
     all_params = list(params.values()) + list(env_params.values())
-    # 3DGS learning-rate ratios (configs/base/gaussian2d.yaml-style groups) scaled by 1e-2: same optimizer work per step, but the seeded
-    # scene stays statistically the one the committed profiles describe over any --steps
-    lr_of = {"means3D": 1.6e-6, "shs": 2.5e-5, "opacities": 5e-4, "scales": 5e-5, "rotations": 1e-5, "specular": 2.5e-5, "roughness": 2.5e-5}
-    groups = [{"params": [v], "lr": lr_of[k], "name": k} for k, v in params.items()] + \
-             [{"params": [v], "lr": lr_of[k], "name": "env_" + k} for k, v in env_params.items()]
+    seeded = [p_.detach().clone() for p_ in all_params] if args.dump_outputs is not None else None
+    groups = [{"params": [v], "lr": LR_OF[k], "name": k} for k, v in params.items()] + \
+             [{"params": [v], "lr": LR_OF[k], "name": "env_" + k} for k, v in env_params.items()]
     opt = None
     if args.optim == "fused":
         from envgs_amd.optim import FusedAdam
@@ -331,7 +375,9 @@ def main():
         reducer = edist.GradExchange(lambda: [list(env_params.values()), list(params.values())], average=True, algo=args.exchange,
                                      overlap=not args.no_overlap_allreduce)
 
-    def step(it):
+    kept = {}
+
+    def step(it, keep=False):
         vi = (it * world + rank) % 8
         cam = cams[vi]
         if reducer is not None:
@@ -352,6 +398,9 @@ def main():
                 means3D=params["means3D"], means2D=means2D, shs=params["shs"], colors_precomp=None,
                 opacities=params["opacities"], scales=params["scales"], rotations=params["rotations"], cov3D_precomp=None)
             loss = (color * dcol).sum() + (allmap * dall).sum()
+        if keep:                                   # --dump-outputs: the forward's results as the caller receives them
+            kept["out"] = (out if envgs else dict(zip(("rgb", "dpt", "acc", "norm", "dist", "aux", "mid", "wet"), (rgb_, dpt_, acc_, norm_, dist_, aux_, mid_, wet_)))
+                           if btrace else dict(color=color, radii=radii, allmap=allmap, weight=weight))
         n_acc["N"] += (raster.LAST_STATS["N"] if not btrace else 0); n_acc["steps"] += 1
         loss.backward()
         tracing.join_deferred_gradients()         # (no-op unless the env surfels' gradients were left to finish beside the base pass's backward)
@@ -416,6 +465,32 @@ def main():
         regions.append(time.perf_counter() - t0)
     lib.envgs_prof_enable(0)
     n_timed = dict(n_acc)                          # (the kernel timers cover the timed steps only; later steps -- the reference-caller form, --step-times -- must not dilute the per-launch figures)
+    if args.dump_outputs is not None:
+        # The step of the timed path once more, on the last timed step's view, from the seeded parameters and a fresh optimizer state.  The float
+        # atomics of the backward make each step's gradients differ in their last bits from run to run, and Adam turns that into parameters (and so
+        # outputs) that drift apart over the timed steps (up to 2.5e-2 of an output's scale after 25 steps); this step's inputs are identical on every run.
+        trained = [p_.detach().clone() for p_ in all_params]
+        with torch.no_grad():
+            for p_, s_ in zip(all_params, seeded):
+                p_.copy_(s_)
+        if opt is not None:
+            trained_state, opt.state = opt.state, type(opt.state)(dict)
+        step(args.warmup + len(regions) * args.steps - 1, keep=True)
+        sync_all()
+        if rank == 0:
+            arrays = {}
+            flatten_outputs("out", kept.pop("out"), arrays)
+            p_names = list(params) + ["env." + k for k in env_params]
+            arrays.update(("grad." + k, g_) for k, g_ in zip(p_names, last_grads) if g_ is not None)
+            arrays.update(("param." + k, p_) for k, p_ in zip(p_names, all_params))
+            dump_outputs(args.dump_outputs, arrays)
+            del arrays
+        with torch.no_grad():                      # back to where the timed steps ended, for the passes below
+            for p_, t_ in zip(all_params, trained):
+                p_.copy_(t_)
+        if opt is not None:
+            opt.state = trained_state
+        del trained
     if world > 1:
         tt = torch.tensor(regions, device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)  # per region: the slowest rank
@@ -668,8 +743,8 @@ def main():
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = args.steps * world / elapsed
-        spread = {"repeats": len(regions), "min": round(min(regions) / args.steps * 1e3, 4), "max": round(max(regions) / args.steps * 1e3, 4),
-                  "timed_seconds_total": round(sum(regions), 3), "note": "ms_per_step / value = the median of `repeats` back-to-back timed regions of exactly `steps` steps each"}
+        spread = {"repeats": len(regions), "timed_steps": n_timed["steps"], "min": round(min(regions) / args.steps * 1e3, 4), "max": round(max(regions) / args.steps * 1e3, 4),
+                  "timed_seconds_total": round(sum(regions), 3), "note": "ms_per_step / value = the median of `repeats` back-to-back timed regions of exactly `steps` steps each; timed_steps = the steps counted inside them"}
         leaf = {k: v for k, v in kernels.items() if k not in ("trace_fwd", "trace_bwd") and v["GBps"]}
         dom = max(leaf, key=lambda k: leaf[k]["ms"] * leaf[k]["launches"]) if leaf else None      # most time per step (launches included)
         roof = None

@@ -7,8 +7,8 @@ the 2DGS / EnvGS papers.  Whoever has the CUDA/OptiX build on an NVIDIA box runs
 
     python dump_reference_kernel_golden.py --out reference_kernel_golden.pt            # needs: torch + the four installed packages, nothing else
 
-and copies the file to tests/golden/reference_kernel_golden.pt of this repository; tests/test_reference_kernel_golden.py then feeds the stored
-INPUTS to the HIP path and compares with the stored outputs and gradients (radii bit-exact, everything else within 1e-4).  The script is
+and commits the file under tests/golden/ of this repository with a test that hands it to tests/test_reference_kernel_golden.py:_compare_file,
+which feeds the stored INPUTS to the HIP path and compares with the stored outputs and gradients (radii bit-exact, everything else within 1e-4).  The script is
 self-contained on purpose: it imports torch, the four installed extension packages and -- by file path, for the seeded scene generators only --
 envgs_amd/synth.py (pure torch; copy that one file next to the script, or pass --synth).  It contains no reference source.
 

@@ -1,11 +1,11 @@
-"""GPU: the HIP path against fixtures dumped from the REAL extensions (tests/golden/dump_reference_kernel_golden.py).
+"""GPU: the fixture format of tests/golden/dump_reference_kernel_golden.py and the loader that feeds such a fixture to the HIP path.
 
-The extension sources are absent from /root/reference (empty submodules), so the oracle's kernel-body arithmetic is "parity unpinned"
-(DESIGN.md section 5).  The day someone runs the dump script where the CUDA/OptiX build is installed and commits its output as
-tests/golden/reference_kernel_golden.pt, `test_hip_path_matches_the_real_extensions` compares every stored output and gradient with this
-path on the stored inputs (radii bit-exact, values within 1e-4 of the tensor's scale) -- and "unpinned" can close.  Until then that test skips,
-and `test_dump_script_and_loader_agree` keeps the two halves honest against each other: it runs the dump script over this repository's own
-drop-in packages (--allow-local) into a temporary file and consumes that file with the same loader."""
+The sources of the real CUDA/OptiX extensions are not available (the reference tree carries them as empty submodules), so no fixture of
+their outputs exists and the oracle's kernel-body arithmetic is "parity unpinned" (DESIGN.md section 5).  Whoever dumps one where that build
+is installed commits it under tests/golden/ together with a test that passes it to `_compare_file` (radii bit-exact, every other output and
+gradient within 1e-4 of the tensor's scale; a fixture dumped with --allow-local, from this repository's own packages, is refused there).  Until then `test_dump_script_and_loader_agree` keeps the two halves honest against each other:
+it runs the dump script over this repository's own drop-in packages (--allow-local) into a temporary file and consumes that file with the
+same loader."""
 import os
 import subprocess
 import sys
@@ -14,12 +14,11 @@ import numpy as np
 import pytest
 import torch
 
-from tests.util import check_close, record
+from tests.util import check_close
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden", "reference_kernel_golden.pt")
 SCRIPT = os.path.join(ROOT, "tests", "golden", "dump_reference_kernel_golden.py")
 TOL = 1e-4
 
@@ -75,9 +74,12 @@ def _run_tracer(case, dev):
     return res, grads
 
 
-def _compare_file(path, test):
+def _compare_file(path, test, allow_local=False):
+    """Feed the stored inputs of a dump-script fixture to the HIP path and compare.  A fixture dumped from this repository's own packages
+    (--allow-local) pins nothing: it is refused unless `allow_local` says the caller is testing the script itself."""
     data = torch.load(path, map_location="cpu", weights_only=False)
     assert data["meta"]["schema"] == 1
+    assert allow_local or not data["meta"].get("local_packages"), "%s was dumped from this repository's own packages (--allow-local): it pins nothing" % path
     dev = torch.device("cuda:0")
     for case in data["raster"]:
         outs, grads = _run_raster(case, dev)
@@ -105,21 +107,14 @@ def _compare_file(path, test):
     return data["meta"]
 
 
-def test_hip_path_matches_the_real_extensions():
-    if not os.path.exists(GOLDEN):
-        pytest.skip("tests/golden/reference_kernel_golden.pt absent: nobody has run tests/golden/dump_reference_kernel_golden.py over the real CUDA/OptiX "
-                    "extensions yet (their sources are not in /root/reference) -- parity of the kernel bodies stays unpinned")
-    meta = _compare_file(GOLDEN, "real_extensions")
-    assert not meta.get("local_packages"), "the committed fixture was dumped from this repository's own packages (--allow-local): it pins nothing"
-    record("real_extensions", "fixture_device", 0.0, "(%s, torch %s)" % (meta.get("device_name"), meta.get("torch")))
-
-
 def test_dump_script_and_loader_agree(tmp_path):
     out = str(tmp_path / "self_golden.pt")
     r = subprocess.run([sys.executable, SCRIPT, "--allow-local", "--out", out], capture_output=True, text=True, cwd=ROOT, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    meta = _compare_file(out, "dump_self_test")
+    meta = _compare_file(out, "dump_self_test", allow_local=True)
     assert meta["local_packages"] and len(meta["packages"]) == 4
+    with pytest.raises(AssertionError, match="pins nothing"):           # as a committed fixture, the same file is refused
+        _compare_file(out, "dump_self_test")
     # without --allow-local the script must refuse this repository's own same-named packages (it would pin nothing)
     r2 = subprocess.run([sys.executable, SCRIPT, "--out", out + ".x"], capture_output=True, text=True, cwd=ROOT, timeout=600)
     assert r2.returncode != 0 and not os.path.exists(out + ".x")
