@@ -375,6 +375,7 @@ int envgs_trace_backward(const envgs_trace_cfg *cfg, const float *nodes, const f
         if (!no_finish) { ZERO(dmeans3D, P * 3); ZERO(dgrads3D, P * 3); ZERO(dscales, P * 2); ZERO(drots, P * 4); ZERO(dopacities, P); }
         ZERO(dothers, P * 2); ZERO(dray_o, R * 3); ZERO(dray_d, R * 3);
         if (counters && cfg->num_rays > 0 && cfg->P > 0) ZERO(reinterpret_cast<float *>(counters), 1);      // only the ray-fetch counter: [1] (largest list) and the stats stay readable
+        if (counters && cfg->num_rays > 0 && cfg->P > 0) ZERO(reinterpret_cast<float *>(counters + 66), 1); // and this backward's count of invalid sparse-list entries
 #undef ZERO
         const int rcz = launch_zero_many(zb, stream);              // one launch instead of eleven fills
         if (rcz) return rcz;

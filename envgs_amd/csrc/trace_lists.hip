@@ -387,6 +387,20 @@ sort_composite_fwd(const TraceArgs A)
 //   entries[b][e]  e < D: the distinct surfels of the table, packed  sid | (hits-1) << 24 | slot << 32 ; singles that found no room in
 //                  the table are filed from the TOP of the region downwards (n_entries[2b] = D, n_entries[2b+1] = singles)
 //   pairs[b][...]  (lane << 16 | k) of every hit, grouped by entry in entry order (singles again from the top)
+// Claims n consecutive slots of the sparse-hit list (counters[64] = slots handed out so far): the first slot, or 0xFFFFFFFF when they do
+// not fit.  The counter only grows and only by claims that fit (compare-and-swap), so [0, counters[64]) is exactly the slots written, each
+// by the one claim that counted it, and a smaller later claim can still fit after a larger one failed.
+__device__ __forceinline__ unsigned sparse_claim(const TraceArgs &A, const unsigned n)
+{
+    unsigned cur = __hip_atomic_load(A.counter + 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (;;) {
+        if (cur > A.sparse_cap || n > A.sparse_cap - cur) return 0xFFFFFFFFu;      // (sparse_cap <= 0xFFFFFFF0: a first slot never reads as the sentinel)
+        const unsigned prev = atomicCAS(A.counter + 64, cur, cur + n);
+        if (prev == cur) return cur;
+        cur = prev;                                                             // another claim fitted first: the counter grew, try behind it
+    }
+}
+
 constexpr int RH_TAB = 1024;
 constexpr int RH_STAGE = 8192;                           // pairs staged in LDS per batch (32 KB); the rest, if any, is stored directly
 template <bool CACHED>                                   // CACHED: lists of at most 256 hits with pairs wanted (see `cached` below); the launch decides
@@ -520,9 +534,10 @@ register_hits(const TraceArgs A)
         // SPARSE entries (round 6; envgs_trace.h: sparse_hits): a surfel that at most sparse_max of the batch's 64 rays blended does not become an
         // entry -- batch_surfel_bwd pays one 64-lane pass per entry however few of its lanes are live, and a fifth of the entries of the benchmark
         // view carry 1.4 % of its hits.  Its hits are filed in a global list instead (one lane of sparse_hits_bwd and one gradient record PER HIT:
-        // the surfel's record count grows by its hit count).  List space is claimed per 64-surfel chunk with one atomic; a chunk that finds no
-        // room gives its claim back and files ordinary entries (successful claims stay compact: a later claim can only succeed once the
-        // counter is back below the capacity, i.e. behind every successful one).
+        // the surfel's record count grows by its hit count).  List space is claimed per 64-surfel chunk by a compare-and-swap that adds only
+        // when the claim fits (sparse_claim); a chunk that does not fit files ordinary entries.  Space is never given back, so counters[64] is
+        // exactly the number of hits filed and every slot below it is written by the chunk that counted it (an add-then-give-back claim left
+        // holes and overlaps whenever two failed claims were in flight at once).
         const bool sparse_on = A.sparse != nullptr && A.sparse_max > 0 && ent != nullptr && prs != nullptr;
         if (part == 0) {
             unsigned carry_off = 0u, carry_d = 0u;
@@ -541,10 +556,7 @@ register_hits(const TraceArgs A)
                     const unsigned stot = (unsigned)wave_bcast(sincl, 63);
                     if (stot > 0u) {
                         unsigned sb = 0u;
-                        if (lane == 0) {
-                            sb = atomicAdd(A.counter + 64, stot);
-                            if (sb > A.sparse_cap || stot > A.sparse_cap - sb) { atomicSub(A.counter + 64, stot); sb = 0xFFFFFFFFu; }
-                        }
+                        if (lane == 0) sb = sparse_claim(A, stot);
                         sb = (unsigned)__builtin_amdgcn_readfirstlane((int)sb);
                         if (sb == 0xFFFFFFFFu) sp = false;
                         else sp_pos = sb + (unsigned)sincl - spn;
@@ -644,9 +656,7 @@ register_hits(const TraceArgs A)
             if (sparse_on && nfail > 0u) {
                 __shared__ unsigned fbase;
                 if (threadIdx.x == 0) {
-                    unsigned sb = atomicAdd(A.counter + 64, nfail);
-                    if (sb > A.sparse_cap || nfail > A.sparse_cap - sb) { atomicSub(A.counter + 64, nfail); sb = 0xFFFFFFFFu; }
-                    fbase = sb;
+                    fbase = sparse_claim(A, nfail);
                 }
                 __syncthreads();                                   // (also: this workgroup's own ent / prs stores of the first phase are visible to it)
                 if (fbase != 0xFFFFFFFFu) {

@@ -491,9 +491,21 @@ sparse_hits_bwd(const TraceArgs A, const int rgbo)
     const int nb = (A.D + 1) * (A.D + 1);
     for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
         const uint4 e = A.sparse[i];
+        // every entry is checked before it is used as an index: a ray slot of the call, a composited position of that ray's list, a surfel, a
+        // gradient record of the call.  One that fails is skipped and counted in counters[66] (zeroed by every backward; envgs_trace.h: sparse_hits)
+        // -- the claim in register_hits makes the list exact, so the count is 0 and a nonzero one is a bug to report, not an address to follow
+        bool ok = e.x < (unsigned)A.R && e.z < (unsigned)A.P;
+        int r = A.R;
+        if (ok) {
+            r = ray_of(A, (int)e.x);
+            ok = r < A.R && A.hit_cnt[r] <= A.cap && e.y < (unsigned)A.n_used[r];
+        }
+        if (ok) {
+            const size_t ci0 = (size_t)e.z * NCOPY + (((int)e.x >> 6) & (NCOPY - 1));
+            ok = (unsigned long long)(A.surf_off[ci0] - A.surf_cnt[ci0]) + (unsigned long long)e.w < A.num_records;
+        }
+        if (!ok) { atomicAdd(A.counter + 66, 1u); continue; }
         const int slot = (int)e.x, k = (int)e.y, sid = (int)e.z;
-        const int r = ray_of(A, slot);
-        if (r >= A.R) continue;
         BwdRay B;
         bwd_load_ray(A, r, B);
         float basis[16];
@@ -559,8 +571,8 @@ sparse_hits_bwd(const TraceArgs A, const int rgbo)
         // the record: (16, 3) SH gradient = basis (x) dL/dcolour (or the 3 colour words), then the 15 geometry words
         const int copy = (slot >> 6) & (NCOPY - 1);
         const size_t ci = (size_t)sid * NCOPY + copy;
-        const unsigned long long rec = (unsigned long long)(A.surf_off[ci] - A.surf_cnt[ci]) + (unsigned long long)e.w;
-        if (rec < A.num_records) {
+        const unsigned long long rec = (unsigned long long)(A.surf_off[ci] - A.surf_cnt[ci]) + (unsigned long long)e.w;     // (< num_records: checked above)
+        {
             float4 *ro = reinterpret_cast<float4 *>(A.records + rec * RECW);
             if (A.M > 0) {
 #pragma unroll

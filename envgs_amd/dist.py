@@ -143,6 +143,12 @@ def exchange_flat(flat, average=True, group=None, algo="direct", async_op=False,
     return done
 
 
+def _join_deferred():
+    """Make the current stream wait for surfel gradients a tracer backward left to finish on the library's stream (no-op when none are pending)."""
+    from . import tracing
+    tracing.join_deferred_gradients()
+
+
 class _Bucket:
     __slots__ = ("params", "ids", "flat", "recv", "mine", "numel", "offsets", "pending", "done", "launched")
 
@@ -267,12 +273,16 @@ class GradExchange:
             self._launch(B)
 
     def _launch(self, B):
+        _join_deferred()                                  # (the tracer may still be finishing surfel gradients this bucket views)
         B.launched = True
         if B.flat.numel():
             B.done = exchange_flat(B.flat, average=self.average, group=self.group, algo=self.algo, async_op=True, recv=B.recv, mine=B.mine)
 
     def finish(self):
-        """Call after the last backward(): launches the remaining buckets in order, completes all of them, returns the bytes exchanged."""
+        """Call after the last backward(): launches the remaining buckets in order, completes all of them, returns the bytes exchanged.
+        Joins deferred tracer gradients first (envgs_amd.tracing.join_deferred_gradients), also with one process: the `.grad` views are
+        complete on the current stream when this returns."""
+        _join_deferred()
         self._in_step = False
         if not self.enabled:
             return 0

@@ -164,7 +164,9 @@ def env_pass(tracer, tpkg, cam, env, ref_o, ref_d, env_bg, sh_degree, prepared_v
         tracer.set_colour_only_backward(bool(FUSED["on"] and not REFERENCE_FORMS["on"] and COLOUR_ONLY["on"] and int(TRACE["depth"]) == 0))
     if hasattr(tracer, "set_deferred_surfel_gradients"):
         tracer.set_deferred_surfel_gradients(bool(FUSED["on"] and not REFERENCE_FORMS["on"] and DEFER["on"]))       # (bounce stages chain their accumulators)
-    if FUSED["on"] and not REFERENCE_FORMS["on"]:
+    if env.get("grads3D") is not None:
+        grads3D = env["grads3D"]                                                  # (the sink envgs_forward put behind the deferral barrier)
+    elif FUSED["on"] and not REFERENCE_FORMS["on"]:
         grads3D = torch.zeros_like(env["means3D"]).requires_grad_(True)          # (gradient sink, never read: one fill, no `+ 0`)
     else:
         grads3D = torch.zeros_like(env["means3D"], requires_grad=True) + 0
@@ -178,14 +180,19 @@ def envgs_forward(pkg, tpkg, tracer, cam, rays, base, env, bg, env_bg, sh_degree
     """One EnvGS forward: base raster -> reflect -> env trace -> blend.  Returns dict of (H,W,*) maps."""
     H, W = cam.image_height, cam.image_width
     if FUSED["on"] and not REFERENCE_FORMS["on"] and DEFER["on"]:
-        # env surfel tensors that are not leaves (activated parameters): through the barrier node NOW, before the base pass, so that its backward --
-        # the join -- comes up after the base pass's backward has been queued (envgs_amd.tracing.defer_barrier); the tracer is their only consumer here
+        # every env surfel tensor that requires a gradient: through a barrier node NOW, before the base pass, so that its backward -- which orders
+        # the stream after the deferred tail -- comes up after the base pass's backward has been queued.  Activated (non-leaf) tensors: defer_barrier,
+        # which joins; leaves: leaf_barrier, which leaves the tail pending for FusedAdam.step to release (envgs_amd.tracing).  The barriers' outputs
+        # feed the tracer alone; the caller's tensors may feed other terms of the loss too (the env opacity regulariser of the reference's
+        # supervisor): autograd adds those gradients to the tracer's behind the barrier
         from . import tracing
-        keys = [k for k in ("means3D", "shs", "opacities", "scales", "rotations") if k in env and env[k].requires_grad and not env[k].is_leaf]
-        if keys:
-            outs = tracing.defer_barrier(*[env[k].contiguous() for k in keys])
-            env = dict(env)
-            env.update(zip(keys, outs if isinstance(outs, tuple) else (outs,)))
+        # (the grads3D gradient sink too: a bare leaf reaching the tracer would get a barrier of its own at the call, whose wait comes early)
+        env = dict(env, grads3D=torch.zeros_like(env["means3D"]).requires_grad_(True))
+        for barrier, leaf in ((tracing.defer_barrier, False), (tracing.leaf_barrier, True)):
+            keys = [k for k in ("means3D", "grads3D", "shs", "opacities", "scales", "rotations") if k in env and env[k].requires_grad and env[k].is_leaf == leaf]
+            if keys:
+                outs = barrier(*[env[k].contiguous() for k in keys])
+                env.update(zip(keys, outs if isinstance(outs, tuple) else (outs,)))
     prepared_v = env_prepare(tracer, env) if (FUSED["on"] and not REFERENCE_FORMS["on"] and PREBUILD["on"] and hasattr(tracer, "prepare")) else None
     b = base_pass(pkg, cam, base, bg, sh_degree)
     ray_o, ray_d = rays

@@ -214,7 +214,9 @@ def _carve_i32(dev, sizes):
 
 # record backward: entries with few hits filed per hit (envgs_trace.h: sparse_hits).  "auto": when this tracer state's previous call averaged fewer than
 # `below` composited hits per entry; "on" / "off": tests
-SPARSE = {"mode": "auto", "below": 6.0}
+# tests only: "cap" (None | int) passes min(cap, buffer rows) as sparse_cap -- the buffer keeps its full size -- so that claims fail (the C-ABI
+# overflow fall-back); "poison" (None | int32) fills the buffer before the forward, so that a slot nobody wrote can be recognised
+SPARSE = {"mode": "auto", "below": 6.0, "cap": None, "poison": None}
 QUAD_SH = {"on": True}       # list path: four lanes share the fetch of a surfel's SH block (tests switch it off to cover the per-lane gathers)
 KEEP_LISTS = {"on": False}   # tests: keep the last forward's per-ray hit lists reachable through last_hit_lists()
 
@@ -249,24 +251,63 @@ class _DeferBarrier(torch.autograd.Function):
 
 
 def defer_barrier(*tensors):
-    """OPTIONAL, for a training loop whose tracer inputs are NOT leaves (EasyVolcap feeds the tracer sigmoid / exp / normalize of its raw parameters)
-    and that wants set_deferred_surfel_gradients all the same:
+    """OPTIONAL, for a training loop with set_deferred_surfel_gradients: put the tracer's surfel inputs behind this node at the START of the step,
+    before the base pass -- activated parameters (EasyVolcap feeds the tracer sigmoid / exp / normalize of its raw ones) and leaves alike:
 
         act = [torch.sigmoid(raw_opacity), torch.exp(raw_scale), ...]          # at the START of the step, before the base pass
-        opacities, scales, ... = envgs_amd.tracing.defer_barrier(*act)         # identity; pass THESE (and only to) the tracer
+        opacities, scales, ... = envgs_amd.tracing.defer_barrier(*act)         # identity; pass THESE (and only these) to the tracer
 
     The tracer's backward returns its (still unfinished) surfel gradients into this node, whose backward makes the current stream wait for them and
-    only then hands them to the activations' backward.  Autograd runs ready nodes latest-created first, so a barrier created BEFORE the base pass
-    comes up after the base pass's backward has been queued -- which is the overlap the deferral is for; created later it is merely correct.
-    The returned tensors must feed the tracer and nothing else (a second consumer makes autograd ADD the two gradients on arrival, before the
-    join), and each parameter must still receive its tracer gradient from one traced call or bounce chain per backward pass."""
+    only then hands them on -- to the activations' backward, or to a leaf that other ops of the graph use too (a regulariser on the opacities, a
+    second traced call): autograd adds such gradients on arrival.  Autograd runs ready nodes latest-created first, so a barrier created BEFORE the base
+    pass comes up after the base pass's backward has been queued -- which is the overlap the deferral is for; created later it is merely correct.
+    Guaranteed: every gradient that leaves the barrier is complete on the current stream, and nothing is pending afterwards (leaf_barrier: the
+    same ordering for leaves, without the release).  Required: the returned tensors feed the tracer and nothing else (a second consumer of an OUTPUT
+    gets its gradient added before the join; the inputs may have any number of consumers), and each parameter receives its tracer gradient from
+    one traced call or bounce chain per barrier."""
     outs = _DeferBarrier.apply(*tensors)
+    return outs if len(tensors) != 1 else outs[0]
+
+
+def _order_after_deferred():
+    """Make the current stream wait for the pending deferred tail WITHOUT releasing it: the buffers it writes stay held, and join_deferred_gradients()
+    still has work to do (release them), so the state a caller observes -- pending until someone joins -- is that of a backward without barriers."""
+    if not _DEFERRED["pending"]:
+        return
+    dev = _DEFERRED["dev"]
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().envgs_trace_backward_join(_stream(dev)), "envgs_trace_backward_join")
+
+
+class _LeafBarrier(torch.autograd.Function):
+    """Identity in the forward; its backward orders the current stream after the deferred tail before it hands the gradients on to a LEAF, where
+    autograd may add them to another consumer's gradient at once (leaf_barrier)."""
+
+    @staticmethod
+    def forward(ctx, *ts):
+        return tuple(t.view_as(t) for t in ts)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        _order_after_deferred()
+        return gs
+
+
+def leaf_barrier(*tensors):
+    """OPTIONAL companion of defer_barrier for LEAF tracer inputs of a tracer with set_deferred_surfel_gradients.  A leaf may feed other ops of the
+    same graph too (a regulariser on the opacities such as the reference's env_opacity_loss, a second traced call): autograd ADDS their gradients
+    to the tracer's as soon as both have arrived.  This identity node's backward first makes the current stream wait for the deferred tail, so that
+    sum -- and anything else autograd does with the gradient -- sees finished values.  Unlike defer_barrier it releases nothing: the tail stays
+    pending (its buffers held) until join_deferred_gradients(), which FusedAdam.step, GradExchange and the next traced call do.  SurfelTracer.forward
+    creates one at the call for every bare leaf surfel input; envgs_step.envgs_forward creates one before the base pass (where autograd reaches it
+    after the base pass's backward has been queued: the overlap is kept).  The returned tensors must feed the tracer and nothing else."""
+    outs = _LeafBarrier.apply(*tensors)
     return outs if len(tensors) != 1 else outs[0]
 
 
 def _behind_barrier(t):
     fn = t.grad_fn
-    return fn is not None and type(fn).__name__ == "_DeferBarrierBackward" and not getattr(t, "_backward_hooks", None)
+    return fn is not None and type(fn).__name__ in ("_DeferBarrierBackward", "_LeafBarrierBackward") and not getattr(t, "_backward_hooks", None)
 
 
 def trace_forward(nodes, ray_o, ray_d, means3D, shs, colors_precomp, others_precomp, opacities, scales, rotations, settings,
@@ -329,6 +370,11 @@ def trace_forward(nodes, ray_o, ray_d, means3D, shs, colors_precomp, others_prec
             # filed; what finds no room takes the batch kernel -- slower, never wrong)
             n_rows = rows if rows else R * cap
             keep["sparse_hits"] = _scratch((max(4096, n_rows), 4), torch.int32, dev)
+            if SPARSE.get("poison") is not None:
+                keep["sparse_hits"].fill_(int(SPARSE["poison"]))
+        sparse_cap = 0
+        if "sparse_hits" in keep:
+            sparse_cap = keep["sparse_hits"].shape[0] if SPARSE.get("cap") is None else min(int(SPARSE["cap"]), keep["sparse_hits"].shape[0])
         lists = _lib.TraceLists(keep["hit_lists"].data_ptr(), keep["hit_cnt"].data_ptr(), keep["n_used"].data_ptr(), cap,
                                 keep["spill"].data_ptr(), keep["surf_acc"].data_ptr(), keep["surf_cnt"].data_ptr(), keep["surf_off"].data_ptr(),
                                 keep["scan_temp"].data_ptr(), sb, keep["ray_keys"].data_ptr() if srt else None,
@@ -337,7 +383,7 @@ def trace_forward(nodes, ray_o, ray_d, means3D, shs, colors_precomp, others_prec
                                 keep["n_entries"].data_ptr() if "hit_state" in keep else None, rows,
                                 *[(keep[k].data_ptr() if (k in keep and rows) else None) for k in ("row_off", "batch_rows", "row_blk")],
                                 keep["sh_perm"].data_ptr() if "sh_perm" in keep else None, 0,
-                                keep["sparse_hits"].data_ptr() if "sparse_hits" in keep else None, keep["sparse_hits"].shape[0] if "sparse_hits" in keep else 0)
+                                keep["sparse_hits"].data_ptr() if "sparse_hits" in keep else None, sparse_cap)
         if "hit_state" in keep and getattr(caps, "colour_only", False):
             lists.state_planes = 1
             keep["colour_only"] = True
@@ -348,7 +394,11 @@ def trace_forward(nodes, ray_o, ray_d, means3D, shs, colors_precomp, others_prec
                                        p(colors_precomp), p(others_precomp), p(bg), p(srec), p(counters), p(rgb), p(dpt), p(acc),
                                        p(norm), p(dist), p(aux), p(mid), p(wet), p(final_T), lists, _stream(dev)), "envgs_trace_forward")
     LAST_STATS.update(P=P, R=R, caps=caps, rows=rows, counters=counters, n_entries=(keep.get("n_entries") if "hit_state" in keep else None), cap=cap,
-                      lists=((keep["hit_lists"], keep["n_used"], keep["hit_cnt"]) if (cap and KEEP_LISTS["on"]) else None))
+                      lists=((keep["hit_lists"], keep["n_used"], keep["hit_cnt"]) if (cap and KEEP_LISTS["on"]) else None),
+                      records=(dict(sparse_hits=keep.get("sparse_hits"), sparse_cap=sparse_cap, entries=keep["entries"], pairs=keep["pairs"],
+                                    n_entries=keep["n_entries"], batch_rows=(keep["batch_rows"].view(-1, 2) if rows else None),
+                                    ray_order=(keep["ray_order"][R:] if SORT_RAYS["on"] else None), surf_cnt=keep["surf_cnt"], surf_off=keep["surf_off"])
+                               if (cap and KEEP_LISTS["on"] and "hit_state" in keep) else None))
     if cap:
         if "hit_state" in keep and not KEEP_LISTS["on"]:
             # the record backward reads the hit counts, the per-hit state and the entries / pairs -- not the lists themselves (rays x capacity
@@ -522,7 +572,7 @@ def _build_stream(dev):
 class _TraceSurfels(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ray_o, ray_d, v, means3D, grads3D, shs, colors_precomp, others_precomp, opacities, scales, rotations,
-                cov3D_precomp, tracer_settings, start_from_first, nodes, caps=None, chain=None):
+                cov3D_precomp, tracer_settings, start_from_first, nodes, caps=None, chain=None, barred_leaves=()):
         ctx.set_materialize_grads(False)          # outputs the loss does not use arrive as None (= NULL upstream pointer), not as buffers of zeros
         none = lambda t: None if (t is None or t.numel() == 0) else t
         from .raster import _store                       # fp16 feature storage selected (envgs_amd.set_feature_storage): half copies made HERE, fp32 gradients
@@ -533,7 +583,10 @@ class _TraceSurfels(torch.autograd.Function):
         # deferred surfel gradients (set_deferred_surfel_gradients) are only safe when autograd does nothing with them but MOVE them into .grad: every
         # differentiated surfel input must be a leaf (a non-leaf's gradient is fed to the next backward node on the current stream at once); whether
         # it has a .grad to add into, or hooks that would read it, is looked at when the backward runs
-        ctx.surfel_inputs = [t for t in (means3D, grads3D, shs, colors_precomp, opacities, scales, rotations) if t is not None and t.requires_grad and t.is_leaf]
+        # (barred_leaves: the leaves SurfelTracer.forward put behind a barrier of this call -- checked like bare leaves: the barrier makes a second
+        #  consumer safe, the check keeps gradient accumulation and hooks on the stream-ordered backward as before)
+        ctx.surfel_inputs = list(barred_leaves) + [t for t in (means3D, grads3D, shs, colors_precomp, opacities, scales, rotations)
+                                                   if t is not None and t.requires_grad and t.is_leaf]
         ctx.surfel_leaves = all(t.is_leaf or _behind_barrier(t) for t in (means3D, grads3D, shs, colors_precomp, opacities, scales, rotations)
                                 if t is not None and t.requires_grad)           # (or the output of defer_barrier: that node joins before anyone else sees the gradient)
         ctx.in_dtypes = tuple(None if t is None else t.dtype for t in (ray_o, ray_d, means3D, grads3D, shs, colors_precomp,
@@ -550,7 +603,7 @@ class _TraceSurfels(torch.autograd.Function):
         order = ("ray_o", "ray_d", "means3D", "grads3D", "shs", "colors_precomp", "others_precomp", "opacities", "scales", "rotations")
         vals = [None if (g[k] is None or dt is None) else g[k].to(dt) for k, dt in zip(order, ctx.in_dtypes)]
         ro, rd, m3, g3, sh, col, oth, op, sc, rot = vals
-        return ro, rd, None, m3, g3, sh, col, oth, op, sc, rot, None, None, None, None, None, None
+        return ro, rd, None, m3, g3, sh, col, oth, op, sc, rot, None, None, None, None, None, None, None
 
 
 class SurfelTracer(nn.Module):
@@ -659,13 +712,14 @@ class SurfelTracer(nn.Module):
     def set_deferred_surfel_gradients(self, on=True):
         """OPTIONAL, not part of the reference interface (include/envgs_trace.h: defer_reduce).  The backward of this tracer's bounce-free calls
         returns as soon as the RAY gradients are complete on the current stream; the gradients of the surfel parameters are finished on a stream
-        of the library's own, beside whatever the caller runs next (the base pass's backward: 0.2 ms of the EnvGS step).  That is only sound when
-        autograd does nothing with those gradients but move them into `.grad`, which the autograd node CHECKS per call -- every differentiated
-        surfel input a leaf, without a `.grad` to add into and without tensor / post-accumulate hooks; anything else (activated parameters as in
-        the unchanged EasyVolcap caller, gradient accumulation over several backward passes, GradExchange's flat `.grad` views) takes the
-        stream-ordered backward -- and when each parameter receives its gradient from ONE traced call (or bounce chain) per backward pass.  What
-        the caller still promises: to call envgs_amd.tracing.join_deferred_gradients() before anything reads the gradients -- FusedAdam.step and
-        the next traced call do."""
+        of the library's own, beside whatever the caller runs next (the base pass's backward: 0.2 ms of the EnvGS step).  Guaranteed: no deferred
+        gradient reaches anything but a barrier that orders the stream after the tail first.  A surfel input must be the output of defer_barrier /
+        leaf_barrier or a leaf; a bare leaf is put behind a leaf_barrier created at the call -- so a leaf that other ops of the graph also use (a
+        regulariser, a second traced call) receives the sum of complete gradients -- and the autograd node CHECKS per call that it has no `.grad`
+        to add into and no tensor / post-accumulate hooks.  Anything else (activated parameters without a barrier, gradient accumulation over
+        several backward passes, GradExchange's flat `.grad` views) takes the stream-ordered backward.  Each parameter must receive its gradient
+        from ONE traced call (or bounce chain) per barrier.  The tail stays pending after backward() unless a defer_barrier released it:
+        join_deferred_gradients() releases it (FusedAdam.step, GradExchange and the next traced call do that themselves)."""
         self.caps.defer_reduce = bool(on)
 
     def set_colour_only_backward(self, on=True):
@@ -730,13 +784,27 @@ class SurfelTracer(nn.Module):
             self.nodes.record_stream(cur)
         if grads3D is None:
             grads3D = torch.zeros_like(means3D)
+        barred = ()
+        if self.caps.defer_reduce and torch.is_grad_enabled():
+            # deferred surfel gradients: a leaf handed over bare may have other consumers in the graph (a regulariser on the opacities, a second
+            # traced call) whose gradients autograd would add to the tracer's before the tail has finished -- it goes through a leaf_barrier created
+            # here, whose backward orders the stream after the tail first.  Always correct; it overlaps less than a barrier created before the base
+            # pass (envgs_step.envgs_forward)
+            surf = [means3D, grads3D, shs, colors_precomp, opacities, scales, rotations]
+            idx = [i for i, t in enumerate(surf) if t is not None and t.requires_grad and t.is_leaf]
+            if idx:
+                barred = tuple(surf[i] for i in idx)
+                outs = leaf_barrier(*barred)
+                for i, t in zip(idx, outs if isinstance(outs, tuple) else (outs,)):
+                    surf[i] = t
+                means3D, grads3D, shs, colors_precomp, opacities, scales, rotations = surf
         e = torch.Tensor([])
         args = (v, means3D, grads3D, e if shs is None else shs, e if colors_precomp is None else colors_precomp,
                 e if others_precomp is None else others_precomp, opacities, scales, rotations, None)
         depth = int(tracer_settings.max_trace_depth)
         if depth == 0 or ray_o.numel() == 0 or means3D.shape[0] == 0:
-            return _TraceSurfels.apply(ray_o, ray_d, *args, tracer_settings._replace(max_trace_depth=0), bool(start_from_first), self.nodes, self.caps)
-        return self._forward_bounces(ray_o, ray_d, args, tracer_settings, bool(start_from_first))
+            return _TraceSurfels.apply(ray_o, ray_d, *args, tracer_settings._replace(max_trace_depth=0), bool(start_from_first), self.nodes, self.caps, None, barred)
+        return self._forward_bounces(ray_o, ray_d, args, tracer_settings, bool(start_from_first), barred)
 
     def bounce_caps(self, k):
         """Bounce stage k traces a different ray population (fewer, less coherent rays) than stage 0: its own capacity state."""
@@ -745,7 +813,7 @@ class SurfelTracer(nn.Module):
             st[k] = CapState(self.caps.cap)
         return st[k]
 
-    def _forward_bounces(self, ray_o, ray_d, args, settings, start_from_first):
+    def _forward_bounces(self, ray_o, ray_d, args, settings, start_from_first, barred=()):
         """max_trace_depth > 0 (gaussian2d_sampler.py:413-426, optix_utils.py:117-118): every stage is one bounce-free traced call
         (the differentiable `_TraceSurfels` node, list path), glued by two differentiable kernels of envgs_amd.fused (bounce_rays: the next
         stage's rays; bounce_blend: the next stage's colour blended back -- one launch each way; round 4, torch expressions until then):
@@ -771,7 +839,7 @@ class SurfelTracer(nn.Module):
         self.caps.colour_only = False                  # (its depth / accumulation / normal / specular outputs build the next stage's rays)
         chain = _BounceChain() if self.caps.defer_reduce else None        # set_deferred_surfel_gradients: the stages' backwards share their accumulators
         try:
-            out0 = _TraceSurfels.apply(o, d, *args, s0, start_from_first, self.nodes, self.caps, (chain, 0) if chain else None)
+            out0 = _TraceSurfels.apply(o, d, *args, s0, start_from_first, self.nodes, self.caps, (chain, 0) if chain else None, barred)
         finally:
             self.caps.colour_only = was
         stages = [dict(o=o, d=d, out=out0, idx=torch.arange(R, device=dev), sel=None)]
@@ -793,7 +861,7 @@ class SurfelTracer(nn.Module):
             bc.colour_only = k == depth                 # the last stage's other outputs go into `mid` (no gradient) and nowhere else
             bc.defer_reduce = chain is not None
             try:
-                out = _TraceSurfels.apply(o2, d2, *args, s0, 2, self.nodes, bc, (chain, k) if chain else None)
+                out = _TraceSurfels.apply(o2, d2, *args, s0, 2, self.nodes, bc, (chain, k) if chain else None, barred)
             finally:
                 bc.colour_only, bc.defer_reduce = was_k  # (the promises are this call's, not the stage state's: ADVICE r4)
             stages.append(dict(o=o2, d=d2, out=out, idx=p["idx"].index_select(0, sel), sel=sel))
@@ -829,6 +897,12 @@ def last_hit_lists():
     return hl[:, :, 1].contiguous(), hl[:, :, 0].contiguous(), n_used, hit_cnt
 
 
+def last_record_scratch():
+    """Tests (KEEP_LISTS on): what the most recent list-path forward handed its record backward -- the sparse-hit list and the capacity passed for
+    it, the (batch, surfel) entries and their pairs, the per-batch entry counts and row ranges, the sorted slot -> ray order.  None without records."""
+    return LAST_STATS.get("records")
+
+
 def last_entry_counts():
     """Diagnostics of the last list-path forward that prepared a record backward: (entries merged in the per-batch tables,
     single entries that found no room in a table).  Host sync."""
@@ -840,11 +914,12 @@ def last_entry_counts():
 
 
 def last_trace_counts():
-    """(composited hits, BVH node visits, traversal rounds) of the most recent forward (synchronises)."""
+    """(composited hits, BVH node visits, traversal rounds) of the most recent forward (synchronises).  sparse_invalid: entries of the sparse-hit
+    list that the most recent backward of that forward had to skip (include/envgs_trace.h: sparse_hits; always 0 unless the list is corrupt)."""
     c = LAST_STATS.get("counters")
     if c is None:
         return None
     w = c.cpu()
     v = w[2:20].view(torch.int64)
     return dict(coop_cycles=dict(expand=int(v[6]), walk=int(v[7]), wait=int(v[8])), hits=int(v[0]), node_visits=int(v[1]), rounds=int(v[2]), found=int(v[3]), packet_nodes=int(v[4]), packet_leaves=int(v[5]),
-                max_list=int(w[1]), sparse_hits=int(w[64]), cap=LAST_STATS["caps"].cap, compact_rows=LAST_STATS.get("rows", 0), rays_without_rows=int(w[21]), rays=LAST_STATS["R"], stack_overflows=int(w[20]))
+                max_list=int(w[1]), sparse_hits=int(w[64]), sparse_invalid=int(w[66]), cap=LAST_STATS["caps"].cap, compact_rows=LAST_STATS.get("rows", 0), rays_without_rows=int(w[21]), rays=LAST_STATS["R"], stack_overflows=int(w[20]))

@@ -126,7 +126,10 @@ typedef struct envgs_trace_lists {
                                 of the benchmark view hold 1-4 hits (1.4 % of the hits): the forward files the hits of such entries here as
                                 (sorted ray slot, list position, surfel id, record slot) -- one gradient record PER HIT -- instead of creating the entry,
                                 and envgs_trace_backward differentiates them one lane per hit (sparse_hits_bwd).  NULL / 0 = every entry takes the batch
-                                kernel; hits that find no room here do too.  counters[64] = hits filed, counters[65] = entries left to the batch kernel.
+                                kernel; hits that find no room here do too (space is claimed only when it fits and never given back: a smaller
+                                later claim may still fit).  counters[64] = hits filed, counters[65] = entries left to the batch kernel; the backward
+                                checks every filed entry before it uses it and counts the ones it had to skip in counters[66] (zeroed by every
+                                envgs_trace_backward; always 0 unless the list is corrupt).
                                 Worth it for INCOHERENT batches only (a filed hit costs ~12x a hit of a full entry: bounce rays off rough geometry,
                                 1-2 hits per entry: 59 -> 48 ms per step; the coherent benchmark views: +-0): envgs_amd.tracing passes the buffer when
                                 the tracer's previous call averaged fewer than 6 composited hits per entry */

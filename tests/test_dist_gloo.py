@@ -141,3 +141,33 @@ def test_single_process_is_a_noop():
     a = torch.zeros(3, requires_grad=True); a.grad = torch.ones(3)
     assert edist.allreduce_grads([a]) == 0 and torch.equal(a.grad, torch.ones(3))
     assert edist.shard_views(8, 0, 1) == list(range(8))
+
+
+def test_grad_exchange_joins_deferred_tracer_gradients_before_reading_them(monkeypatch):
+    """GradExchange reads the `.grad` views a deferring tracer backward may still be finishing on the library's stream: _launch() (the exchange of a
+    bucket) and finish() make the current stream wait for them first -- envgs_amd.tracing.join_deferred_gradients, stubbed here -- also with one
+    process (finish() exchanges nothing then, but the caller reads the views next)."""
+    from envgs_amd import dist as edist, tracing
+    events = []
+    monkeypatch.setattr(tracing, "join_deferred_gradients", lambda: events.append("join"))
+
+    def fake_exchange(flat, **kw):
+        events.append(("exchange", flat.numel()))
+        return lambda: events.append("done")
+    monkeypatch.setattr(edist, "exchange_flat", fake_exchange)
+    a = torch.zeros(3, requires_grad=True); b = torch.zeros(2, requires_grad=True)
+    ex = edist.GradExchange(lambda: [[a], [b]], overlap=False)
+    assert not ex.enabled                                  # (no process group)
+    ex.begin_step()
+    (a.sum() + 2 * b.sum()).backward()
+    assert ex.finish() == 0 and events == ["join"]
+    events.clear()
+    ex.enabled = True                                      # as if a process group of one were up: finish() launches and completes both buckets
+    ex.begin_step()
+    (a.sum() + 2 * b.sum()).backward()
+    ex._launch(ex.buckets[0])
+    assert events == ["join", ("exchange", 3)]
+    events.clear()
+    assert ex.finish() == (3 + 2) * 4
+    assert events == ["join", "join", ("exchange", 2), "done", "done"]
+    assert a.grad.tolist() == [1.0] * 3 and b.grad.tolist() == [2.0] * 2

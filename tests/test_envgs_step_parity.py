@@ -305,3 +305,67 @@ def test_step_with_deferred_env_surfel_gradients():
         if gk is not None:
             big = gk.abs() > 1e-3 * gk.abs().max()
             assert float((a - b)[big].abs().max()) <= 1e-5 if big.any() else True, k
+
+
+def _env_opacity_loss(opacity):
+    """The reference supervisor's sparse env-opacity term (envgs_supervisor.py:140-149, env_opacity_loss on output.env_opacity =
+    self.env.get_opacity, envgs_sampler.py:479): mean(log v + log(1 - v)), v = clamp(opacity, 1e-3, 1 - 1e-3), weight 0.01."""
+    v = opacity.clamp(1e-3, 1 - 1e-3)
+    return 0.01 * (torch.log(v) + torch.log(1 - v)).mean()
+
+
+@pytest.mark.parametrize("variant", ["leaf", "activated"])
+def test_step_with_deferred_env_surfel_gradients_and_env_opacity_loss(variant):
+    """Deferred env-surfel gradients when the env opacities have a SECOND consumer in the graph: the reference's env-opacity regulariser.
+    leaf: the term reads the leaf env["opacities"] that also feeds the tracer -- autograd adds the two gradients on arrival, so the tracer's must be
+    complete by then (the leaf_barrier envgs_forward puts every env leaf behind orders the stream after the deferred tail first).  activated: raw opacities, the tracer sees sigmoid(raw)
+    through the barrier and the term a second sigmoid of its own.  Every gradient = the stream-ordered step's within 2e-5 of its largest element."""
+    import diff_surfel_rasterization_wet_ch05 as pkg
+    import diff_surfel_tracing as tpkg
+    from envgs_amd import tracing
+    dev = torch.device("cuda:0")
+    was = (envgs_step.FUSED["on"], envgs_step.DEFER["on"])
+    res, deferred_calls = {}, {}
+    try:
+        envgs_step.FUSED["on"] = True
+        for defer in (False, True):
+            envgs_step.DEFER["on"] = defer
+            base, env, cam = _scene(dev)
+            if variant == "leaf":
+                leaves, feed = env, env
+                reg = _env_opacity_loss(env["opacities"])
+            else:
+                leaves = dict(env)
+                leaves["opacities"] = torch.logit(env["opacities"].detach().clamp(1e-4, 1 - 1e-4)).requires_grad_(True)
+                feed = dict(env, opacities=torch.sigmoid(leaves["opacities"]))
+                reg = None
+            n_def = [0]
+            orig = tracing.trace_backward
+            def counting(saved, *a, **kw):
+                r = orig(saved, *a, **kw)
+                n_def[0] += int(saved["lists"].defer_reduce & 1)
+                return r
+            tracing.trace_backward = counting
+            try:
+                out = envgs_step.envgs_forward(pkg, tpkg, tpkg.SurfelTracer(), cam, synth.get_rays(cam), base, feed, torch.zeros(3, device=dev),
+                                               torch.tensor([0.1, 0.2, 0.3], device=dev), torch.tensor([2], device=dev))
+                if reg is None:
+                    reg = _env_opacity_loss(torch.sigmoid(leaves["opacities"]))      # (a second activation of the raw parameter)
+                dcol, dall = _upstream(cam.image_height, cam.image_width, dev)
+                ((out["rgb"] * dcol).sum() + (out["base"]["allmap"] * dall).sum() + reg).backward()
+            finally:
+                tracing.trace_backward = orig
+            # leaves: behind leaf_barrier, pending until a join releases the tail; an activated tensor's defer_barrier joins inside backward()
+            assert tracing._DEFERRED["pending"] == (defer and variant == "leaf")
+            tracing.join_deferred_gradients()
+            deferred_calls[defer] = n_def[0]
+            torch.cuda.synchronize()
+            res[defer] = {("env." + k): v.grad.clone() for k, v in leaves.items() if v.grad is not None} | \
+                         {("base." + k): v.grad.clone() for k, v in base.items() if v.grad is not None}
+    finally:
+        envgs_step.FUSED["on"], envgs_step.DEFER["on"] = was
+    assert deferred_calls == {False: 0, True: 1}
+    assert set(res[False]) == set(res[True]) and "env.opacities" in res[False]
+    for k in res[False]:
+        a, b = res[False][k], res[True][k]
+        assert (float(a.abs().max()) > 0 or not k.startswith("env.")) and float((a - b).abs().max()) <= 2e-5 * float(a.abs().max()) + 1e-12, k

@@ -146,7 +146,7 @@ def _parity(test, g, ro, rd, bg, deg, use_sh, sff, gr_scale=1.0, seed=9, which=G
     for k in which:
         if got[k] is None or want[k] is None: continue
         check_close(test, k, got[k].cpu().numpy(), want[k], excluded=nfr, cond=cond[k], unc=unc[k])
-    return dict(ref=ref, cnt=cnt, outs=outs, n_listed=n_listed, R=R, extra=extra)
+    return dict(ref=ref, cnt=cnt, outs=outs, n_listed=n_listed, R=R, extra=extra, got=got, inputs=(ro, rd, gr))
 
 
 @pytest.mark.parametrize("use_sh,camera,deg,P,R", [(True, True, 3, 150, 400), (False, False, 0, 150, 400), (True, False, 2, 2000, 1024),
@@ -179,6 +179,10 @@ class _Switch:
             elif k == "rows_per_ray": self.old[k] = dict(tracing.ROW_CAP); tracing.ROW_CAP["force_per_ray"] = v
             elif k == "compact": self.old[k] = tracing.COMPACT["on"]; tracing.COMPACT["on"] = v
             elif k == "sparse": self.old[k] = tracing.SPARSE["mode"]; tracing.SPARSE["mode"] = v
+            elif k == "sparse_cap": self.old[k] = tracing.SPARSE["cap"]; tracing.SPARSE["cap"] = v
+            elif k == "sparse_poison": self.old[k] = tracing.SPARSE["poison"]; tracing.SPARSE["poison"] = v
+            elif k == "sparse_max":                                  # ENVGS_DBG_SPARSE: value - 1 = the largest hit count of an entry filed per hit
+                lib = _lib.load(); self.old[k] = lib.envgs_debug_get(5); lib.envgs_debug_set(5, v + 1)
             elif k == "sort_rays": self.old[k] = tracing.SORT_RAYS["on"]; tracing.SORT_RAYS["on"] = v
             elif k == "debug_trace":
                 lib = _lib.load(); self.old[k] = lib.envgs_debug_get(0); lib.envgs_debug_set(0, v)
@@ -191,6 +195,9 @@ class _Switch:
             elif k == "rows_per_ray": tracing.ROW_CAP.clear(); tracing.ROW_CAP.update(v)
             elif k == "compact": tracing.COMPACT["on"] = v
             elif k == "sparse": tracing.SPARSE["mode"] = v
+            elif k == "sparse_cap": tracing.SPARSE["cap"] = v
+            elif k == "sparse_poison": tracing.SPARSE["poison"] = v
+            elif k == "sparse_max": _lib.load().envgs_debug_set(5, v)
             elif k == "sort_rays": tracing.SORT_RAYS["on"] = v
             elif k == "debug_trace": _lib.load().envgs_debug_set(0, v)
         if self.lib_kind is not None:
@@ -577,7 +584,7 @@ def test_trace_sparse_entries_vs_oracle(case, request):
     precomputed colours, with and without `others`, the generic and the colour-only backward, and a batch whose merge table overflows (those
     one-hit entries are filed too: the batch kernel sees no singles)."""
     from envgs_amd import tracing
-    kw = dict(hip_ctx=_Switch(sparse="on"), after_hip=tracing.last_entry_counts)
+    kw = dict(hip_ctx=_Switch(sparse="on", sparse_poison=SPARSE_POISON), after_hip=lambda: (tracing.last_entry_counts(), _check_sparse_list(request.node.name)))
     if case == "camera_sh_others":
         g, ro, rd = trace_scene(P=150, R=400, seed=7, camera=True)
         res = _parity(request.node.name, g, ro, rd, torch.tensor([0.3, 0.1, 0.7]), 3, True, True, **kw)
@@ -595,7 +602,7 @@ def test_trace_sparse_entries_vs_oracle(case, request):
         ro = (torch.rand(R, 3, generator=gen) * 2 - 1) * 2.0
         rd = torch.randn(R, 3, generator=gen); rd = rd / rd.norm(dim=-1, keepdim=True)
         res = _parity(request.node.name, g, ro, rd, torch.tensor([0.1, 0.0, 0.2]), 3, True, False, seed=34, **kw)
-        assert res["extra"][1] == 0, "the table-overflow singles were meant to be filed as sparse hits"
+        assert res["extra"][0][1] == 0, "the table-overflow singles were meant to be filed as sparse hits"
     elif case == "colour_only_vs_batch_kernel":
         # the colour-only form (the EnvGS step: only rgb carries a gradient, dpt / acc / norm / aux arrive as None): sparse entries on against off
         import diff_surfel_tracing as mod
@@ -629,7 +636,233 @@ def test_trace_sparse_entries_vs_oracle(case, request):
         g["scales"] = g["scales"] * 0.35
         res = _parity(request.node.name, g, ro, rd, torch.tensor([0.3, 0.1, 0.7]), 2, True, False, zero_geo_grads=True, **kw)
     assert res["cnt"]["sparse_hits"] > 0, "no hit took the sparse path"
-    assert res["cnt"]["sparse_hits"] + res["extra"][0] <= res["cnt"]["hits"]
+    assert res["cnt"]["sparse_hits"] + res["extra"][0][0] <= res["cnt"]["hits"]
+    # (and, tighter: every composited hit is differentiated exactly once -- filed, a single or one hit of its entry -- _check_sparse_list)
+    assert res["extra"][1][0] == res["cnt"]["sparse_hits"] and res["extra"][1][2] <= res["cnt"]["hits"]
+
+
+SPARSE_POISON = -1                  # what the sparse-hit list holds before the forward (tracing.SPARSE["poison"]): no field of a written entry can be 0xFFFFFFFF
+
+
+def _check_sparse_list(test, cap_req=None):
+    """The sparse-hit list of the most recent forward (include/envgs_trace.h: sparse_hits) against the kept hit lists (KEEP_LISTS), after its backward:
+      * counters[64] <= the capacity passed, and the backward skipped no entry (sparse_invalid == 0);
+      * each of the counters[64] filed entries is a composited hit of its ray (list position below n_used, the surfel of that list slot), and no slot
+        holds the poison value; no (ray, list position) and no gradient record appears twice -- over the filed hits, the (batch, surfel) entries
+        and the one-hit singles together, whose record slots are exactly the call's records;
+      * every composited hit is differentiated exactly once: filed, a single, or one of the hits of its (batch, surfel) entry -- whose hit count is
+        the number of such hits.
+    Returns (hits filed, capacity passed, composited hits)."""
+    from envgs_amd import tracing
+    cnt = tracing.last_trace_counts()
+    rec = tracing.last_record_scratch()
+    assert rec is not None and rec["sparse_hits"] is not None, "the forward was given no sparse-hit list"
+    ids, _, n_used, hit_cnt = [x.cpu().numpy() for x in tracing.last_hit_lists()]
+    R, cap = ids.shape
+    P = int(rec["surf_cnt"].numel() // tracing.NCOPY)
+    rows = rec["sparse_hits"].shape[0]
+    sc = rec["sparse_cap"]
+    assert sc == (rows if cap_req is None else min(cap_req, rows)), (sc, cap_req, rows)
+    filed = cnt["sparse_hits"] & 0xFFFFFFFF
+    record(test, "sparse_invalid", float(cnt["sparse_invalid"]), "(counters[66]; %d filed of capacity %d)" % (filed, sc))
+    assert cnt["sparse_invalid"] == 0, cnt["sparse_invalid"]
+    assert filed <= sc, (filed, sc)
+    record(test, "sparse_filed_over_cap", filed / max(sc, 1), "(counters[64] = %d <= cap %d)" % (filed, sc))
+    order = rec["ray_order"].cpu().numpy().astype(np.int64) if rec["ray_order"] is not None else np.arange(R)
+    slot_of = np.empty(R, np.int64); slot_of[order] = np.arange(R)
+    scnt = rec["surf_cnt"].cpu().numpy().astype(np.int64).reshape(-1)
+    soff = rec["surf_off"].cpu().numpy().astype(np.int64).reshape(-1)
+    n_rec = int(soff[-1]) if P > 0 else 0
+    # the filed hits
+    sp = rec["sparse_hits"][:filed].cpu().numpy().astype(np.int64) & 0xFFFFFFFF
+    assert not (sp == (SPARSE_POISON & 0xFFFFFFFF)).any(), "a slot below counters[64] was never written"
+    f_slot, f_k, f_sid, f_rank = sp.T
+    assert (f_slot < R).all() and (f_sid < P).all()
+    f_r = order[f_slot]
+    assert (hit_cnt[f_r] <= cap).all() and (f_k < n_used[f_r]).all(), "a filed entry names no composited hit"
+    assert (ids[f_r, f_k] == f_sid).all(), "a filed entry names the wrong surfel"
+    f_key = f_r * cap + f_k
+    assert np.unique(f_key).size == filed, "a (ray, list position) was filed twice"
+    rec_ci, rec_rank = [f_sid * tracing.NCOPY + ((f_slot >> 6) & (tracing.NCOPY - 1))], [f_rank]
+    # the (batch, surfel) entries and the singles of every batch
+    ne = rec["n_entries"].cpu().numpy().astype(np.int64)
+    ent = rec["entries"].reshape(-1).cpu().numpy().view(np.uint64).astype(np.uint64) if rec["entries"].dtype == torch.int64 else None
+    prs = rec["pairs"].reshape(-1).cpu().numpy().astype(np.int64) & 0xFFFFFFFF
+    nb = ne.shape[0]
+    if rec["batch_rows"] is not None:
+        br = rec["batch_rows"].cpu().numpy().astype(np.int64)
+        start, region = br[:, 0], br[:, 1]
+    else:
+        start, region = np.arange(nb) * 64 * cap, np.full(nb, 64 * cap)
+    d_b, d_sid, d_hits, s_b, s_key = [], [], [], [], []
+    for b in range(nb):
+        D, NF = int(ne[b, 0]), int(ne[b, 1])
+        if D:
+            ev = ent[start[b]:start[b] + D]
+            sid = (ev & np.uint64(0xFFFFFF)).astype(np.int64)
+            d_b.append(np.full(D, b)); d_sid.append(sid); d_hits.append(((ev >> np.uint64(24)) & np.uint64(0xFF)).astype(np.int64) + 1)
+            rec_ci.append(sid * tracing.NCOPY + (b & (tracing.NCOPY - 1))); rec_rank.append(((ev >> np.uint64(32)) & np.uint64(0xFFFFFF)).astype(np.int64))
+        if NF:
+            top = start[b] + region[b] - 1 - np.arange(NF)
+            ev, pv = ent[top], prs[top]
+            sid = (ev & np.uint64(0xFFFFFF)).astype(np.int64)
+            r_ = order[b * 64 + (pv >> 16)]; k_ = pv & 0xFFFF
+            assert (k_ < n_used[r_]).all() and (ids[r_, k_] == sid).all(), "a single names no composited hit of its surfel"
+            s_b.append(np.full(NF, b)); s_key.append(r_ * cap + k_)
+            rec_ci.append(sid * tracing.NCOPY + (b & (tracing.NCOPY - 1))); rec_rank.append((ev >> np.uint64(32)).astype(np.int64))
+    cat = lambda xs: np.concatenate(xs) if xs else np.zeros(0, np.int64)
+    d_b, d_sid, d_hits, s_key = cat(d_b), cat(d_sid), cat(d_hits), cat(s_key)
+    ci, rk = cat(rec_ci), cat(rec_rank)
+    assert (rk < scnt[ci]).all(), "a record slot beyond its surfel's records"
+    rslot = soff[ci] - scnt[ci] + rk
+    assert np.unique(rslot).size == rslot.size, "a gradient record slot was handed out twice"
+    assert rslot.size == n_rec and (rslot < n_rec).all(), (rslot.size, n_rec)
+    assert np.unique(d_b * P + d_sid).size == d_b.size and np.unique(s_key).size == s_key.size
+    # every composited hit of a listed ray, exactly once
+    listed = hit_cnt <= cap
+    rr = np.repeat(np.arange(R), np.where(listed, n_used, 0))
+    kk = np.arange(rr.size) - np.repeat(np.cumsum(np.where(listed, n_used, 0)) - np.where(listed, n_used, 0), np.where(listed, n_used, 0))
+    h_key, h_sid, h_b = rr * cap + kk, ids[rr, kk].astype(np.int64), slot_of[rr] >> 6
+    in_f, in_s = np.isin(h_key, f_key), np.isin(h_key, s_key)
+    dk = d_b * P + d_sid
+    in_d = np.isin(h_b * P + h_sid, dk)
+    cover = in_f.astype(int) + in_s.astype(int) + in_d.astype(int)
+    assert (cover == 1).all(), "composited hits differentiated %d times: %d hits" % (int(cover[cover != 1][0]), int((cover != 1).sum()))
+    assert in_f.sum() == filed and in_s.sum() == s_key.size
+    u, c = np.unique(h_b[in_d] * P + h_sid[in_d], return_counts=True)
+    srt = np.argsort(dk)
+    assert np.array_equal(u, dk[srt]) and np.array_equal(c, d_hits[srt]), "an entry's hit count is not the number of its hits"
+    record(test, "sparse_exactly_once", 0.0, "(%d composited hits: %d filed, %d singles, %d in %d entries)" % (h_key.size, filed, s_key.size, int(in_d.sum()), dk.size))
+    return filed, sc, h_key.size
+
+
+def _incoherent_scene(R, seed=33):
+    """Incoherent rays through a dense set: a 64-ray batch blends more distinct surfels than its merge table holds (one-hit singles)."""
+    gen = torch.Generator().manual_seed(seed)
+    P = 6000
+    means = (torch.rand(P, 3, generator=gen) * 2 - 1) * 2.0
+    q = torch.randn(P, 4, generator=gen)
+    g = dict(means3D=means, scales=0.12 + 0.1 * torch.rand(P, 2, generator=gen), rotations=q / q.norm(dim=-1, keepdim=True),
+             opacities=torch.sigmoid(torch.randn(P, 1, generator=gen) - 2.0), shs=torch.randn(P, 16, 3, generator=gen) * 0.3,
+             others=torch.rand(P, 2, generator=gen), colors_precomp=torch.rand(P, 3, generator=gen))
+    ro = (torch.rand(R, 3, generator=gen) * 2 - 1) * 2.0
+    rd = torch.randn(R, 3, generator=gen); rd = rd / rd.norm(dim=-1, keepdim=True)
+    return g, ro, rd
+
+
+# scene -> (scene tensors, _parity keywords, switches of every run); "contention": enough incoherent rays for TWO forward segments on two streams
+# (>= 512 batches) and entries of up to 16 hits filed per hit, so that most 64-surfel chunks claim list space at once and many claims fail
+SPARSE_CAP_SCENES = {
+    "many_small_surfels": lambda: (_small_surfels(), dict(deg=2, bg=torch.tensor([0.3, 0.1, 0.7]), seed=9), {}),
+    "incoherent_table_overflow": lambda: (_incoherent_scene(1000), dict(deg=3, bg=torch.tensor([0.1, 0.0, 0.2]), seed=34), {}),
+    "contention": lambda: (_incoherent_scene(33000, seed=35), dict(deg=3, bg=torch.tensor([0.1, 0.0, 0.2]), seed=36, gr_scale=1.0 / 64), dict(sparse_max=16)),
+}
+_SPARSE_BASELINES = {}
+
+
+def _small_surfels():
+    g, ro, rd = trace_scene(P=2000, R=1024, seed=7, camera=False)
+    g["scales"] = g["scales"] * 0.35
+    return g, ro, rd
+
+
+def _sparse_baseline(scene):
+    """Per scene, once: the rays the oracle's audit keeps, and on them the sparse-off run (gradients) and the uncapped sparse-on run (hits it files)."""
+    if scene in _SPARSE_BASELINES:
+        return _SPARSE_BASELINES[scene]
+    from envgs_amd import tracing
+    (g, ro, rd), kw, sw = SPARSE_CAP_SCENES[scene]()
+    ro, rd, _, _, _ = _drop_fragile("sparse_cap." + scene, g, ro, rd, False, sh_degree=kw["deg"])
+    R = ro.shape[0]
+    gen = torch.Generator().manual_seed(kw["seed"])
+    sc = kw.get("gr_scale", 1.0)
+    gr = [torch.randn(R, 3, generator=gen) * sc, torch.randn(R, generator=gen) * sc, torch.randn(R, generator=gen) * sc,
+          torch.randn(R, 3, generator=gen) * sc, torch.randn(R, 2, generator=gen) * sc]
+    runs = {}
+    for mode in ("off", "on"):
+        with _Switch(sparse=mode, **sw):
+            outs, L, o, d, g3 = _run_hip(g, ro, rd, kw["bg"], kw["deg"], True, False, grads=gr)
+            filed = tracing.last_trace_counts()["sparse_hits"]
+        runs[mode] = (dict(rgb=outs[0], dpt=outs[1], acc=outs[2], norm=outs[3], aux=outs[5], wet=outs[7], dmeans3D=L["means3D"].grad, grads3D=g3.grad,
+                           dscales=L["scales"].grad, drots=L["rotations"].grad, dopacities=L["opacities"].grad, dothers=L["others"].grad,
+                           dcolor=L["shs"].grad, dray_o=o.grad, dray_d=d.grad), filed)
+    assert runs["off"][1] == 0 and runs["on"][1] > 128, (scene, runs["on"][1])
+    _SPARSE_BASELINES[scene] = (g, ro, rd, gr, kw, sw, {k: v.detach().cpu().numpy() for k, v in runs["off"][0].items()}, runs["on"][1])
+    return _SPARSE_BASELINES[scene]
+
+
+def _close_to(test, got, ref, names):
+    for k in names:
+        a, b = np.asarray(got[k], np.float64).reshape(-1), np.asarray(ref[k], np.float64).reshape(-1)
+        assert a.shape == b.shape, (k, a.shape, b.shape)
+        err = float(np.abs(a - b).max())
+        record(test, "vs_sparse_off." + k, err / (float(np.abs(b).max()) + 1e-30), "(max|a-b| / max|b|, bound 2e-5)")
+        assert err <= 2e-5 * float(np.abs(b).max()) + 1e-12, (k, err)
+
+
+@pytest.mark.parametrize("cap_kind", ["1", "64", "half", "uncapped_minus_1"])
+@pytest.mark.parametrize("scene", list(SPARSE_CAP_SCENES))
+def test_trace_sparse_list_at_every_capacity(scene, cap_kind, request):
+    """The sparse-hit list when it does NOT hold every hit the forward would file (include/envgs_trace.h: sparse_hits -- the C-ABI caller's overflow
+    fall-back: what finds no room takes the batch kernel).  tracing.SPARSE["cap"] passes a capacity of 1, 64, about half and one less than what the
+    uncapped run of the same rays files; the list is poisoned before the forward.  Claims that do not fit must leave no hole and no overlap
+    (register_hits claims by compare-and-swap: [0, counters[64]) is exactly what was filed), so: every output and gradient against the oracle at
+    the 1e-4 contract, the same as the sparse-off run within 2e-5 of each tensor's largest element, and _check_sparse_list's invariants."""
+    g, ro, rd, gr, kw, sw, off, n0 = _sparse_baseline(scene)
+    cap = {"1": 1, "64": 64, "half": n0 // 2, "uncapped_minus_1": n0 - 1}[cap_kind]
+    test = request.node.name
+    res = _parity(test, g, ro, rd, kw["bg"], kw["deg"], True, False, seed=kw["seed"], gr_scale=kw.get("gr_scale", 1.0),
+                  hip_ctx=_Switch(sparse="on", sparse_cap=cap, sparse_poison=SPARSE_POISON, **sw), after_hip=lambda: _check_sparse_list(test, cap))
+    filed, sc, hits = res["extra"]
+    assert sc == cap and filed <= cap
+    # a claim is one 64-surfel chunk of a batch's entries, or the batch's table-overflow singles.  In the incoherent scenes every chunk holds more
+    # than 64 hits and every batch more than 64 singles, so a capacity of 64 admits no claim there and nothing is filed -- legitimately, like 1
+    if cap_kind in ("half", "uncapped_minus_1") or (cap >= 64 and scene == "many_small_surfels"):
+        assert filed > 0, "nothing was filed under a capacity of %d" % cap
+    assert res["R"] == ro.shape[0]
+    got = {k: v.detach().cpu().numpy() for k, v in res["got"].items() if v is not None}
+    got.update(rgb=res["outs"][0].detach().cpu().numpy(), dpt=res["outs"][1].detach().cpu().numpy(), acc=res["outs"][2].detach().cpu().numpy(),
+               norm=res["outs"][3].detach().cpu().numpy(), aux=res["outs"][5].detach().cpu().numpy(), wet=res["outs"][7].detach().cpu().numpy())
+    _close_to(test, got, off, sorted(off))
+
+
+def test_trace_sparse_list_capped_colour_only_backward(request):
+    """The colour-only record backward (only rgb carries an upstream gradient: the EnvGS step) with the sparse-hit list capped at about half of what
+    it would file: every gradient equals the sparse-off run's within 2e-5, and _check_sparse_list's invariants hold."""
+    import diff_surfel_tracing as mod
+    from envgs_amd import tracing
+    dev = torch.device("cuda:0")
+    test = request.node.name
+    g, ro, rd = _small_surfels()
+    up = torch.randn(ro.shape[0], 3, generator=torch.Generator().manual_seed(2)).to(dev)
+    got, n0 = {}, None
+    for mode in ("off", "uncapped", "capped"):
+        sw = dict(sparse="off") if mode == "off" else dict(sparse="on", sparse_poison=SPARSE_POISON, sparse_cap=(None if mode == "uncapped" else n0 // 2))
+        with _Switch(**sw):
+            old_keep = tracing.KEEP_LISTS["on"]
+            tracing.KEEP_LISTS["on"] = True
+            try:
+                L = {k: g[k].to(dev).requires_grad_(True) for k in ("means3D", "scales", "rotations", "opacities", "shs")}
+                o = ro.to(dev).requires_grad_(True); d = rd.to(dev).requires_grad_(True)
+                v, f = synth.get_disks(L["means3D"].detach(), L["scales"].detach(), L["rotations"].detach())
+                tracer = mod.SurfelTracer()
+                tracer.build_acceleration_structure(v, f, rebuild=True)
+                outs = tracer(o, d, v, means3D=L["means3D"], grads3D=None, shs=L["shs"], colors_precomp=None, others_precomp=None, opacities=L["opacities"],
+                              scales=L["scales"], rotations=L["rotations"], cov3D_precomp=None, tracer_settings=_settings(mod, torch.zeros(3), 2, dev, 0, 0.0),
+                              start_from_first=False)
+                (outs[0] * up).sum().backward()
+                torch.cuda.synchronize()
+                if mode == "uncapped":
+                    n0 = _check_sparse_list(test)[0]
+                elif mode == "capped":
+                    filed, sc, _ = _check_sparse_list(test, n0 // 2)
+                    assert 0 < filed <= sc == n0 // 2
+            finally:
+                tracing.KEEP_LISTS["on"] = old_keep
+        got[mode] = {k: t.grad.detach().cpu().numpy() for k, t in L.items()} | dict(dray_o=o.grad.cpu().numpy(), dray_d=d.grad.cpu().numpy())
+    assert n0 > 128
+    _close_to(test, got["capped"], got["off"], sorted(got["off"]))
+    _close_to(test, got["uncapped"], got["off"], sorted(got["off"]))
 
 
 def test_trace_two_segment_forward_pipeline_vs_oracle():
@@ -915,6 +1148,22 @@ def test_trace_colour_only_state_promise():
         run(True, True)
 
 
+class _CountDeferred:
+    """Counts the traced backward calls that deferred their surfel gradients (the ENVGS_TRACE_DEFER bit handed to the library): what says whether
+    the kernel calls deferred when a defer_barrier in front of the tracer has already joined inside backward()."""
+    def __enter__(self):
+        from envgs_amd import tracing
+        self.tracing, self.orig, self.n = tracing, tracing.trace_backward, 0
+        def counting(saved, *a, **kw):
+            r = self.orig(saved, *a, **kw)
+            self.n += int(saved["lists"] is not None and (saved["lists"].defer_reduce & 1))
+            return r
+        tracing.trace_backward = counting
+        return self
+    def __exit__(self, *a):
+        self.tracing.trace_backward = self.orig
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("force_cap", [0, 16])
 def test_trace_deferred_surfel_gradients(force_cap, request):
@@ -1172,6 +1421,55 @@ def test_trace_two_tracers_with_deferred_surfel_gradients():
         for k in a:
             err = float((a[k] - b[k]).abs().max())
             assert float(a[k].abs().max()) > 0 and err <= 2e-5 * float(a[k].abs().max()) + 1e-12, (k, err)
+
+
+@pytest.mark.parametrize("case", ["scale_regulariser", "two_calls_share_leaves"])
+def test_trace_deferred_leaf_with_a_second_consumer(case):
+    """A bare leaf surfel input of a deferring tracer that ANOTHER op of the same graph also uses: a regulariser on the scales, or a second traced
+    call over the same parameters.  Autograd adds the gradients of a leaf's consumers as they arrive, so a deferred gradient handed straight to
+    the leaf would be summed before the library's stream had finished it; SurfelTracer.forward puts bare leaves behind a leaf_barrier created at
+    the call, which orders the stream after the deferred tail first.  The calls still defer, and every gradient = the stream-ordered one within 2e-5 of its largest element."""
+    import diff_surfel_tracing as mod
+    from envgs_amd import tracing
+    dev = torch.device("cuda:0")
+    g, _, _ = trace_scene(P=900, R=4, seed=37, camera=False)
+    rays = []
+    for c in (1, 2):
+        ro, rd = synth.get_rays(synth.orbit_camera(c, H=64, W=64, fx=60.0, radius=1.0))
+        rays.append((ro.reshape(-1, 3).contiguous().to(dev), rd.reshape(-1, 3).contiguous().to(dev)))
+    R = rays[0][0].shape[0]
+    up = [(torch.randn(R, 3, generator=torch.Generator().manual_seed(8 + i)) / R).to(dev) for i in range(2)]
+    reg_w = (torch.rand(900, 2, generator=torch.Generator().manual_seed(10)) / 900).to(dev)
+
+    def run(defer):
+        L = {k: g[k].to(dev).requires_grad_(True) for k in ("means3D", "scales", "rotations", "opacities", "shs")}
+        v, f = synth.get_disks(L["means3D"].detach(), L["scales"].detach(), L["rotations"].detach())
+        tracer = mod.SurfelTracer()
+        tracer.set_deferred_surfel_gradients(defer)
+        tracer.build_acceleration_structure(v.detach().clone(), f.detach().clone(), rebuild=True)
+        ncalls = 2 if case == "two_calls_share_leaves" else 1
+        loss = 0.0
+        for i in range(ncalls):
+            outs = tracer(rays[i][0], rays[i][1], v, means3D=L["means3D"], grads3D=None, shs=L["shs"], colors_precomp=None, others_precomp=None,
+                          opacities=L["opacities"], scales=L["scales"], rotations=L["rotations"], cov3D_precomp=None,
+                          tracer_settings=_settings(mod, torch.tensor([0.2, 0.3, 0.1]), 3, dev), start_from_first=False)
+            loss = loss + (outs[0] * up[i]).sum()
+        if case == "scale_regulariser":
+            loss = loss + (L["scales"].square() * reg_w).sum()
+        with _CountDeferred() as cd:
+            loss.backward()
+        assert tracing._DEFERRED["pending"] == defer              # (the leaf barriers ordered the stream; the tail is released by a join)
+        tracing.join_deferred_gradients()
+        gr = {k: t.grad.clone() for k, t in L.items()}
+        torch.cuda.synchronize()
+        return gr, cd.n, ncalls
+
+    ref, n0, _ = run(False)
+    got, n1, ncalls = run(True)
+    assert n0 == 0 and n1 == ncalls
+    for k in ref:
+        err = float((ref[k] - got[k]).abs().max())
+        assert float(ref[k].abs().max()) > 0 and err <= 2e-5 * float(ref[k].abs().max()) + 1e-12, (k, err)
 
 
 def test_trace_c_abi_refuses_a_lists_struct_with_a_missing_buffer():
