@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- one JSON line for the EnvGS render-and-trace hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one training iteration's pass of the hot path over one camera view per GPU, exactly as the
@@ -11,13 +11,17 @@ gradient N(0,1)/HW on colour and allmap, `loss.backward()`; with N > 1 the 8-vie
 the flat per-Gaussian gradient buffer is all-reduced once per step over RCCL/xGMI (weak scaling: one view per GPU).
 Inputs are synthetic and resident in HBM before the timed region starts.
 
-Besides the driver's contract fields the line carries
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints the line with the headline figure.  Everything else
+the benchmark measures runs after the timed regions only under --full; a plain line has those fields null.  Besides the driver's contract
+fields a --full line carries
   roofline     : dominant kernel (most time per step): DEDUPLICATED algorithmic HBM bytes (what one launch must move at minimum: every
                  input structure once, every output once) / HIP-event launch time vs the 8 TB/s HBM peak -- every frac <= 1 and the sum over
                  the step stays below the peak; `traffic` = measured HBM bytes (PMC), `issue` = the instruction-issue roofline of the same
                  kernel (VALU / SALU wave-instructions per second against the issue peaks) from the tracked SQ counter summary in profiles/
   cpu_baseline : the CPU oracle (oracle/, OpenMP over the host cores) on the same scene + the PyTorch-eager config-1 figure, rank 0, N=1 only
   kernels      : per-kernel ms/launch and achieved GB/s from HIP events on the launch stream
+  and the reference-caller form of the step, forward-only render Mpix/s, LBVH build / refit times, R7 lane occupancy, trace counters, the step's
+  kernel inventory and, N > 1, both gradient exchange forms timed on their own.
   caller       : --caller fused (default: HIP glue) | twin (torch glue) | reference (the expression forms the unchanged EasyVolcap caller runs)
 """
 import argparse
@@ -229,6 +233,10 @@ def main():
                     "the backward, amplified by Adam), so a difference between builds that only shows after several steps -- Adam moments beyond the "
                     "first update, the environment structure refitted to moved surfels -- does not reach the dump.  The trained parameters and optimizer "
                     "state are put back afterwards, so the passes after it start where the timed steps ended")
+    ap.add_argument("--full", action="store_true", help="after the timed regions (and --dump-outputs), also measure everything beyond the headline figure: "
+                    "per-kernel HIP-event times (a separate pass for the kernels whose scopes were off in the regions) and the roofline, the "
+                    "reference-caller form, forward-only render, LBVH build / refit, R7 lane occupancy, trace counters, the CPU baselines and, "
+                    "N > 1, both exchange forms on their own.  Off: the line carries null there; the timed steps are the same either way")
     ap.add_argument("--no-reference-caller", action="store_true", help="skip the extra few steps that time the unchanged-EasyVolcap-caller form of the step (config.reference_caller_ms_per_step)")
     ap.add_argument("--step-times", type=int, default=0, help="diagnostics: after the timed region, run this many extra steps one by one (synchronised) and print their wall times and the allocator statistics to stderr")
     ap.add_argument("--stage-counts", action="store_true", help="diagnostics: after the timed region, one more step with every traced call's counters (rays, hits found / composited, entries) printed to stderr")
@@ -422,7 +430,8 @@ def main():
     # The library's HIP-event scopes are barrier packets on their streams: with every scope of an EnvGS step on, the step is 0.17 ms (2.3 %) longer than with
     # none (measured, --live-scopes all / none).  The warm-up runs with all of them and says which TWO kernels take most of the step (the collection and
     # the sort / composite pass swap places from run to run); those two stay on inside the timed regions -- the dominant kernel's launch time in
-    # `roofline` is measured there -- and every other kernel is timed in a separate pass of a few steps right after them.
+    # `roofline` is measured there -- and every other kernel is timed in a separate pass of a few steps right after them (--full).  A plain run keeps the
+    # same scopes in its warm-up and timed regions, so that its timed steps are those of a --full run.
     NK = 0
     while lib.envgs_prof_kernel_name(NK): NK += 1
     KNAMES = [lib.envgs_prof_kernel_name(k).decode() for k in range(NK)]
@@ -513,7 +522,7 @@ def main():
         return out, ext
     timed_prof, ext_ms = read_prof(steps_done)
     kernel_pass_steps = 0
-    if live is not None:
+    if args.full and live is not None:
         # the pass for the kernels whose scopes were off: same steps, every scope on, outside the timed regions.  Launch counts are scaled to the timed step
         # count so that the per-step arithmetic below holds for both sources; the two live kernels keep their in-region figures
         kernel_pass_steps = max(4, min(args.steps, 10))
@@ -537,7 +546,7 @@ def main():
     ref_caller_ms = None
     ref_caller_by_blas = None
     ref_ext_ms = None
-    if envgs and args.caller != "reference" and not args.no_reference_caller:
+    if args.full and envgs and args.caller != "reference" and not args.no_reference_caller:
         set_caller("reference")
         ref_ext = []
 
@@ -582,7 +591,7 @@ def main():
     # N > 1: the gradient exchange on its own, both forms, on the step's own flat buffers (after the timed region): the first hardware run with
     # N > 1 ranks decides between the direct reduce-scatter + all-gather and the library's all_reduce from these fields
     exch = None
-    if world > 1 and reducer is not None and reducer.buckets:
+    if args.full and world > 1 and reducer is not None and reducer.buckets:
         exch = {"bytes_per_step": int(sum(B.flat.numel() * 4 for B in reducer.buckets)), "world": world}
         for algo in ("direct", "allreduce"):
             for _ in range(2):
@@ -641,7 +650,7 @@ def main():
     # tile's list it blended; a (wavefront = 8x8 quadrant, splat) pass of composite_bwd runs when any of the quadrant's 64 pixels blended the splat, with
     # exactly those lanes live.  Outside the timed region, rank 0.
     lane_occ = None
-    if rank == 0 and not btrace and H % 16 == 0 and W % 16 == 0:
+    if args.full and rank == 0 and not btrace and H % 16 == 0 and W % 16 == 0:
         try:
             with torch.no_grad():
                 st_ = (pkg.GaussianRasterizationSettings(image_height=H, image_width=W, tanfovx=cams[0].tanfovx, tanfovy=cams[0].tanfovy, bg=(bg if not envgs else torch.zeros(C, device=dev)), scale_modifier=1.0,
@@ -669,13 +678,13 @@ def main():
     N_avg = n_timed["N"] / max(n_timed["steps"], 1)
     traced = envgs or btrace
     P_trace = args.env_gaussians if envgs else P                 # the set the tracer walks
-    tcounts = tracing.last_trace_counts() if traced else None    # (with --trace-depth > 0: the LAST stage's counters)
-    entries = sum(tracing.last_entry_counts()) if traced else 0
+    tcounts = tracing.last_trace_counts() if (args.full and traced) else None    # (with --trace-depth > 0: the LAST stage's counters)
+    entries = sum(tracing.last_entry_counts()) if (args.full and traced) else 0
 
     # acceleration structure on its own (outside the timed region): a full build (Morton keys, sort, hierarchy, fit) against a REFIT of the same
     # topology (envgs_bvh_refit: OptiX's "update", build_acceleration_structure(rebuild=False)) over the step's own environment set
     bvh_times = None
-    if envgs and rank == 0:
+    if args.full and envgs and rank == 0:
         from envgs_amd import fused as _fz
         with torch.no_grad():
             vq, _ = _fz.surfel_quads(env_params["means3D"], env_params["scales"], env_params["rotations"])
@@ -706,7 +715,7 @@ def main():
                 pkg.GaussianRasterizer(raster_settings=settings(cams[vi]))(
                     means3D=params["means3D"], means2D=torch.zeros_like(params["means3D"]), shs=params["shs"], colors_precomp=None,
                     opacities=params["opacities"], scales=params["scales"], rotations=params["rotations"], cov3D_precomp=None)
-    n_render = 0 if args.no_render else max(2, min(args.steps, 10))
+    n_render = 0 if (args.no_render or not args.full) else max(2, min(args.steps, 10))
     render_s = float("nan")
     if n_render:
         render(0); render(1)
@@ -721,7 +730,7 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         render_s = float(tt.item())
     kernels = {}
-    for name, (ms, launches, _tot) in timed_prof.items():      # (the timers of the timed regions were drained right after them: timed_prof)
+    for name, (ms, launches, _tot) in (timed_prof.items() if args.full else ()):      # (the timers of the timed regions were drained right after them: timed_prof)
         if launches > 0:
             ab = algorithmic_bytes(name, P, N_avg, HW, C, not envgs) if not btrace else 0
             pr = 0
@@ -749,7 +758,7 @@ def main():
         dom = max(leaf, key=lambda k: leaf[k]["ms"] * leaf[k]["launches"]) if leaf else None      # most time per step (launches included)
         roof = None
         pm = {}
-        wkey = workload_key(args, H, W)
+        wkey = workload_key(args, H, W) if args.full else None
         PMC_SUMMARY = os.path.join("profiles", "%s_pmc_%s.json" % (PMC_TAG, wkey)) if wkey else None
         try:                                   # tracked PMC summary of the SAME workload (profiles/collect_profiles.sh <key> -> profiles/summarize.py; separate --pmc passes)
             pm = json.load(open(os.path.join(ROOT, PMC_SUMMARY)))["kernels"] if PMC_SUMMARY else {}
@@ -819,7 +828,7 @@ def main():
                     roof["raster_composite_bwd"]["shares_the_chip"] = ("with the tracer backward's deferred record sums (reduce_surfel_records on the library's stream, 512 workgroups): "
                                                                        "its launch time here includes that; alone (--no-deferred-surfel-grads) it takes ~0.06 ms less")
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if not btrace:
                 cpu = cpu_baseline(g, cams[0], bg, dcol, dall, H, W, args.cpu_reps, C,
                                    (ge, last_rays, args.cpu_rays) if envgs else None)
@@ -842,7 +851,7 @@ def main():
                                        "reference": "the unchanged EasyVolcap caller's expression forms (batched-matmul get_disks, render()'s regulariser maps + normal term)"}[args.caller]),
                        "reference_caller_ms_per_step": (None if ref_caller_ms is None else round(ref_caller_ms, 3)),
                        "reference_caller_ms_by_torch_blas": ref_caller_by_blas,
-                       "extension_ms_per_step": round(ext_ms, 3),
+                       "extension_ms_per_step": (round(ext_ms, 3) if args.full else None),
                        "reference_caller_extension_ms_per_step": (None if ref_ext_ms is None else round(ref_ext_ms, 3)),
                        "extension_note": "HIP-event time of the two extensions' own launches per step (raster stages, structure build / refit, tracer forward and backward) under the measured caller and under the reference-caller form: what is left of reference_caller_ms_per_step beyond it is torch glue of the caller (get_disks' batched matmuls, SH colours, reflection, regulariser maps, torch.optim-free here), not extension time",
                        "reference_caller_note": "the same step with the UNCHANGED EasyVolcap caller's expression forms around the same extensions (--caller reference), a few steps outside the timed region; reference_caller_ms_per_step is under torch's OWN BLAS choice (importing the packages changes nothing process-wide), reference_caller_ms_by_torch_blas has it under both (cublas = rocBLAS, cublaslt = hipBLASLt; the one-line pin of INTEGRATION.md section 5)",
@@ -860,8 +869,8 @@ def main():
             "render_mpix_per_s": (round(world * HW / render_s / 1e6, 2) if n_render else None),
             "render_ms_per_view": (round(render_s * 1e3, 4) if n_render else None),
             "exchange": exch,
-            "launches": (step_inventory() if (envgs and args.caller == "fused" and H == 800 and W == 800 and not args.trace_depth and P == 300000 and args.env_gaussians == 163840 and args.bvh_rebuild_every == 16) else None),
-            "roofline": roof, "cpu_baseline": cpu, "kernels": kernels, "bvh": bvh_times, "trace_counts": (dict(tcounts, entries=entries) if tcounts else None),
+            "launches": (step_inventory() if (args.full and envgs and args.caller == "fused" and H == 800 and W == 800 and not args.trace_depth and P == 300000 and args.env_gaussians == 163840 and args.bvh_rebuild_every == 16) else None),
+            "roofline": roof, "cpu_baseline": cpu, "kernels": (kernels if args.full else None), "bvh": bvh_times, "trace_counts": (dict(tcounts, entries=entries) if tcounts else None),
         }
         print(json.dumps(line))
     if world > 1:

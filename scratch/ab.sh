@@ -7,7 +7,7 @@ cp envgs_amd/libenvgs_hip.so /tmp/_orig.so
 for v in $VARS; do
   cp scratch/variants/$v.so envgs_amd/libenvgs_hip.so
   for rep in 1 2; do
-    python bench.py --no-cpu-baseline --no-render --no-reference-caller --steps 20 --warmup 5 "$@" 2>/dev/null | python scratch/ab_show.py "$v.$rep"
+    python bench.py --full --no-cpu-baseline --no-render --no-reference-caller --steps 20 --warmup 5 "$@" 2>/dev/null | python scratch/ab_show.py "$v.$rep"
   done
 done
 cp /tmp/_orig.so envgs_amd/libenvgs_hip.so

@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
 cp envgs_amd/libenvgs_hip.so /tmp/_orig.so
 for v in $1; do
   cp scratch/variants/$v.so envgs_amd/libenvgs_hip.so
-  timeout 250 python bench.py --height 1200 --width 1600 --trace-depth 2 --channels 7 --feature-dtype f16 --no-cpu-baseline --no-reference-caller --no-render --steps 8 --warmup 3 --repeats 3 2>/dev/null > /tmp/c5_$v.json
+  timeout 250 python bench.py --full --height 1200 --width 1600 --trace-depth 2 --channels 7 --feature-dtype f16 --no-cpu-baseline --no-reference-caller --no-render --steps 8 --warmup 3 --repeats 3 2>/dev/null > /tmp/c5_$v.json
   python - <<PY
 import json
 d = json.load(open("/tmp/c5_$v.json"))

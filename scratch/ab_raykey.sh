@@ -3,5 +3,5 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
 VALS="$1"; shift
 for v in $VALS; do
-  python bench.py --no-cpu-baseline --no-render --no-reference-caller --steps 20 --warmup 5 --debug-raykey $v "$@" 2>/dev/null | python scratch/ab_show.py "raykey=$v"
+  python bench.py --full --no-cpu-baseline --no-render --no-reference-caller --steps 20 --warmup 5 --debug-raykey $v "$@" 2>/dev/null | python scratch/ab_show.py "raykey=$v"
 done

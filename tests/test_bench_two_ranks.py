@@ -24,7 +24,7 @@ def test_bench_two_ranks_gloo_on_one_gpu(exchange):
     env = dict(os.environ, ENVGS_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--gaussians", "20000", "--env-gaussians", "8192", "--res", "128",
-           "--no-cpu-baseline", "--no-render", "--exchange", exchange]
+           "--full", "--no-cpu-baseline", "--no-render", "--exchange", exchange]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT, timeout=540)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -86,7 +86,7 @@ def test_dp_training_keeps_ranks_identical_nccl(exchange):
 @pytest.mark.skipif(not TWO_GPUS, reason="needs >= 2 GPUs (RCCL over xGMI)")
 def test_bench_two_gpus_nccl():
     d = _launch([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--gaussians", "20000", "--env-gaussians", "8192",
-                 "--res", "128", "--no-cpu-baseline", "--no-render"], "nccl")
+                 "--res", "128", "--full", "--no-cpu-baseline", "--no-render"], "nccl")
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["value"] > 0
     assert "nccl" in str(d["config"].get("dist_backend", "nccl"))
     ex = d["exchange"]
