@@ -58,6 +58,16 @@ class TraceCfg(ctypes.Structure):
                 ("scale_modifier", ctypes.c_float), ("specular_threshold", ctypes.c_float), ("feature_f16", ctypes.c_int32)]
 
 
+class SupervisorArgs(ctypes.Structure):
+    """struct envgs_supervisor_args (include/envgs_supervisor.h)."""
+    _fields_ = ([("N", ctypes.c_int64), ("P", ctypes.c_int64), ("flags", ctypes.c_uint32), ("reserved0", ctypes.c_uint32),
+                 ("weight", ctypes.c_float * 5), ("reserved1", ctypes.c_float)]
+                + [(n, ctypes.c_void_p) for n in ("norm_map", "surf_norm_map", "acc_map", "dpt_map", "dist_map", "env_opacity", "prior", "msk", "R", "near_far")]
+                + [(n, ctypes.c_int64) for n in ("norm_map_row", "norm_map_ch", "surf_norm_map_row", "surf_norm_map_ch", "acc_map_row", "dpt_map_row",
+                                                 "dist_map_row", "env_opacity_row", "prior_row", "prior_ch", "msk_row")]
+                + [(n, ctypes.c_void_p) for n in ("g_norm_map", "g_surf_norm_map", "g_acc_map", "g_dist_map", "g_env_opacity", "partial")])
+
+
 # every symbol include/*.h declares: name -> (restype, argtypes)
 _P = c_void_p
 SYMBOLS = {
@@ -100,6 +110,12 @@ SYMBOLS = {
     "envgs_l1_ssim_partial_count": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "envgs_l1_ssim_forward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P]),
     "envgs_l1_ssim_backward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, ctypes.c_float, ctypes.c_float, _P, _P]),
+    "envgs_depth_percentiles_temp_bytes": (c_size_t, []),
+    "envgs_depth_percentiles": (c_int, [ctypes.c_int64, _P, ctypes.c_int64, _P, _P, c_size_t, _P]),
+    "envgs_supervisor_partial_count": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64]),
+    "envgs_supervisor_forward": (c_int, [ctypes.POINTER(SupervisorArgs), _P]),
+    "envgs_supervisor_finish": (c_int, [ctypes.POINTER(SupervisorArgs), _P, _P]),
+    "envgs_supervisor_backward": (c_int, [ctypes.c_int64, _P, _P, _P, _P]),
     "envgs_debug_set": (None, [ctypes.c_int32, ctypes.c_int32]),
     "envgs_debug_get": (ctypes.c_int32, [ctypes.c_int32]),
     "envgs_prof_enable": (None, [c_int]),

@@ -1,0 +1,132 @@
+"""A float64 numpy statement of the geometry regularisers EnvGS trains with, and of their gradients -- written out by hand, in this project's
+own words, as the checker of envgs_amd.loss.EnvGSGeometryLoss (tests/test_supervisor_loss.py).  It is itself pinned against the reference's
+outputs (tests/golden/supervisor_golden.npz, produced by tests/golden/make_supervisor_golden.py).
+
+One view.  Inputs (numpy, any float dtype; pixels are rows):
+  norm_map (N,3), surf_norm_map (N,3), acc_map (N,), dpt_map (N,), dist_map (N,), env_opacity (P,), norm (N,3; stored as n/2 + 1/2), msk (N,), R (3,3)
+Options: a dict with the reference's keyword names (see DEFAULTS).  Terms, each active when its weight is positive, its inputs are present and
+`it` lies in [start_iter, until_iter):
+  env_opacity_loss  'sparse': mean(log v + log(1 - v)), v = clamp(o, 1e-3, 1 - 1e-3);   'l1': mean |1 - o|
+  norm_loss         a = unit(R unit(norm_map)), g = unit(2 norm - 1), unit(x) = x / (|x| + 1e-8);  mean over pixels of  s * (sum|a - g| + 1 - cos(a, g))
+  gs_norm_loss      mean of  s * (1 - <norm_map, surf_norm_map>)
+  msk_loss          mean (acc - m)^2,  m = [msk > 0.5 and |norm| > 0.25]
+  gs_dist_loss      mean dist_map
+with s = (acc if use_acc_scale_*) * (depth scale if use_dpt_scale_*), both constants for the gradient, and
+  depth scale = clip(1 - (d - near) / (far - near), 0, 1),  near / far = the n-th smallest / largest depth, n = int(0.01 N).
+cos(a, g) = <a / max(|a|, 1e-8), g / max(|g|, 1e-8)> where the clamp is a constant for the gradient.  |x| has gradient 0 at x = 0."""
+import numpy as np
+
+EPS = 1e-8
+DEFAULTS = dict(
+    norm_loss_weight=0.0, norm_loss_start_iter=7000, norm_loss_until_iter=None, use_acc_scale_norm_loss=False, use_dpt_scale_norm_loss=False,
+    gs_norm_loss_weight=0.0, gs_norm_loss_start_iter=7000, gs_norm_loss_until_iter=None, use_acc_scale_gs_norm_loss=False,
+    use_dpt_scale_gs_norm_loss=False, gs_dist_loss_weight=0.0, gs_dist_loss_start_iter=3000, gs_dist_loss_until_iter=None,
+    env_opacity_loss_weight=0.0, env_opacity_loss_type="sparse", env_opacity_loss_start_iter=0,
+    msk_loss_weight=0.0, msk_loss_start_iter=7000, msk_loss_until_iter=None)
+
+
+def percentiles(d, p=0.01):
+    """(near, far): the n-th smallest and the n-th largest element of d, n = int(d.size * p) >= 1, as elements of d (no interpolation)."""
+    d = np.asarray(d).ravel()
+    n = int(d.size * p)
+    if n < 1:
+        raise ValueError("percentiles need at least %d values" % int(np.ceil(1 / p)))
+    s = np.sort(d, kind="stable")
+    return s[n - 1], s[d.size - n]
+
+
+def depth_scale(d, near=None, far=None):
+    if near is None:
+        near, far = percentiles(d)
+    d = np.asarray(d, np.float64)
+    return np.clip(1.0 - (d - float(near)) / (float(far) - float(near)), 0.0, 1.0)
+
+
+def _unit(x):
+    """x / (|x| + eps) and the pieces its adjoint needs."""
+    r = np.sqrt((x * x).sum(-1, keepdims=True))
+    return x / (r + EPS), r
+
+
+def _unit_adjoint(x, r, gy):
+    """Adjoint of y = x / (|x| + eps):  gy / (r + eps) - x/|x| * <gy, x> / (r + eps)^2, the second part absent where |x| = 0."""
+    safe = np.where(r > 0, r, 1.0)
+    return gy / (r + EPS) - np.where(r > 0, x / safe, 0.0) * (gy * x).sum(-1, keepdims=True) / (r + EPS) ** 2
+
+
+def _window(it, start, until):
+    return it >= start and (until is None or it < until)
+
+
+def geometry_loss(inp, opts, it):
+    """-> (loss, stats: dict name -> float, grads: dict input name -> array), everything float64."""
+    o = dict(DEFAULTS, **opts)
+    f = lambda k: None if inp.get(k) is None else np.asarray(inp[k], np.float64)
+    nm, sn, acc, dpt, dist, env, prior, msk, R = (f(k) for k in ("norm_map", "surf_norm_map", "acc_map", "dpt_map", "dist_map", "env_opacity", "norm", "msk", "R"))
+    loss, stats, grads = 0.0, {}, {}
+
+    def add(name, g):
+        grads[name] = grads.get(name, 0.0) + g
+
+    def scale(use_acc, use_dpt):
+        s = np.ones(nm.shape[0])
+        if use_acc:
+            s = s * acc
+        if use_dpt:
+            s = s * depth_scale(dpt, *percentiles(inp["dpt_map"]))            # order statistics of the values as given (their own dtype)
+        return s
+
+    if env is not None and o["env_opacity_loss_weight"] > 0 and it >= o["env_opacity_loss_start_iter"]:
+        w = o["env_opacity_loss_weight"] / env.size
+        if o["env_opacity_loss_type"] == "sparse":
+            lo, hi = 1e-3, 1 - 1e-3
+            v = np.clip(env, lo, hi)
+            stats["env_opacity_loss"] = (np.log(v) + np.log(1 - v)).mean()
+            add("env_opacity", w * np.where((env >= lo) & (env <= hi), 1 / v - 1 / (1 - v), 0.0))
+        elif o["env_opacity_loss_type"] == "l1":
+            stats["env_opacity_loss"] = np.abs(1 - env).mean()
+            add("env_opacity", -w * np.sign(1 - env))
+        else:
+            raise ValueError(o["env_opacity_loss_type"])
+        loss += o["env_opacity_loss_weight"] * stats["env_opacity_loss"]
+
+    if nm is not None and prior is not None and o["norm_loss_weight"] > 0 and _window(it, o["norm_loss_start_iter"], o["norm_loss_until_iter"]):
+        a0, r0 = _unit(nm)
+        b = a0 @ R.T
+        a, r1 = _unit(b)
+        t = 2.0 * prior - 1.0
+        g, _ = _unit(t)
+        na = np.maximum(np.sqrt((a * a).sum(-1, keepdims=True)), EPS)
+        ng = np.maximum(np.sqrt((g * g).sum(-1, keepdims=True)), EPS)
+        gn = g / ng
+        c = (a / na * gn).sum(-1)
+        s = scale(o["use_acc_scale_norm_loss"], o["use_dpt_scale_norm_loss"])
+        stats["norm_loss"] = (s * (np.abs(a - g).sum(-1) + 1 - c)).mean()
+        loss += o["norm_loss_weight"] * stats["norm_loss"]
+        ra = np.sqrt((a * a).sum(-1, keepdims=True))
+        # d cos / d a = gn / na - a/|a| * <a, gn> / na^2  (the clamp inside na is a constant; |a| has gradient 0 at 0)
+        dc = gn / na - np.where(ra > 0, a / np.where(ra > 0, ra, 1.0), 0.0) * (a * gn).sum(-1, keepdims=True) / na ** 2
+        ga = (np.sign(a - g) - dc) * (s * o["norm_loss_weight"] / nm.shape[0])[:, None]
+        gb = _unit_adjoint(b, r1, ga)
+        add("norm_map", _unit_adjoint(nm, r0, gb @ R))
+
+    if nm is not None and sn is not None and o["gs_norm_loss_weight"] > 0 and _window(it, o["gs_norm_loss_start_iter"], o["gs_norm_loss_until_iter"]):
+        s = scale(o["use_acc_scale_gs_norm_loss"], o["use_dpt_scale_gs_norm_loss"])
+        stats["gs_norm_loss"] = (s * (1 - (nm * sn).sum(-1))).mean()
+        loss += o["gs_norm_loss_weight"] * stats["gs_norm_loss"]
+        w = (s * o["gs_norm_loss_weight"] / nm.shape[0])[:, None]
+        add("norm_map", -w * sn)
+        add("surf_norm_map", -w * nm)
+
+    if acc is not None and o["msk_loss_weight"] > 0 and _window(it, o["msk_loss_start_iter"], o["msk_loss_until_iter"]):
+        m = ((msk > 0.5) & (np.sqrt((prior * prior).sum(-1)) > 0.25)).astype(np.float64)
+        stats["msk_loss"] = ((acc - m) ** 2).mean()
+        loss += o["msk_loss_weight"] * stats["msk_loss"]
+        add("acc_map", 2 * (acc - m) * o["msk_loss_weight"] / acc.size)
+
+    if dist is not None and o["gs_dist_loss_weight"] > 0 and _window(it, o["gs_dist_loss_start_iter"], o["gs_dist_loss_until_iter"]):
+        stats["gs_dist_loss"] = dist.mean()
+        loss += o["gs_dist_loss_weight"] * stats["gs_dist_loss"]
+        add("dist_map", np.full(dist.shape, o["gs_dist_loss_weight"] / dist.size))
+
+    return loss, stats, grads
