@@ -100,6 +100,23 @@ static int join_deferred(hipStream_t stream)
     return hipStreamWaitEvent(stream, s_def_done[dev], 0) == hipSuccess ? 0 : ENVGS_ERR_BAD_ARG;
 }
 
+static TraceArgs base_args(const envgs_trace_cfg *cfg, const float *nodes, const float *srec, const float *shs, const float *colors_precomp,
+                           const float *others_precomp, const float *bg, const float *ray_o, const float *ray_d, uint32_t *counters)
+{
+    TraceArgs A = TraceArgs{};
+    A.P = cfg->P; A.R = cfg->num_rays; A.D = cfg->sh_degree; A.M = cfg->sh_coeffs; A.ND = 1;
+    A.start_from_first = cfg->start_from_first; A.has_others = cfg->has_others; A.bg_len = cfg->bg_len; A.spec_thr = cfg->specular_threshold;
+    A.nodes = (const float4 *)nodes; A.srec = (const float4 *)srec; A.shs = shs; A.colors = colors_precomp; A.others = others_precomp;
+    A.bg = bg; A.ray_o = ray_o; A.ray_d = ray_d; A.counter = counters;
+    A.mod = cfg->scale_modifier; A.f16 = cfg->feature_f16; A.exp = debug_switch(ENVGS_DBG_TRACE);
+    return A;
+}
+
+static unsigned sparse_capacity(const envgs_trace_lists *L)       // (the kernels count the filed hits in a 32-bit word)
+{
+    return (unsigned)(L->sparse_cap > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : L->sparse_cap);
+}
+
 extern "C" {
 
 size_t envgs_trace_ray_sort_temp_bytes(int32_t num_rays) { return ray_sort_temp_bytes(num_rays); }
@@ -152,16 +169,9 @@ int envgs_trace_forward(const envgs_trace_cfg *cfg, const float *nodes, const fl
         hipLaunchKernelGGL(forward_prepare, dim3((unsigned)(FP.zero_blocks + FP.rec_blocks + FP.perm_blocks)), dim3(256), 0, st, FP);
         return (int)hipGetLastError();
     };
-    TraceArgs A;
-    A = TraceArgs{};
-    A.P = cfg->P; A.R = cfg->num_rays; A.D = cfg->sh_degree; A.M = cfg->sh_coeffs; A.ND = cfg->max_trace_depth + 1;
-    A.start_from_first = cfg->start_from_first; A.has_others = cfg->has_others; A.bg_len = cfg->bg_len; A.spec_thr = cfg->specular_threshold;
-    A.nodes = (const float4 *)nodes; A.srec = (const float4 *)srec; A.shs = shs; A.colors = colors_precomp; A.others = others_precomp;
-    A.bg = bg; A.ray_o = ray_o; A.ray_d = ray_d; A.counter = counters; A.stats = (unsigned long long *)(counters + 2);
+    TraceArgs A = base_args(cfg, nodes, srec, shs, colors_precomp, others_precomp, bg, ray_o, ray_d, counters);
+    A.ND = cfg->max_trace_depth + 1; A.stats = (unsigned long long *)(counters + 2);
     A.rgb = rgb; A.dpt = dpt; A.acc = acc; A.norm = norm; A.dist = dist; A.aux = aux; A.mid = mid; A.wet = wet; A.final_T = final_T;
-    A.mod = cfg->scale_modifier;
-    A.f16 = cfg->feature_f16;
-    A.exp = debug_switch(ENVGS_DBG_TRACE);
 #ifndef ENVGS_DIAG
     if (A.exp & (8 | 16 | 512 | 2048 | 4096 | 8192)) return ENVGS_ERR_BAD_ARG;      // A/B kernels of the diagnostic build (libenvgs_hip_diag.so) were requested
 #endif
@@ -190,7 +200,7 @@ int envgs_trace_forward(const envgs_trace_cfg *cfg, const float *nodes, const fl
             // sparse entries (envgs_trace.h: sparse_hits): entries of at most 4 hits are filed per hit (ENVGS_DBG_SPARSE: value - 1 overrides, 1 = off)
             const int sw = debug_switch(ENVGS_DBG_SPARSE);
             A.sparse = (uint4 *)L->sparse_hits;
-            A.sparse_cap = (unsigned)(L->sparse_cap > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : L->sparse_cap);
+            A.sparse_cap = sparse_capacity(L);
             A.sparse_max = sw > 0 ? (sw - 1 > 64 ? 64 : sw - 1) : 4;
         }
         if (L->sh_perm && shs && cfg->sh_coeffs == 16) {
@@ -385,21 +395,13 @@ int envgs_trace_backward(const envgs_trace_cfg *cfg, const float *nodes, const f
         return ENVGS_ERR_BAD_ARG;
     if (!no_finish && (!dmeans3D || !dscales || !drots || !dopacities)) return ENVGS_ERR_BAD_ARG;
     if (cfg->sh_coeffs > 0 ? (!shs || !dshs) : (!colors_precomp || !dcolors)) return ENVGS_ERR_BAD_ARG;
-    TraceArgs A;
-    A = TraceArgs{};
-    A.P = cfg->P; A.R = cfg->num_rays; A.D = cfg->sh_degree; A.M = cfg->sh_coeffs; A.ND = 1;
-    A.start_from_first = cfg->start_from_first; A.has_others = cfg->has_others; A.bg_len = cfg->bg_len; A.spec_thr = cfg->specular_threshold;
-    A.nodes = (const float4 *)nodes; A.srec = (const float4 *)srec; A.shs = shs; A.colors = colors_precomp; A.others = others_precomp;
-    A.bg = bg; A.ray_o = ray_o; A.ray_d = ray_d; A.counter = counters;
+    TraceArgs A = base_args(cfg, nodes, srec, shs, colors_precomp, others_precomp, bg, ray_o, ray_d, counters);
     A.f_rgb = rgb; A.f_dpt = dpt; A.f_acc = acc; A.f_norm = norm; A.f_aux = aux; A.f_T = final_T;
     A.g_rgb = dL_drgb; A.g_dpt = dL_ddpt; A.g_acc = dL_dacc; A.g_norm = dL_dnorm; A.g_aux = dL_daux;
-    A.geo_rec = geo_rec; A.dshs = dshs; A.dcolors = dcolors;
-    A.exp = debug_switch(ENVGS_DBG_TRACE);
+    A.geo_rec = geo_rec; A.dshs = dshs; A.dcolors = dcolors; A.dothers = dothers; A.dray_o = dray_o; A.dray_d = dray_d;
 #ifndef ENVGS_DIAG
     if (A.exp & (8 | 16 | 512 | 2048 | 4096 | 8192)) return ENVGS_ERR_BAD_ARG;
 #endif
-    A.f16 = cfg->feature_f16;
-    A.dothers = dothers; A.dray_o = dray_o; A.dray_d = dray_d; A.mod = cfg->scale_modifier;
     int rh, rw; ray_layout(cfg, &rh, &rw);
     bool deferred = false, have_records = false;
     int def_dev = 0;
@@ -429,7 +431,7 @@ int envgs_trace_backward(const envgs_trace_cfg *cfg, const float *nodes, const f
                     else hipLaunchKernelGGL((batch_surfel_bwd<false, false>), g, dim3(64), 0, stream, A);
                     if (L->sparse_hits && L->sparse_cap > 0) {      // the hits of sparse entries, one lane each (adds to the ray gradients stored above)
                         A.sparse = (uint4 *)L->sparse_hits;
-                        A.sparse_cap = (unsigned)(L->sparse_cap > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : L->sparse_cap);
+                        A.sparse_cap = sparse_capacity(L);
                         hipLaunchKernelGGL(sparse_hits_bwd, dim3(2048), dim3(256), 0, stream, A, rgb_only ? 1 : 0);
                     }
                 }

@@ -320,20 +320,26 @@ __device__ __forceinline__ void load_sh(const TraceArgs &A, const int sid, const
     }
 }
 
+// SH colour of one hit: sum_k basis_k sh_k + 0.5 clamped at 0, cl[] = the clamped channels.  nb: active coefficients (16 if the rest are zeros)
+__device__ __forceinline__ void sh_colour_clamped(const float *basis, const float *shv, const int nb, float *col, bool *cl)
+{
+    float r0 = 0.f, r1 = 0.f, r2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < 16; k++)
+        if (k < nb) { const float b = basis[k]; r0 += b * shv[k * 3]; r1 += b * shv[k * 3 + 1]; r2 += b * shv[k * 3 + 2]; }
+    r0 += 0.5f; r1 += 0.5f; r2 += 0.5f;
+    cl[0] = r0 < 0.f; cl[1] = r1 < 0.f; cl[2] = r2 < 0.f;
+    col[0] = cl[0] ? 0.f : r0; col[1] = cl[1] ? 0.f : r1; col[2] = cl[2] ? 0.f : r2;
+}
+
 __device__ __forceinline__ void surfel_color(const TraceArgs &A, int sid, const float *basis, float *col, bool *cl)
 {
     if (A.M > 0) {
         const int nb = (A.D + 1) * (A.D + 1);
-        float r0 = 0.f, r1 = 0.f, r2 = 0.f;
         // the usual layout (16 coefficients x RGB, 16 B aligned): 12 x 16 B loads (6 with fp16 storage) instead of 48 x 4 B gathers
         float v[48];
         load_sh(A, sid, nb, v);
-#pragma unroll
-        for (int k = 0; k < 16; k++)
-            if (k < nb) { const float b = basis[k]; r0 += b * v[k * 3]; r1 += b * v[k * 3 + 1]; r2 += b * v[k * 3 + 2]; }
-        r0 += 0.5f; r1 += 0.5f; r2 += 0.5f;
-        cl[0] = r0 < 0.f; cl[1] = r1 < 0.f; cl[2] = r2 < 0.f;
-        col[0] = cl[0] ? 0.f : r0; col[1] = cl[1] ? 0.f : r1; col[2] = cl[2] ? 0.f : r2;
+        sh_colour_clamped(basis, v, nb, col, cl);
     } else {
         const Feat c = Feat{A.colors, A.f16 != 0}.at((size_t)sid * 3);
         col[0] = c[0]; col[1] = c[1]; col[2] = c[2];
@@ -423,7 +429,67 @@ __device__ __forceinline__ void bwd_init_acc(BwdAcc &a)
     for (int k = 0; k < 16; k++) a.Sk[k] = 0.f;
 }
 
-// Gradient of one composited hit.  Returns false when the ray terminates at this hit (it is then NOT blended).
+// ---- the per-hit gradient shared by bwd_hit (K-buffer, per-ray lists), batch_surfel_bwd (records) and sparse_hits_bwd: plain values in and out ----
+// F = sum_j g_j final_j + T_final (bg . g_rgb): the suffix terms of dL/dalpha only ever appear as  sum_j g_j (final_j - prefix_j)  (+ the
+// background term), so the twelve final sums fold into this ONE scalar per ray
+__device__ __forceinline__ float bwd_final_dot(const BwdRay &B)
+{
+    return B.gR0 * B.fr0 + B.gR1 * B.fr1 + B.gR2 * B.fr2 + B.gD * B.fD + B.gA * B.fA + B.gN0 * B.fN0 + B.gN1 * B.fN1 + B.gN2 * B.fN2 +
+           B.gX0 * B.fX0 + B.gX1 * B.fX1 + B.fT * B.bgdot;
+}
+
+// dL/dalpha of a hit from the state the forward stored for it (TraceArgs::state): st0 = plane 0, st1 / sx0 / sx1 = plane 1's depth + normal and aux
+// sums; Fsum = bwd_final_dot of its ray.  colour_only: only the colour has an upstream gradient, the other outputs' terms and plane 1 drop out.
+__device__ __forceinline__ float alpha_grad_from_state(const bool colour_only, const float gR0, const float gR1, const float gR2, const float gD, const float gA,
+                                                       const float gN0, const float gN1, const float gN2, const float gX0, const float gX1, const float Fsum,
+                                                       const float *col, const float t, const float nf0, const float nf1, const float nf2, const float x0, const float x1,
+                                                       const float alpha, const float inv1m, const float4 st0, const float4 st1, const float sx0, const float sx1)
+{
+    const float Tb = st0.x;
+    float gv_ = gR0 * col[0] + gR1 * col[1] + gR2 * col[2], gS = gR0 * st0.y + gR1 * st0.z + gR2 * st0.w;
+    if (!colour_only) {
+        gv_ += gD * t + gA + gN0 * nf0 + gN1 * nf1 + gN2 * nf2 + gX0 * x0 + gX1 * x1;
+        gS += gD * st1.x + gA * (1.0f - Tb * (1.0f - alpha)) + gN0 * st1.y + gN1 * st1.z + gN2 * st1.w + gX0 * sx0 + gX1 * sx1;
+    }
+    return Tb * gv_ - (Fsum - gS) * inv1m;
+}
+
+// From dL/dalpha and the blend weight w of one hit to the 15 geometry-record words gw[0..14] (finish_surfel_grads) and the ray-origin term e
+// (dL/do = e, dL/dd = t e).  isu, isv, iden = 1 / s_u, 1 / s_v, 1 / denom as the caller rounds them: v_rcp_f32 or IEEE.
+__device__ __forceinline__ void hit_geometry_grad(const float4 s0, const float4 s1, const float4 s2, const float4 s3, const SurfHit &h, const float ox, const float oy,
+                                                  const float oz, const float dx, const float dy, const float dz, const float w, const float sgn, const float dLa,
+                                                  const float gD, const float gN0, const float gN1, const float gN2, const float mod, const float isu, const float isv,
+                                                  const float iden, float *gw, float &e0, float &e1, float &e2)
+{
+    const float dLG = s0.w * dLa;
+    const float dLu = dLG * (-h.G * h.u), dLv = dLG * (-h.G * h.v);
+    const float qx = ox + h.t * dx - s0.x, qy = oy + h.t * dy - s0.y, qz = oz + h.t * dz - s0.z;
+    // u = (a/su).q : dL/dq = dLu*(a/su) + dLv*(b/sv) ; dL/da = (dLu/su) q ; dL/dsu = -dLu*u/su
+    const float dq0 = dLu * s1.x + dLv * s2.x, dq1 = dLu * s1.y + dLv * s2.y, dq2 = dLu * s1.z + dLv * s2.z;
+    const float cu = dLu * isu, cv = dLv * isv;
+    const float dLt_tot = w * gD + dq0 * dx + dq1 * dy + dq2 * dz;
+    const float kt = dLt_tot * iden;
+    e0 = dq0 - kt * s3.x; e1 = dq1 - kt * s3.y; e2 = dq2 - kt * s3.z;
+    gw[0] = -e0; gw[1] = -e1; gw[2] = -e2;
+    gw[3] = cu * qx; gw[4] = cu * qy; gw[5] = cu * qz;
+    gw[6] = cv * qx; gw[7] = cv * qy; gw[8] = cv * qz;
+    const float ws = w * sgn;
+    gw[9] = ws * gN0 - kt * qx; gw[10] = ws * gN1 - kt * qy; gw[11] = ws * gN2 - kt * qz;
+    gw[12] = -cu * h.u * mod;
+    gw[13] = -cv * h.v * mod;
+    gw[14] = h.G * dLa;
+}
+
+// dd (dL/d unit direction) -> dL/d ray_d:  (|d|^2 I - d d^T) / |d|^3 . dd
+__device__ __forceinline__ void ray_dir_grad(const BwdRay &B, const float dd0, const float dd1, const float dd2, float *out)
+{
+    const float inv3 = B.il * B.il * B.il;
+    out[0] = ((B.dl2 - B.dx * B.dx) * dd0 - B.dy * B.dx * dd1 - B.dz * B.dx * dd2) * inv3;
+    out[1] = (-B.dx * B.dy * dd0 + (B.dl2 - B.dy * B.dy) * dd1 - B.dz * B.dy * dd2) * inv3;
+    out[2] = (-B.dx * B.dz * dd0 - B.dy * B.dz * dd1 + (B.dl2 - B.dz * B.dz) * dd2) * inv3;
+}
+
+// Gradient of one composited hit, dL/dalpha from the running sums.  Returns false when the ray terminates at this hit (it is then NOT blended).
 // Out: dc[3] (dL/dcolour of the surfel from this hit) and gv[15] (the geometry-record words).
 __device__ __forceinline__ bool bwd_hit(const TraceArgs &A, const BwdRay &B, BwdAcc &a, const float *basis, const int nb,
                                         const int sid, float &dc0, float &dc1, float &dc2, float *gv)
@@ -440,13 +506,7 @@ __device__ __forceinline__ bool bwd_hit(const TraceArgs &A, const BwdRay &B, Bwd
     float shv[48];
     if (A.M > 0) {
         load_sh(A, sid, nb, shv);
-        float r0 = 0.f, r1 = 0.f, r2 = 0.f;
-#pragma unroll
-        for (int k = 0; k < 16; k++)
-            if (k < nb) { const float b = basis[k]; r0 += b * shv[k * 3]; r1 += b * shv[k * 3 + 1]; r2 += b * shv[k * 3 + 2]; }
-        r0 += 0.5f; r1 += 0.5f; r2 += 0.5f;
-        cl[0] = r0 < 0.f; cl[1] = r1 < 0.f; cl[2] = r2 < 0.f;
-        col[0] = cl[0] ? 0.f : r0; col[1] = cl[1] ? 0.f : r1; col[2] = cl[2] ? 0.f : r2;
+        sh_colour_clamped(basis, shv, nb, col, cl);
     } else surfel_color(A, sid, basis, col, cl);
     const float sgn = h.denom < 0.0f ? 1.0f : -1.0f;
     const float nf0 = sgn * s3.x, nf1 = sgn * s3.y, nf2 = sgn * s3.z;
@@ -470,23 +530,11 @@ __device__ __forceinline__ bool bwd_hit(const TraceArgs &A, const BwdRay &B, Bwd
             if (k < nb) a.Sk[k] += shv[k * 3] * dc0 + shv[k * 3 + 1] * dc1 + shv[k * 3 + 2] * dc2;
     }
     if (A.has_others && A.dothers) { atomic_add_f32(A.dothers + 2 * sid, w * B.gX0); atomic_add_f32(A.dothers + 2 * sid + 1, w * B.gX1); }
-    const float dLG = s0.w * dLa;
-    const float dLu = dLG * (-h.G * h.u), dLv = dLG * (-h.G * h.v);
-    const float su = s1.w, sv = s2.w;
-    const float qx = B.ox + h.t * B.dx - s0.x, qy = B.oy + h.t * B.dy - s0.y, qz = B.oz + h.t * B.dz - s0.z;
-    // u = (a/su).q : dL/dq = dLu*(a/su) + dLv*(b/sv) ; dL/da = (dLu/su) q ; dL/dsu = -dLu*u/su
-    const float dq0 = dLu * s1.x + dLv * s2.x, dq1 = dLu * s1.y + dLv * s2.y, dq2 = dLu * s1.z + dLv * s2.z;
-    const float cu = dLu / su, cv = dLv / sv;
-    const float dLt_tot = w * B.gD + dq0 * B.dx + dq1 * B.dy + dq2 * B.dz;
-    const float kt = dLt_tot / h.denom;
-    gv[0] = -dq0 + kt * s3.x; gv[1] = -dq1 + kt * s3.y; gv[2] = -dq2 + kt * s3.z;
-    gv[3] = cu * qx; gv[4] = cu * qy; gv[5] = cu * qz;
-    gv[6] = cv * qx; gv[7] = cv * qy; gv[8] = cv * qz;
-    gv[9] = w * sgn * B.gN0 - kt * qx; gv[10] = w * sgn * B.gN1 - kt * qy; gv[11] = w * sgn * B.gN2 - kt * qz;
-    gv[12] = -dLu * h.u / su * A.mod; gv[13] = -dLv * h.v / sv * A.mod;
-    gv[14] = h.G * dLa;
-    a.dO0 += dq0 - kt * s3.x; a.dO1 += dq1 - kt * s3.y; a.dO2 += dq2 - kt * s3.z;
-    a.dD0 += h.t * (dq0 - kt * s3.x); a.dD1 += h.t * (dq1 - kt * s3.y); a.dD2 += h.t * (dq2 - kt * s3.z);
+    float e0, e1, e2;
+    hit_geometry_grad(s0, s1, s2, s3, h, B.ox, B.oy, B.oz, B.dx, B.dy, B.dz, w, sgn, dLa, B.gD, B.gN0, B.gN1, B.gN2, A.mod,
+                      1.0f / s1.w, 1.0f / s2.w, 1.0f / h.denom, gv, e0, e1, e2);
+    a.dO0 += e0; a.dO1 += e1; a.dO2 += e2;
+    a.dD0 += h.t * e0; a.dD1 += h.t * e1; a.dD2 += h.t * e2;
     a.T = test_T;
     return true;
 }
@@ -550,12 +598,10 @@ __device__ __forceinline__ void bwd_store_ray(const TraceArgs &A, int r, const B
 #pragma unroll
         for (int k = 0; k < 16; k++) { dd0 += bgx[k] * a.Sk[k]; dd1 += bgy[k] * a.Sk[k]; dd2 += bgz[k] * a.Sk[k]; }
     }
-    const float inv3 = B.il * B.il * B.il;
-    const float e0 = a.dD0 + ((B.dl2 - B.dx * B.dx) * dd0 - B.dy * B.dx * dd1 - B.dz * B.dx * dd2) * inv3;
-    const float e1 = a.dD1 + (-B.dx * B.dy * dd0 + (B.dl2 - B.dy * B.dy) * dd1 - B.dz * B.dy * dd2) * inv3;
-    const float e2 = a.dD2 + (-B.dx * B.dz * dd0 - B.dy * B.dz * dd1 + (B.dl2 - B.dz * B.dz) * dd2) * inv3;
+    float e[3];
+    ray_dir_grad(B, dd0, dd1, dd2, e);
     A.dray_o[3 * r] = a.dO0; A.dray_o[3 * r + 1] = a.dO1; A.dray_o[3 * r + 2] = a.dO2;
-    A.dray_d[3 * r] = e0; A.dray_d[3 * r + 1] = e1; A.dray_d[3 * r + 2] = e2;
+    A.dray_d[3 * r] = a.dD0 + e[0]; A.dray_d[3 * r + 1] = a.dD1 + e[1]; A.dray_d[3 * r + 2] = a.dD2 + e[2];
 }
 
 // Rays are processed in a coherence-sorted order when A.order is set: 64 consecutive slots = one wavefront = rays with nearly the same

@@ -1,5 +1,6 @@
 // trace_surfel_bwd.hip -- list path backward: the surfel-major batch kernel (lane = ray, MFMA reduction), the per-surfel record reduction, the
-// parameter-gradient finish, and the per-ray atomic-flush fallback (composite_lists_bwd).
+// hits of sparse entries one lane each (sparse_hits_bwd), the parameter-gradient finish, and -- diagnostic build only -- the per-ray atomic-flush
+// backward (composite_lists_bwd).  The per-hit gradient itself is trace_common.h's (hit_geometry_grad and its neighbours).
 #include "trace_common.h"
 
 namespace envgs {
@@ -94,8 +95,7 @@ batch_surfel_bwd(const TraceArgs A)
         const int r = ray_of(A, base + lane);
         const bool valid = r < A.R && A.hit_cnt[r < A.R ? r : 0] <= A.cap;
         const int rr = r < A.R ? r : 0;
-        // Per-ray constants.  The suffix terms of dL/dalpha only ever appear as  sum_j g_j (final_j - prefix_j)  (+ the background term), so
-        // the twelve final sums fold into ONE scalar F = sum_j g_j final_j + T_final (bg . g_rgb): 17 live registers instead of 33.
+        // Per-ray constants.  The twelve final sums fold into ONE scalar (bwd_final_dot): 17 live registers instead of 33.
         float basis[16], Box, Boy, Boz, Bdx, Bdy, Bdz, gR0, gR1, gR2, gD, gA, gN0, gN1, gN2, gX0, gX1, Fsum;
         {
             BwdRay B;
@@ -114,8 +114,7 @@ batch_surfel_bwd(const TraceArgs A)
             gR0 = B.gR0; gR1 = B.gR1; gR2 = B.gR2;
             if constexpr (RGBO) { gD = gA = gN0 = gN1 = gN2 = gX0 = gX1 = 0.f; }
             else { gD = B.gD; gA = B.gA; gN0 = B.gN0; gN1 = B.gN1; gN2 = B.gN2; gX0 = B.gX0; gX1 = B.gX1; }
-            Fsum = B.gR0 * B.fr0 + B.gR1 * B.fr1 + B.gR2 * B.fr2 + B.gD * B.fD + B.gA * B.fA + B.gN0 * B.fN0 + B.gN1 * B.fN1 + B.gN2 * B.fN2 +
-                   B.gX0 * B.fX0 + B.gX1 * B.fX1 + B.fT * B.bgdot;
+            Fsum = bwd_final_dot(B);
         }
         // A operand of the reduction MFMAs, constant for the batch: lane l holds basis_{l & 15} of ray 4s + (l >> 4)
         float Areg[16];
@@ -325,39 +324,19 @@ batch_surfel_bwd(const TraceArgs A)
                     } else { const float4 x = sdat[buf][el][4]; col[0] = x.x; col[1] = x.y; col[2] = x.z; }
                     float x0 = 0.f, x1 = 0.f;                 // (staged with the record: a global load here sat on every entry's critical path)
                     if constexpr (OTH) { const float2 xo = sox[buf][el]; x0 = xo.x; x1 = xo.y; }
-                    const float alpha = h.alpha, Tb = st0.x;
-                    const float w = alpha * Tb;
+                    const float alpha = h.alpha, w = alpha * st0.x;
                     const float sgn = h.denom < 0.0f ? 1.0f : -1.0f;
                     const float nf0 = sgn * s3.x, nf1 = sgn * s3.y, nf2 = sgn * s3.z;
                     const float inv1m = __builtin_amdgcn_rcpf(1.0f - alpha);          // v_rcp_f32 (1 ulp): gradient-only terms need no IEEE division
-                    float gv_ = gR0 * col[0] + gR1 * col[1] + gR2 * col[2], gS = gR0 * st0.y + gR1 * st0.z + gR2 * st0.w;
-                    if constexpr (!RGBO) {
-                        gv_ += gD * h.t + gA + gN0 * nf0 + gN1 * nf1 + gN2 * nf2 + gX0 * x0 + gX1 * x1;
-                        gS += gD * st1.x + gA * (1.0f - Tb * (1.0f - alpha)) + gN0 * st1.y + gN1 * st1.z + gN2 * st1.w + gX0 * st2.x + gX1 * st2.y;
-                    }
-                    const float dLa = Tb * gv_ - (Fsum - gS) * inv1m;
-                    const float dc[3] = {cl[0] ? 0.f : w * gR0, cl[1] ? 0.f : w * gR1, cl[2] ? 0.f : w * gR2};
+                    const float dLa = alpha_grad_from_state(RGBO, gR0, gR1, gR2, gD, gA, gN0, gN1, gN2, gX0, gX1, Fsum, col, h.t, nf0, nf1, nf2, x0, x1,
+                                                            alpha, inv1m, st0, st1, st2.x, st2.y);
                     // dL/d(others) = sum over the batch's rays of w g_aux: words 15 / 16 of the (then five-register) transpose-reduce below and ONE two-lane
                     // atomic per entry (round 6; until then every lane added its own term -- 64 same-address atomics per entry and word: 2.1 of 5.1 ms)
                     if constexpr (OTH) { gw[15] = w * gX0; gx1 = w * gX1; }
-                    const float dLG = s0.w * dLa;
-                    const float dLu = dLG * (-h.G * h.u), dLv = dLG * (-h.G * h.v);
-                    const float isu = __builtin_amdgcn_rcpf(s1.w), isv = __builtin_amdgcn_rcpf(s2.w);
-                    const float qx = Box + h.t * Bdx - s0.x, qy = Boy + h.t * Bdy - s0.y, qz = Boz + h.t * Bdz - s0.z;
-                    const float dq0 = dLu * s1.x + dLv * s2.x, dq1 = dLu * s1.y + dLv * s2.y, dq2 = dLu * s1.z + dLv * s2.z;
-                    const float cu = dLu * isu, cv = dLv * isv;
-                    const float dLt_tot = w * gD + dq0 * Bdx + dq1 * Bdy + dq2 * Bdz;
-                    const float kt = dLt_tot * __builtin_amdgcn_rcpf(h.denom);
-                    BT(0) = dc[0]; BT(1) = dc[1]; BT(2) = dc[2];
-                    const float e0 = dq0 - kt * s3.x, e1 = dq1 - kt * s3.y, e2 = dq2 - kt * s3.z;
-                    gw[0] = -e0; gw[1] = -e1; gw[2] = -e2;
-                    gw[3] = cu * qx; gw[4] = cu * qy; gw[5] = cu * qz;
-                    gw[6] = cv * qx; gw[7] = cv * qy; gw[8] = cv * qz;
-                    const float ws = w * sgn;
-                    gw[9] = ws * gN0 - kt * qx; gw[10] = ws * gN1 - kt * qy; gw[11] = ws * gN2 - kt * qz;
-                    gw[12] = -cu * h.u * A.mod;
-                    gw[13] = -cv * h.v * A.mod;
-                    gw[14] = h.G * dLa;
+                    BT(0) = cl[0] ? 0.f : w * gR0; BT(1) = cl[1] ? 0.f : w * gR1; BT(2) = cl[2] ? 0.f : w * gR2;
+                    float e0, e1, e2;
+                    hit_geometry_grad(s0, s1, s2, s3, h, Box, Boy, Boz, Bdx, Bdy, Bdz, w, sgn, dLa, gD, gN0, gN1, gN2, A.mod,
+                                      __builtin_amdgcn_rcpf(s1.w), __builtin_amdgcn_rcpf(s2.w), __builtin_amdgcn_rcpf(h.denom), gw, e0, e1, e2);
                     dO0 += e0; dO1 += e1; dO2 += e2;
                     dD0 += h.t * e0; dD1 += h.t * e1; dD2 += h.t * e2;
                 } else {
@@ -481,8 +460,8 @@ template __global__ void __attribute__((amdgpu_waves_per_eu(ENVGS_BSB_WAVES, ENV
 // 64-lane pass on an entry whatever its hit count, so entries that 1-4 of the batch's rays blended (a fifth of the entries of the benchmark
 // view, three quarters for incoherent bounce rays) are differentiated here instead, each hit on its own -- its ray's constants, its per-hit
 // state row, the surfel's record and SH block gathered per lane -- and write one gradient record PER HIT (no reduction over rays is left to
-// do; reduce_surfel_records sums a surfel's records whoever wrote them).  Same formulas as batch_surfel_bwd (IEEE-rounded where that kernel
-// uses v_rcp_f32: the contract is 1e-4).  Runs AFTER the batch kernel, which stores the rays' gradients: this one adds to them.
+// do; reduce_surfel_records sums a surfel's records whoever wrote them).  The reciprocals are IEEE divisions where the batch kernel uses
+// v_rcp_f32 (the contract is 1e-4).  Runs AFTER the batch kernel, which stores the rays' gradients: this one adds to them.
 __global__ void __launch_bounds__(256)
 sparse_hits_bwd(const TraceArgs A, const int rgbo)
 {
@@ -526,48 +505,22 @@ sparse_hits_bwd(const TraceArgs A, const int rgbo)
         const float4 s0 = sr[0], s1 = sr[1], s2 = sr[2], s3 = sr[3];
         const SurfHit h = hit_surfel(s0, s1, s2, s3, B.ox, B.oy, B.oz, B.dx, B.dy, B.dz);
         float shv[48];
-        float col[3]; bool cl[3] = {false, false, false};
+        float col[3]; bool cl[3];
         if (A.M > 0) {
             load_sh(A, sid, nb, shv);
-            float c0 = 0.f, c1 = 0.f, c2 = 0.f;
-#pragma unroll
-            for (int q = 0; q < 16; q++) { const float b = basis[q]; c0 += b * shv[q * 3]; c1 += b * shv[q * 3 + 1]; c2 += b * shv[q * 3 + 2]; }
-            c0 += 0.5f; c1 += 0.5f; c2 += 0.5f;
-            cl[0] = c0 < 0.f; cl[1] = c1 < 0.f; cl[2] = c2 < 0.f;
-            col[0] = cl[0] ? 0.f : c0; col[1] = cl[1] ? 0.f : c1; col[2] = cl[2] ? 0.f : c2;
-        } else {
-            const Feat c = Feat{A.colors, A.f16 != 0}.at((size_t)sid * 3);
-            col[0] = c[0]; col[1] = c[1]; col[2] = c[2];
-        }
+            sh_colour_clamped(basis, shv, 16, col, cl);         // (basis and shv hold zeros beyond the active degree)
+        } else surfel_color(A, sid, basis, col, cl);
         const float x0 = (!rgbo && A.has_others) ? A.others[2 * sid] : 0.f, x1 = (!rgbo && A.has_others) ? A.others[2 * sid + 1] : 0.f;
-        const float alpha = h.alpha, Tb = st0.x, w = alpha * Tb;
+        const float alpha = h.alpha, w = alpha * st0.x;
         const float sgn = h.denom < 0.0f ? 1.0f : -1.0f;
         const float nf0 = sgn * s3.x, nf1 = sgn * s3.y, nf2 = sgn * s3.z;
-        const float inv1m = 1.0f / (1.0f - alpha);
-        const float Fsum = B.gR0 * B.fr0 + B.gR1 * B.fr1 + B.gR2 * B.fr2 + B.gD * B.fD + B.gA * B.fA + B.gN0 * B.fN0 + B.gN1 * B.fN1 + B.gN2 * B.fN2 +
-                           B.gX0 * B.fX0 + B.gX1 * B.fX1 + B.fT * B.bgdot;
-        float gv_ = B.gR0 * col[0] + B.gR1 * col[1] + B.gR2 * col[2], gS = B.gR0 * st0.y + B.gR1 * st0.z + B.gR2 * st0.w;
-        if (!rgbo) {
-            gv_ += B.gD * h.t + B.gA + B.gN0 * nf0 + B.gN1 * nf1 + B.gN2 * nf2 + B.gX0 * x0 + B.gX1 * x1;
-            gS += B.gD * st1.x + B.gA * (1.0f - Tb * (1.0f - alpha)) + B.gN0 * st1.y + B.gN1 * st1.z + B.gN2 * st1.w + B.gX0 * sx0 + B.gX1 * sx1;
-        }
-        const float dLa = Tb * gv_ - (Fsum - gS) * inv1m;
+        const float dLa = alpha_grad_from_state(rgbo != 0, B.gR0, B.gR1, B.gR2, B.gD, B.gA, B.gN0, B.gN1, B.gN2, B.gX0, B.gX1, bwd_final_dot(B), col, h.t,
+                                                nf0, nf1, nf2, x0, x1, alpha, 1.0f / (1.0f - alpha), st0, st1, sx0, sx1);
         const float dc[3] = {cl[0] ? 0.f : w * B.gR0, cl[1] ? 0.f : w * B.gR1, cl[2] ? 0.f : w * B.gR2};
-        const float dLG = s0.w * dLa;
-        const float dLu = dLG * (-h.G * h.u), dLv = dLG * (-h.G * h.v);
-        const float qx = B.ox + h.t * B.dx - s0.x, qy = B.oy + h.t * B.dy - s0.y, qz = B.oz + h.t * B.dz - s0.z;
-        const float dq0 = dLu * s1.x + dLv * s2.x, dq1 = dLu * s1.y + dLv * s2.y, dq2 = dLu * s1.z + dLv * s2.z;
-        const float cu = dLu / s1.w, cv = dLv / s2.w;
-        const float dLt_tot = w * B.gD + dq0 * B.dx + dq1 * B.dy + dq2 * B.dz;
-        const float kt = dLt_tot / h.denom;
-        const float e0 = dq0 - kt * s3.x, e1 = dq1 - kt * s3.y, e2 = dq2 - kt * s3.z;
-        float gw[16];
-        gw[0] = -e0; gw[1] = -e1; gw[2] = -e2;
-        gw[3] = cu * qx; gw[4] = cu * qy; gw[5] = cu * qz;
-        gw[6] = cv * qx; gw[7] = cv * qy; gw[8] = cv * qz;
-        const float ws = w * sgn;
-        gw[9] = ws * B.gN0 - kt * qx; gw[10] = ws * B.gN1 - kt * qy; gw[11] = ws * B.gN2 - kt * qz;
-        gw[12] = -cu * h.u * A.mod; gw[13] = -cv * h.v * A.mod; gw[14] = h.G * dLa; gw[15] = 0.f;
+        float gw[16], e0, e1, e2;
+        hit_geometry_grad(s0, s1, s2, s3, h, B.ox, B.oy, B.oz, B.dx, B.dy, B.dz, w, sgn, dLa, B.gD, B.gN0, B.gN1, B.gN2, A.mod,
+                          1.0f / s1.w, 1.0f / s2.w, 1.0f / h.denom, gw, e0, e1, e2);
+        gw[15] = 0.f;
         // the record: (16, 3) SH gradient = basis (x) dL/dcolour (or the 3 colour words), then the 15 geometry words
         const int copy = (slot >> 6) & (NCOPY - 1);
         const size_t ci = (size_t)sid * NCOPY + copy;
@@ -597,12 +550,10 @@ sparse_hits_bwd(const TraceArgs A, const int rgbo)
                 dd0 += bgx[q] * sk; dd1 += bgy[q] * sk; dd2 += bgz[q] * sk;
             }
         }
-        const float inv3 = B.il * B.il * B.il;
-        const float f0 = h.t * e0 + ((B.dl2 - B.dx * B.dx) * dd0 - B.dy * B.dx * dd1 - B.dz * B.dx * dd2) * inv3;
-        const float f1 = h.t * e1 + (-B.dx * B.dy * dd0 + (B.dl2 - B.dy * B.dy) * dd1 - B.dz * B.dy * dd2) * inv3;
-        const float f2 = h.t * e2 + (-B.dx * B.dz * dd0 - B.dy * B.dz * dd1 + (B.dl2 - B.dz * B.dz) * dd2) * inv3;
+        float f[3];
+        ray_dir_grad(B, dd0, dd1, dd2, f);
         atomic_add_f32(A.dray_o + 3 * r, e0); atomic_add_f32(A.dray_o + 3 * r + 1, e1); atomic_add_f32(A.dray_o + 3 * r + 2, e2);
-        atomic_add_f32(A.dray_d + 3 * r, f0); atomic_add_f32(A.dray_d + 3 * r + 1, f1); atomic_add_f32(A.dray_d + 3 * r + 2, f2);
+        atomic_add_f32(A.dray_d + 3 * r, h.t * e0 + f[0]); atomic_add_f32(A.dray_d + 3 * r + 1, h.t * e1 + f[1]); atomic_add_f32(A.dray_d + 3 * r + 2, h.t * e2 + f[2]);
         if (!rgbo && A.has_others && A.dothers) { atomic_add_f32(A.dothers + 2 * sid, w * B.gX0); atomic_add_f32(A.dothers + 2 * sid + 1, w * B.gX1); }
     }
 }

@@ -576,13 +576,14 @@ def test_trace_batch_table_overflow_and_unsorted_rays(sort_rays, request):
     assert table + singles <= res["cnt"]["hits"]
 
 
-@pytest.mark.parametrize("case", ["camera_sh_others", "free_rays_colours", "incoherent_table_overflow", "many_small_surfels", "colour_only_vs_batch_kernel"])
+@pytest.mark.parametrize("case", ["camera_sh_others", "free_rays_colours", "incoherent_table_overflow", "many_small_surfels", "colour_only_vs_batch_kernel",
+                                  "generic_three_forms"])
 def test_trace_sparse_entries_vs_oracle(case, request):
     """Round 6: SPARSE entries (include/envgs_trace.h: sparse_hits) -- (batch, surfel) entries of at most four hits are filed per hit by the
     forward and differentiated one lane per hit (sparse_hits_bwd) instead of costing the batch kernel a 64-lane pass each.  Forced on here (the
     default passes the list only when the tracer's previous call was incoherent): every output and gradient against the oracle, with SH and
     precomputed colours, with and without `others`, the generic and the colour-only backward, and a batch whose merge table overflows (those
-    one-hit entries are filed too: the batch kernel sees no singles)."""
+    one-hit entries are filed too: the batch kernel sees no singles); and the backward's forms against each other (the last two cases)."""
     from envgs_amd import tracing
     kw = dict(hip_ctx=_Switch(sparse="on", sparse_poison=SPARSE_POISON), after_hip=lambda: (tracing.last_entry_counts(), _check_sparse_list(request.node.name)))
     if case == "camera_sh_others":
@@ -630,6 +631,27 @@ def test_trace_sparse_entries_vs_oracle(case, request):
             check_close(request.node.name, k, a, b, tol=2e-5)
         check_close(request.node.name, "dray_o", got["on"][1].cpu().numpy(), got["off"][1].cpu().numpy(), tol=2e-5)
         check_close(request.node.name, "dray_d", got["on"][2].cpu().numpy(), got["off"][2].cpu().numpy(), tol=2e-5)
+        return
+    elif case == "generic_three_forms":
+        # the GENERIC backward (SH degree 3, `others`, all five outputs carry a gradient) in its three forms on the camera_sh_others scene -- sparse
+        # entries one lane per hit, every entry through the batch kernel, the K-buffer kernels -- pairwise: the two list forms evaluate the same
+        # expressions from the same stored state (2e-5, as the colour-only case above), the K-buffer form sums along the ray (the 1e-4 contract)
+        g, ro, rd = trace_scene(P=150, R=400, seed=7, camera=True)
+        ro, rd = _drop_fragile(request.node.name, g, ro, rd, True, sh_degree=3)[:2]
+        R = ro.shape[0]
+        gen = torch.Generator().manual_seed(9)
+        gr = [torch.randn(R, 3, generator=gen), torch.randn(R, generator=gen), torch.randn(R, generator=gen), torch.randn(R, 3, generator=gen), torch.randn(R, 2, generator=gen)]
+        got = {}
+        for form, sw in (("on", dict(sparse="on")), ("off", dict(sparse="off")), ("kbuffer", dict(no_lists=True))):
+            with _Switch(**sw):
+                _, L, o, d, _ = _run_hip(g, ro, rd, torch.tensor([0.3, 0.1, 0.7]), 3, True, True, grads=gr)
+                got[form] = (dict({k: t.grad.cpu().numpy() for k, t in L.items()}, dray_o=o.grad.cpu().numpy(), dray_d=d.grad.cpu().numpy()),
+                             tracing.LAST_STATS["cap"], tracing.last_trace_counts()["sparse_hits"])
+        assert got["on"][1] > 0 and got["on"][2] > 0 and got["off"][1] > 0 and got["off"][2] == 0 and got["kbuffer"][1] == 0, [v[1:] for v in got.values()]
+        for a, b, tol in (("on", "off", 2e-5), ("on", "kbuffer", 1e-4), ("off", "kbuffer", 1e-4)):
+            for k in got[a][0]:
+                mx = check_close(request.node.name, "%s_vs_%s.%s" % (a, b, k), got[a][0][k], got[b][0][k], tol=tol)
+                print("generic_three_forms %s vs %s %-10s max elementwise error %.3e (tol %.0e)" % (a, b, k, mx, tol))
         return
     else:
         g, ro, rd = trace_scene(P=2000, R=1024, seed=7, camera=False)
