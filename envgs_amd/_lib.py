@@ -100,6 +100,11 @@ SYMBOLS = {
     "envgs_bounce_pack_mid": (c_int, [ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_int32] + [_P] * 8 + [_P]),
     "envgs_reflect_forward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_float] + [_P] * 8 + [_P]),
     "envgs_reflect_backward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_float] + [_P] * 11 + [_P]),
+    "envgs_select_acc": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_float, _P, _P, _P]),
+    "envgs_reflect_filtered_forward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_int32] + [_P] * 10 + [_P]),
+    "envgs_reflect_filtered_backward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_int32] + [_P] * 13 + [_P]),
+    "envgs_blend_filtered_forward": (c_int, [ctypes.c_int32] * 4 + [_P] * 6 + [_P]),
+    "envgs_blend_filtered_backward": (c_int, [ctypes.c_int32] * 4 + [_P] * 7 + [_P]),
     "envgs_surface_normal_forward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float] + [_P] * 4 + [_P]),
     "envgs_surface_normal_backward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float] + [_P] * 5 + [_P]),
     "envgs_fused_adam": (c_int, [ctypes.c_int32, ctypes.POINTER(AdamTensor), ctypes.c_float, ctypes.c_float, ctypes.c_float, _P]),

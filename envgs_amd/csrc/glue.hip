@@ -298,12 +298,12 @@ int launch_sh_record_bwd(int P, int D, const float *means3D, const float *shs, c
 }
 
 // ------------------------------------------------------------------------------------------------ reflect
-__global__ void __launch_bounds__(256)
-reflect_fwd(int HW, float ratio, const float *__restrict__ allmap, const float *__restrict__ ray_o, const float *__restrict__ ray_d,
-            const float *__restrict__ V, float *__restrict__ nw, float *__restrict__ depth, float *__restrict__ ref_o, float *__restrict__ ref_d)
+// One pixel of the reflected-ray construction; the dense and the filtered kernels both call it, so the two cannot drift.  ro / rd: this pixel's
+// output row of ref_o / ref_d (dense: row p; filtered: row positions[p] of a kept pixel, NULL for a pixel that is not kept).
+__device__ __forceinline__ void reflect_pixel_fwd(int HW, int p, float ratio, const float *__restrict__ allmap, const float *__restrict__ ray_o,
+                                                  const float *__restrict__ ray_d, const float *__restrict__ V, float *__restrict__ nw,
+                                                  float *__restrict__ depth, float *__restrict__ ro, float *__restrict__ rd)
 {
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= HW) return;
     const float Dw = allmap[p], A = allmap[HW + p], n0 = allmap[2 * HW + p], n1 = allmap[3 * HW + p], n2 = allmap[4 * HW + p], med = allmap[5 * HW + p];
     // normal_world_c = sum_k n_view_k * V[c][k]   (V = world_view_transform, rows 0..2 = R^T)
     const float w0 = n0 * V[0] + n1 * V[1] + n2 * V[2], w1 = n0 * V[4] + n1 * V[5] + n2 * V[6], w2 = n0 * V[8] + n1 * V[9] + n2 * V[10];
@@ -314,27 +314,52 @@ reflect_fwd(int HW, float ratio, const float *__restrict__ allmap, const float *
     const float dep = de * (1.0f - ratio) + dm * ratio;
     nw[p] = w0; nw[HW + p] = w1; nw[2 * HW + p] = w2;
     depth[p] = dep;
+    if (!ro) return;
     const float len = sqrtf(w0 * w0 + w1 * w1 + w2 * w2), il = 1.0f / (len + 1e-8f);     // math_utils.normalize: x / (|x| + 1e-8)
     const float u0 = w0 * il, u1 = w1 * il, u2 = w2 * il;
     const float o0 = ray_o[3 * p], o1 = ray_o[3 * p + 1], o2 = ray_o[3 * p + 2];
     const float d0 = ray_d[3 * p], d1 = ray_d[3 * p + 1], d2 = ray_d[3 * p + 2];
     const float dn = d0 * u0 + d1 * u1 + d2 * u2;
-    ref_d[3 * p] = d0 - 2.0f * dn * u0; ref_d[3 * p + 1] = d1 - 2.0f * dn * u1; ref_d[3 * p + 2] = d2 - 2.0f * dn * u2;
-    ref_o[3 * p] = o0 + d0 * dep; ref_o[3 * p + 1] = o1 + d1 * dep; ref_o[3 * p + 2] = o2 + d2 * dep;
+    rd[0] = d0 - 2.0f * dn * u0; rd[1] = d1 - 2.0f * dn * u1; rd[2] = d2 - 2.0f * dn * u2;
+    ro[0] = o0 + d0 * dep; ro[1] = o1 + d1 * dep; ro[2] = o2 + d2 * dep;
 }
 
 __global__ void __launch_bounds__(256)
-reflect_bwd(int HW, float ratio, const float *__restrict__ allmap, const float *__restrict__ ray_o, const float *__restrict__ ray_d,
-            const float *__restrict__ V, const float *__restrict__ dnw, const float *__restrict__ ddepth, const float *__restrict__ dref_o,
-            const float *__restrict__ dref_d, float *__restrict__ dallmap, float *__restrict__ dray_o, float *__restrict__ dray_d)
+reflect_fwd(int HW, float ratio, const float *__restrict__ allmap, const float *__restrict__ ray_o, const float *__restrict__ ray_d,
+            const float *__restrict__ V, float *__restrict__ nw, float *__restrict__ depth, float *__restrict__ ref_o, float *__restrict__ ref_d)
 {
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= HW) return;
+    reflect_pixel_fwd(HW, p, ratio, allmap, ray_o, ray_d, V, nw, depth, ref_o + 3 * (size_t)p, ref_d + 3 * (size_t)p);
+}
+
+// Filtered form (envgs_sampler.py:433-455): normal_world / depth for every pixel, ref_o / ref_d as COMPACT rows -- kept pixel p owns row
+// positions[p], its rank among the kept pixels in row-major order (envgs_compact_scan), which is the order of torch's x[mask].
+__global__ void __launch_bounds__(256)
+reflect_filtered_fwd(int HW, int n_kept, float ratio, const float *__restrict__ allmap, const float *__restrict__ ray_o,
+                     const float *__restrict__ ray_d, const float *__restrict__ V, const uint8_t *__restrict__ keep,
+                     const uint32_t *__restrict__ pos, float *__restrict__ nw, float *__restrict__ depth, float *__restrict__ ref_o,
+                     float *__restrict__ ref_d)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= HW) return;
+    const uint32_t row = keep[p] ? pos[p] : 0xffffffffu;
+    const bool kept = row < (uint32_t)n_kept;                                 // (a row outside the compact tensors is never written)
+    reflect_pixel_fwd(HW, p, ratio, allmap, ray_o, ray_d, V, nw, depth, kept ? ref_o + 3 * (size_t)row : nullptr, kept ? ref_d + 3 * (size_t)row : nullptr);
+}
+
+// One pixel of the backward, shared like reflect_pixel_fwd.  go / gd: this pixel's row of dref_o / dref_d, NULL = no such gradient (an unused
+// output, or a pixel that is not kept: it then receives the dense terms only and its dray_o / dray_d are zero).
+__device__ __forceinline__ void reflect_pixel_bwd(int HW, int p, float ratio, const float *__restrict__ allmap, const float *__restrict__ ray_d,
+                                                  const float *__restrict__ V, const float *__restrict__ dnw, const float *__restrict__ ddepth,
+                                                  const float *__restrict__ go, const float *__restrict__ gd, float *__restrict__ dallmap,
+                                                  float *__restrict__ dray_o, float *__restrict__ dray_d)
+{
     const float Dw = allmap[p], A = allmap[HW + p], n0 = allmap[2 * HW + p], n1 = allmap[3 * HW + p], n2 = allmap[4 * HW + p], med = allmap[5 * HW + p];
     const float w0 = n0 * V[0] + n1 * V[1] + n2 * V[2], w1 = n0 * V[4] + n1 * V[5] + n2 * V[6], w2 = n0 * V[8] + n1 * V[9] + n2 * V[10];
     const float d0 = ray_d[3 * p], d1 = ray_d[3 * p + 1], d2 = ray_d[3 * p + 2];
-    const float go0 = dref_o ? dref_o[3 * p] : 0.f, go1 = dref_o ? dref_o[3 * p + 1] : 0.f, go2 = dref_o ? dref_o[3 * p + 2] : 0.f;
-    const float gd0 = dref_d ? dref_d[3 * p] : 0.f, gd1 = dref_d ? dref_d[3 * p + 1] : 0.f, gd2 = dref_d ? dref_d[3 * p + 2] : 0.f;
+    const float go0 = go ? go[0] : 0.f, go1 = go ? go[1] : 0.f, go2 = go ? go[2] : 0.f;
+    const float gd0 = gd ? gd[0] : 0.f, gd1 = gd ? gd[1] : 0.f, gd2 = gd ? gd[2] : 0.f;
     float de = Dw / A; const bool de_ok = fabsf(de) <= 3.0e38f; if (!de_ok) de = 0.f;
     float dm = med; const bool dm_ok = fabsf(dm) <= 3.0e38f; if (!dm_ok) dm = 0.f;
     const float dep = de * (1.0f - ratio) + dm * ratio;
@@ -372,6 +397,39 @@ reflect_bwd(int HW, float ratio, const float *__restrict__ allmap, const float *
     }
 }
 
+__global__ void __launch_bounds__(256)
+reflect_bwd(int HW, float ratio, const float *__restrict__ allmap, const float *__restrict__ ray_o, const float *__restrict__ ray_d,
+            const float *__restrict__ V, const float *__restrict__ dnw, const float *__restrict__ ddepth, const float *__restrict__ dref_o,
+            const float *__restrict__ dref_d, float *__restrict__ dallmap, float *__restrict__ dray_o, float *__restrict__ dray_d)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= HW) return;
+    reflect_pixel_bwd(HW, p, ratio, allmap, ray_d, V, dnw, ddepth, dref_o ? dref_o + 3 * (size_t)p : nullptr, dref_d ? dref_d + 3 * (size_t)p : nullptr,
+                      dallmap, dray_o, dray_d);
+}
+
+// dref_o / dref_d are the COMPACT (n_kept,3) gradients; dallmap (7,H,W) and dray_o / dray_d (H,W,3) are written for every pixel
+__global__ void __launch_bounds__(256)
+reflect_filtered_bwd(int HW, int n_kept, float ratio, const float *__restrict__ allmap, const float *__restrict__ ray_d, const float *__restrict__ V,
+                     const uint8_t *__restrict__ keep, const uint32_t *__restrict__ pos, const float *__restrict__ dnw,
+                     const float *__restrict__ ddepth, const float *__restrict__ dref_o, const float *__restrict__ dref_d,
+                     float *__restrict__ dallmap, float *__restrict__ dray_o, float *__restrict__ dray_d)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= HW) return;
+    const uint32_t row = keep[p] ? pos[p] : 0xffffffffu;
+    const bool kept = row < (uint32_t)n_kept;
+    reflect_pixel_bwd(HW, p, ratio, allmap, ray_d, V, dnw, ddepth, (kept && dref_o) ? dref_o + 3 * (size_t)row : nullptr,
+                      (kept && dref_d) ? dref_d + 3 * (size_t)row : nullptr, dallmap, dray_o, dray_d);
+}
+
+// keep[p] = alpha > thr, the reference's acc filter (envgs_sampler.py:443: strict)
+__global__ void __launch_bounds__(256)
+select_acc(int HW, float thr, const float *__restrict__ allmap, uint8_t *__restrict__ keep)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p < HW) keep[p] = allmap[HW + p] > thr ? 1 : 0;
+}
 
 // ------------------------------------------------------------------------------------------------ surface normal (dpt2norm)
 // Tail of render() (gaussian2d_utils.py:1125-1142): surface depth = expected depth mixed with the median depth, back-projected through
@@ -523,18 +581,46 @@ surfel_quads(int P, const float *__restrict__ means, const float *__restrict__ s
     }
 }
 
-// rgb = (1 - s) img[:3] + s rgb_env, one lane per pixel (img is channel-major, rgb_env / rgb pixel-major)
+// rgb = (1 - s) img[:3] + s rgb_env, one lane per pixel (img is channel-major, rgb_env / rgb pixel-major).  The per-pixel arithmetic is shared by
+// the dense and the filtered kernels; e: this pixel's row of rgb_env.
+__device__ __forceinline__ void blend_pixel_fwd(int HW, int C, int p, const float *__restrict__ img, const float *__restrict__ e, float *__restrict__ rgb,
+                                                float *__restrict__ ref_rgb)
+{
+    const int S = C - 4;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const float s = img[(size_t)(3 + (S == 3 ? c : 0)) * HW + p], se = s * e[c];
+        // the fused multiply-add is spelled out: left to the compiler, which of the two products it contracts depends on the other uses of s * e,
+        // and the filtered kernel (which has one, ref_rgb) would round differently from the dense one
+        rgb[(size_t)p * 3 + c] = __builtin_fmaf(1.0f - s, img[(size_t)c * HW + p], se);
+        if (ref_rgb) ref_rgb[(size_t)p * 3 + c] = se * 2.0f;                  // envgs_sampler.py:476, the visualisation image
+    }
+}
+
+// e / de: this pixel's row of rgb_env / drgb_env (de may be NULL)
+__device__ __forceinline__ void blend_pixel_bwd(int HW, int C, int p, const float *__restrict__ img, const float *__restrict__ e, const float *__restrict__ g,
+                                                float *__restrict__ dimg, float *__restrict__ de)
+{
+    const int S = C - 4;
+    float ds[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const int sc = S == 3 ? c : 0;
+        const float s = img[(size_t)(3 + sc) * HW + p], gc = g[(size_t)p * 3 + c];
+        dimg[(size_t)c * HW + p] = (1.0f - s) * gc;
+        if (de) de[c] = s * gc;
+        ds[sc] += (e[c] - img[(size_t)c * HW + p]) * gc;
+    }
+    for (int sc = 0; sc < S; sc++) dimg[(size_t)(3 + sc) * HW + p] = ds[sc];
+    dimg[(size_t)(C - 1) * HW + p] = 0.f;
+}
+
 __global__ void __launch_bounds__(256)
 blend_fwd(int HW, int C, const float *__restrict__ img, const float *__restrict__ env, float *__restrict__ rgb)
 {
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= HW) return;
-    const int S = C - 4;
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const float s = img[(size_t)(3 + (S == 3 ? c : 0)) * HW + p];
-        rgb[(size_t)p * 3 + c] = (1.0f - s) * img[(size_t)c * HW + p] + s * env[(size_t)p * 3 + c];
-    }
+    blend_pixel_fwd(HW, C, p, img, env + (size_t)p * 3, rgb, nullptr);
 }
 
 __global__ void __launch_bounds__(256)
@@ -543,18 +629,39 @@ blend_bwd(int HW, int C, const float *__restrict__ img, const float *__restrict_
 {
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= HW) return;
-    const int S = C - 4;
-    float ds[3] = {0.f, 0.f, 0.f};
+    blend_pixel_bwd(HW, C, p, img, env + (size_t)p * 3, g, dimg, denv ? denv + (size_t)p * 3 : nullptr);
+}
+
+// Filtered form (envgs_sampler.py:465-476): env (n_kept,3) holds the traced colour of the kept pixels only, row positions[p] belongs to pixel p.
+// A pixel that is not kept keeps its base colour bit for bit; ref_rgb (optional) is zero there.
+__global__ void __launch_bounds__(256)
+blend_filtered_fwd(int HW, int C, int n_kept, const float *__restrict__ img, const float *__restrict__ env, const uint8_t *__restrict__ keep,
+                   const uint32_t *__restrict__ pos, float *__restrict__ rgb, float *__restrict__ ref_rgb)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= HW) return;
+    const uint32_t row = keep[p] ? pos[p] : 0xffffffffu;
+    if (row < (uint32_t)n_kept) { blend_pixel_fwd(HW, C, p, img, env + (size_t)row * 3, rgb, ref_rgb); return; }
 #pragma unroll
     for (int c = 0; c < 3; c++) {
-        const int sc = S == 3 ? c : 0;
-        const float s = img[(size_t)(3 + sc) * HW + p], gc = g[(size_t)p * 3 + c];
-        dimg[(size_t)c * HW + p] = (1.0f - s) * gc;
-        if (denv) denv[(size_t)p * 3 + c] = s * gc;
-        ds[sc] += (env[(size_t)p * 3 + c] - img[(size_t)c * HW + p]) * gc;
+        rgb[(size_t)p * 3 + c] = img[(size_t)c * HW + p];
+        if (ref_rgb) ref_rgb[(size_t)p * 3 + c] = 0.f;
     }
-    for (int sc = 0; sc < S; sc++) dimg[(size_t)(3 + sc) * HW + p] = ds[sc];
-    dimg[(size_t)(C - 1) * HW + p] = 0.f;
+}
+
+// dimg (C,H,W) is written for every pixel (a pixel that is not kept: g in the colour channels, 0 in the others); denv (n_kept,3), optional, is
+// written by the pixel that owns the row -- every row has exactly one owner, so nothing is accumulated
+__global__ void __launch_bounds__(256)
+blend_filtered_bwd(int HW, int C, int n_kept, const float *__restrict__ img, const float *__restrict__ env, const uint8_t *__restrict__ keep,
+                   const uint32_t *__restrict__ pos, const float *__restrict__ g, float *__restrict__ dimg, float *__restrict__ denv)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= HW) return;
+    const uint32_t row = keep[p] ? pos[p] : 0xffffffffu;
+    if (row < (uint32_t)n_kept) { blend_pixel_bwd(HW, C, p, img, env + (size_t)row * 3, g, dimg, denv ? denv + (size_t)row * 3 : nullptr); return; }
+#pragma unroll
+    for (int c = 0; c < 3; c++) dimg[(size_t)c * HW + p] = g[(size_t)p * 3 + c];
+    for (int c = 3; c < C; c++) dimg[(size_t)c * HW + p] = 0.f;
 }
 
 
@@ -720,6 +827,40 @@ int envgs_reflect_backward(int32_t H, int32_t W, float depth_ratio, const float 
     return (int)hipGetLastError();
 }
 
+int envgs_select_acc(int32_t H, int32_t W, float threshold, const float *allmap, uint8_t *keep, void *stream)
+{
+    if (H <= 0 || W <= 0 || !allmap || !keep) return ENVGS_ERR_BAD_ARG;
+    const int HW = H * W;
+    hipLaunchKernelGGL(select_acc, dim3((HW + 255) / 256), dim3(256), 0, (hipStream_t)stream, HW, threshold, allmap, keep);
+    return (int)hipGetLastError();
+}
+
+int envgs_reflect_filtered_forward(int32_t H, int32_t W, float depth_ratio, int32_t n_kept, const float *allmap, const float *ray_o,
+                                   const float *ray_d, const float *viewmatrix, const uint8_t *keep, const uint32_t *positions,
+                                   float *normal_world, float *depth, float *ref_o, float *ref_d, void *stream)
+{
+    if (H <= 0 || W <= 0 || n_kept < 0 || (int64_t)n_kept > (int64_t)H * W) return ENVGS_ERR_BAD_ARG;
+    if (!allmap || !ray_o || !ray_d || !viewmatrix || !keep || !positions || !normal_world || !depth) return ENVGS_ERR_BAD_ARG;
+    if (n_kept > 0 && (!ref_o || !ref_d)) return ENVGS_ERR_BAD_ARG;
+    const int HW = H * W;
+    hipLaunchKernelGGL(reflect_filtered_fwd, dim3((HW + 255) / 256), dim3(256), 0, (hipStream_t)stream, HW, n_kept, depth_ratio, allmap, ray_o, ray_d,
+                       viewmatrix, keep, positions, normal_world, depth, ref_o, ref_d);
+    return (int)hipGetLastError();
+}
+
+int envgs_reflect_filtered_backward(int32_t H, int32_t W, float depth_ratio, int32_t n_kept, const float *allmap, const float *ray_o,
+                                    const float *ray_d, const float *viewmatrix, const uint8_t *keep, const uint32_t *positions,
+                                    const float *dnormal_world, const float *ddepth, const float *dref_o, const float *dref_d, float *dallmap,
+                                    float *dray_o, float *dray_d, void *stream)
+{
+    if (H <= 0 || W <= 0 || n_kept < 0 || (int64_t)n_kept > (int64_t)H * W) return ENVGS_ERR_BAD_ARG;
+    if (!allmap || !ray_o || !ray_d || !viewmatrix || !keep || !positions || !dallmap) return ENVGS_ERR_BAD_ARG;
+    const int HW = H * W;
+    hipLaunchKernelGGL(reflect_filtered_bwd, dim3((HW + 255) / 256), dim3(256), 0, (hipStream_t)stream, HW, n_kept, depth_ratio, allmap, ray_d,
+                       viewmatrix, keep, positions, dnormal_world, ddepth, dref_o, dref_d, dallmap, dray_o, dray_d);
+    return (int)hipGetLastError();
+}
+
 int envgs_surface_normal_forward(int32_t H, int32_t W, float depth_ratio, float fx, float fy, const float *allmap, const float *viewmatrix,
                                  float *surf_depth, float *surf_normal, void *stream)
 {
@@ -763,6 +904,28 @@ int envgs_blend_backward(int32_t H, int32_t W, int32_t channels, const float *im
     if (H <= 0 || W <= 0 || (channels != 5 && channels != 7) || !img || !rgb_env || !drgb || !dimg) return ENVGS_ERR_BAD_ARG;
     const int HW = H * W;
     hipLaunchKernelGGL(blend_bwd, dim3((HW + 255) / 256), dim3(256), 0, (hipStream_t)stream, HW, channels, img, rgb_env, drgb, dimg, drgb_env);
+    return (int)hipGetLastError();
+}
+
+int envgs_blend_filtered_forward(int32_t H, int32_t W, int32_t channels, int32_t n_kept, const float *img, const float *rgb_env, const uint8_t *keep,
+                                 const uint32_t *positions, float *rgb, float *ref_rgb, void *stream)
+{
+    if (H <= 0 || W <= 0 || (channels != 5 && channels != 7) || n_kept < 0 || (int64_t)n_kept > (int64_t)H * W) return ENVGS_ERR_BAD_ARG;
+    if (!img || !keep || !positions || !rgb || (n_kept > 0 && !rgb_env)) return ENVGS_ERR_BAD_ARG;
+    const int HW = H * W;
+    hipLaunchKernelGGL(blend_filtered_fwd, dim3((HW + 255) / 256), dim3(256), 0, (hipStream_t)stream, HW, channels, n_kept, img, rgb_env, keep, positions,
+                       rgb, ref_rgb);
+    return (int)hipGetLastError();
+}
+
+int envgs_blend_filtered_backward(int32_t H, int32_t W, int32_t channels, int32_t n_kept, const float *img, const float *rgb_env, const uint8_t *keep,
+                                  const uint32_t *positions, const float *drgb, float *dimg, float *drgb_env, void *stream)
+{
+    if (H <= 0 || W <= 0 || (channels != 5 && channels != 7) || n_kept < 0 || (int64_t)n_kept > (int64_t)H * W) return ENVGS_ERR_BAD_ARG;
+    if (!img || !keep || !positions || !drgb || !dimg || (n_kept > 0 && !rgb_env)) return ENVGS_ERR_BAD_ARG;
+    const int HW = H * W;
+    hipLaunchKernelGGL(blend_filtered_bwd, dim3((HW + 255) / 256), dim3(256), 0, (hipStream_t)stream, HW, channels, n_kept, img, rgb_env, keep, positions,
+                       drgb, dimg, drgb_env);
     return (int)hipGetLastError();
 }
 

@@ -8,6 +8,8 @@ Followed call sequence (all paths relative to /root/reference):
   easyvolcap/models/samplers/envgs_sampler.py:420-455       get_reflect_rays: ref_d = d - 2(d.n)n, ref_o = o + d*depth
   easyvolcap/utils/optix_utils.py:71-85,87-267              build_bvh (get_disks + rebuild) and render_gaussians (env pass)
   easyvolcap/models/samplers/envgs_sampler.py:474           rgb = (1 - spec) * rgb_base + spec * rgb_env
+  easyvolcap/models/samplers/envgs_sampler.py:433-455       filtered form: ref_msk, ref_o[ref_msk][None] (FILTER below)
+  easyvolcap/models/samplers/envgs_sampler.py:461-476       filtered form: the masked blend and ref_rgb_map
 """
 import torch
 
@@ -120,6 +122,41 @@ DEFER = {"on": False}
 TRACE = {"depth": 0, "specular_threshold": 0.0}    # EnvGS hard-codes 0 bounces (envgs_sampler.py:510,548); bench.py --trace-depth overrides
 
 
+# Filtered reflection rays (envgs_sampler.py:433-455): once acc_filtering_start_iter / specular_filtering_start_iter is reached the reference traces
+# only the pixels of a mask -- (1,S,3) rays, S < H*W -- and scatters the traced colour back (:461-476).  mode None: every pixel, as before.
+# "acc": alpha > acc_threshold (:443; configs/models/envgs_synth.yaml turns it on at iteration 30000).  "specular": spec above its
+# specular_percent quantile (:441; the reference's config calls it "do not use this": torch.quantile in both caller forms).
+FILTER = {"mode": None, "acc_threshold": 0.75, "specular_percent": 0.75}
+
+
+def reflection_mask(mode, alpha=None, spec=None, acc_threshold=0.75, specular_percent=0.75):
+    """ref_msk of envgs_sampler.py:438-443.  alpha (..., 1) / spec (..., S): acc_map / spec_map, pixels leading; returns a bool tensor of the
+    leading shape.  Works on CPU tensors."""
+    if mode == "specular":
+        s0 = spec[..., 0]
+        return s0 > torch.quantile(s0, specular_percent)
+    if mode == "acc":
+        return alpha[..., 0] > acc_threshold
+    raise ValueError("reflection filter mode must be 'acc' or 'specular', got %r" % (mode,))
+
+
+def filtered_rays(ref_o, ref_d, mask):
+    """envgs_sampler.py:444-445: the rays of the masked pixels, (1,S,3) each, in row-major pixel order."""
+    return ref_o[mask][None], ref_d[mask][None]
+
+
+def filtered_blend(rgb, spec, rgb_env, mask):
+    """envgs_sampler.py:465-476.  rgb (..., 3), spec (..., 1 or 3) with the mask's leading shape, rgb_env (1,S,3) or (S,3): the traced colour of the
+    masked pixels.  Returns (rgb, ref_rgb): the blend at the masked pixels and the base colour elsewhere; the visualisation image."""
+    env = rgb_env.reshape(-1, 3)
+    out = rgb.clone()                                   # (the reference assigns into output.rgb_map in place)
+    out[mask] = (1 - spec[mask]) * rgb[mask] + spec[mask] * env
+    ref_rgb = torch.zeros_like(rgb)
+    ref_rgb[mask] = env
+    ref_rgb = ref_rgb * spec * 2
+    return out, ref_rgb
+
+
 def _apply_policy(tracer):
     """REFIT["every"] -> the tracer's policy, ONCE per change of the value: a policy the user set on the tracer afterwards stays, and only the
     fields this module owns (mode, max_age) are touched -- max_growth is the tracer's / the user's."""
@@ -196,6 +233,8 @@ def envgs_forward(pkg, tpkg, tracer, cam, rays, base, env, bg, env_bg, sh_degree
     prepared_v = env_prepare(tracer, env) if (FUSED["on"] and not REFERENCE_FORMS["on"] and PREBUILD["on"] and hasattr(tracer, "prepare")) else None
     b = base_pass(pkg, cam, base, bg, sh_degree)
     ray_o, ray_d = rays
+    if FILTER["mode"] is not None:
+        return _filtered_forward(tracer, tpkg, cam, env, b, ray_o, ray_d, env_bg, sh_degree, prepared_v)
     if FUSED["on"]:
         from . import fused
         nw, dep, ref_o, ref_d = fused.reflect(b["allmap"], ray_o, ray_d, cam.world_view_transform, 0.0)
@@ -213,3 +252,38 @@ def envgs_forward(pkg, tpkg, tracer, cam, rays, base, env, bg, env_bg, sh_degree
     spec = b["spec"].permute(1, 2, 0)
     rgb = (1 - spec) * b["rgb"].permute(1, 2, 0) + spec * rgb_env
     return dict(rgb=rgb, base=b, rgb_env=rgb_env, env_wet=wet, ref_o=ref_o, ref_d=ref_d)
+
+
+def _filtered_forward(tracer, tpkg, cam, env, b, ray_o, ray_d, env_bg, sh_degree, prepared_v):
+    """The tail of envgs_forward with FILTER["mode"] set: only the S pixels of ref_msk are traced, both caller forms hand the tracer (1,S,3) rays.
+    S = 0: no env pass, the base colour is the result."""
+    mode, thr, pct = FILTER["mode"], float(FILTER["acc_threshold"]), float(FILTER["specular_percent"])
+    if FUSED["on"]:
+        from . import fused
+        if mode == "acc":
+            sel = fused.select_pixels(allmap=b["allmap"], acc_threshold=thr)
+        else:
+            sel = fused.select_pixels(mask=reflection_mask(mode, spec=b["spec"].detach().permute(1, 2, 0), specular_percent=pct))
+        mask = sel.mask
+        nw, dep, ref_o, ref_d = fused.reflect_filtered(b["allmap"], ray_o, ray_d, cam.world_view_transform, sel, 0.0)
+        b["normal"], b["depth"] = nw, dep
+    else:
+        if REFERENCE_FORMS["on"]:
+            b["surf_depth"], b["surf_normal"] = REFERENCE_FORMS["surface_maps"](cam, b["allmap"], 0.0)
+        nrm = b["normal"].permute(1, 2, 0)
+        nrm = nrm / (nrm.norm(dim=-1, keepdim=True) + 1e-8)            # easyvolcap/utils/math_utils.py:6-8
+        ref_d = ray_d - 2 * (ray_d * nrm).sum(-1, keepdim=True) * nrm
+        ref_o = ray_o + ray_d * b["depth"].permute(1, 2, 0)
+        mask = reflection_mask(mode, alpha=b["alpha"].detach().permute(1, 2, 0), spec=b["spec"].detach().permute(1, 2, 0), acc_threshold=thr,
+                               specular_percent=pct)
+        ref_o, ref_d = filtered_rays(ref_o, ref_d, mask)
+    if ref_o.shape[1] > 0:
+        rgb_env, dpt, acc, norm, dist, aux, mid, wet = env_pass(tracer, tpkg, cam, env, ref_o, ref_d, env_bg, sh_degree, prepared_v if FUSED["on"] else None)
+    else:
+        rgb_env = ref_o.detach().new_zeros(1, 0, 3)
+        wet = torch.zeros_like(env["means3D"][:, :1]).detach()
+    if FUSED["on"]:
+        rgb, ref_rgb = fused.blend_filtered(b["img"], rgb_env, sel)
+    else:
+        rgb, ref_rgb = filtered_blend(b["rgb"].permute(1, 2, 0), b["spec"].permute(1, 2, 0), rgb_env, mask)
+    return dict(rgb=rgb, base=b, rgb_env=rgb_env, env_wet=wet, ref_o=ref_o, ref_d=ref_d, ref_msk=mask, ref_rgb=ref_rgb)

@@ -5,6 +5,8 @@ reference evaluates between its two extension calls.  Optional -- the extensions
         == cat([clamp_min(eval_sh(deg, shs^T, normalize(xyz - campos)) + 0.5, 0), specular, roughness], -1)     gaussian2d_utils.py:1071-1084
     reflect(allmap, ray_o, ray_d, viewmatrix, depth_ratio=0.0) -> normal_world (3,H,W), depth (1,H,W), ref_o (H,W,3), ref_d (H,W,3)
         == gaussian2d_utils.py:1119-1136 + envgs_sampler.py:420-431
+    select_pixels / reflect_filtered / blend_filtered: the same two stages when only the pixels of a mask are traced
+        == envgs_sampler.py:433-455 (ref_msk, ref_o[ref_msk][None]) and :461-476 (the masked blend, ref_rgb_map)
 """
 import torch
 
@@ -194,6 +196,145 @@ def blend(img, rgb_env):
     traced colour rgb_env (H,W,3): envgs_sampler.py:474, one launch each way instead of ~20 (include/envgs_glue.h)."""
     return _Blend.apply(img, rgb_env)
 
+
+class PixelSelection:
+    """The pixels whose reflection rays are traced (select_pixels).  mask (H,W) bool: the reference's ref_msk; count: S, a host int; keep (H*W)
+    uint8 and positions (H*W) int32 on the device: kept pixel p owns compact row positions[p], its rank in row-major order (= x[mask] order)."""
+    __slots__ = ("mask", "count", "keep", "positions", "H", "W")
+
+    def __init__(self, mask, count, keep, positions):
+        self.mask, self.count, self.keep, self.positions = mask, count, keep, positions
+        self.H, self.W = mask.shape
+
+
+def select_pixels(mask=None, allmap=None, acc_threshold=0.75):
+    """The pixel selection of a filtered reflection pass.  Exactly one of
+        mask   (H,W) bool / uint8 on the GPU: any selection the caller computed (the reference's specular filter, envgs_sampler.py:441), or
+        allmap (7,H,W): the acc filter, mask = allmap[1] > acc_threshold (:443), evaluated by one kernel.
+    One prefix scan (envgs_compact_scan) gives every kept pixel its compact row and the kept count; reading that count is the ONE host
+    synchronisation of the filtered path (the tracer launches by ray count; the reference's boolean indexing synchronises at the same place)."""
+    if (mask is None) == (allmap is None):
+        raise ValueError("select_pixels: give exactly one of mask and allmap")
+    lib = _lib.load()
+    src = mask if mask is not None else allmap
+    dev = src.device
+    if dev.type != "cuda":
+        raise RuntimeError("envgs_amd.fused needs tensors on the GPU; there is no CPU path")
+    p = _lib.ptr
+    if mask is not None:
+        if mask.dim() != 2:
+            raise ValueError("select_pixels: mask must be (H,W), got %s" % (tuple(mask.shape),))
+        H, W = mask.shape
+        mask = (mask if mask.dtype == torch.bool else mask != 0).contiguous()
+        keep = mask.view(torch.uint8).reshape(-1)                           # (bool storage is one 0 / 1 byte per element)
+    else:
+        if allmap.dim() != 3 or allmap.shape[0] < 2:
+            raise ValueError("select_pixels: allmap must be (7,H,W), got %s" % (tuple(allmap.shape),))
+        a = _f32c(allmap.detach())
+        _, H, W = a.shape
+        keep = torch.empty(H * W, dtype=torch.uint8, device=dev)
+        _lib.check(lib.envgs_select_acc(H, W, float(acc_threshold), p(a), p(keep), _stream(dev)), "envgs_select_acc")
+        mask = keep.view(torch.bool).view(H, W)
+    P = H * W
+    pos = torch.empty(max(P, 1), dtype=torch.int32, device=dev)
+    nk = torch.empty(1, dtype=torch.int32, device=dev)
+    tb = lib.envgs_compact_temp_bytes(P)
+    temp = torch.empty(max(tb, 1), dtype=torch.uint8, device=dev)
+    _lib.check(lib.envgs_compact_scan(P, p(keep), p(pos), p(nk), p(temp), tb, _stream(dev)), "envgs_compact_scan")
+    return PixelSelection(mask, int(nk.item()) & 0xFFFFFFFF, keep, pos)
+
+
+def _check_selection(sel, H, W, dev):
+    if (sel.H, sel.W) != (H, W) or sel.keep.device != dev:
+        raise RuntimeError("pixel selection is for a %dx%d image on %s, the call is %dx%d on %s" % (sel.H, sel.W, sel.keep.device, H, W, dev))
+
+
+class _ReflectFiltered(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, allmap, ray_o, ray_d, viewmatrix, depth_ratio, sel):
+        ctx.set_materialize_grads(False)          # outputs the loss does not use arrive as None (= NULL upstream pointer), not as buffers of zeros
+        lib = _lib.load()
+        if allmap.device.type != "cuda":
+            raise RuntimeError("envgs_amd.fused needs tensors on the GPU; there is no CPU path")
+        allmap, ray_o, ray_d, viewmatrix = _f32c(allmap), _f32c(ray_o), _f32c(ray_d), _f32c(viewmatrix)
+        _, H, W = allmap.shape
+        _check_selection(sel, H, W, allmap.device)
+        S = sel.count
+        f32 = dict(dtype=torch.float32, device=allmap.device)
+        nw = torch.empty(3, H, W, **f32); dep = torch.empty(1, H, W, **f32)
+        ref_o = torch.empty(1, S, 3, **f32); ref_d = torch.empty(1, S, 3, **f32)
+        p = _lib.ptr
+        _lib.check(lib.envgs_reflect_filtered_forward(H, W, float(depth_ratio), S, p(allmap), p(ray_o), p(ray_d), p(viewmatrix), p(sel.keep),
+                                                      p(sel.positions), p(nw), p(dep), p(ref_o), p(ref_d), _stream(allmap.device)),
+                   "envgs_reflect_filtered_forward")
+        ctx.save_for_backward(allmap, ray_o, ray_d, viewmatrix, sel.keep, sel.positions)
+        ctx.ratio, ctx.count = float(depth_ratio), S
+        ctx.need = (ctx.needs_input_grad[1], ctx.needs_input_grad[2])
+        return nw, dep, ref_o, ref_d
+
+    @staticmethod
+    def backward(ctx, g_nw, g_dep, g_ro, g_rd):
+        lib = _lib.load()
+        allmap, ray_o, ray_d, viewmatrix, keep, pos = ctx.saved_tensors
+        _, H, W = allmap.shape
+        c = lambda g: None if (g is None or g.numel() == 0) else _f32c(g)
+        g_nw, g_dep, g_ro, g_rd = c(g_nw), c(g_dep), c(g_ro), c(g_rd)
+        dall = torch.empty_like(allmap)
+        dro = torch.empty_like(ray_o) if ctx.need[0] else None
+        drd = torch.empty_like(ray_d) if ctx.need[1] else None
+        p = _lib.ptr
+        _lib.check(lib.envgs_reflect_filtered_backward(H, W, ctx.ratio, ctx.count, p(allmap), p(ray_o), p(ray_d), p(viewmatrix), p(keep), p(pos),
+                                                       p(g_nw), p(g_dep), p(g_ro), p(g_rd), p(dall), p(dro), p(drd), _stream(allmap.device)),
+                   "envgs_reflect_filtered_backward")
+        return dall, dro, drd, None, None, None
+
+
+def reflect_filtered(allmap, ray_o, ray_d, viewmatrix, sel, depth_ratio=0.0):
+    """reflect() for a filtered pass: normal_world (3,H,W) and depth (1,H,W) for every pixel, ref_o / ref_d (1,S,3) for the S pixels of `sel`
+    (select_pixels) in x[mask] order -- envgs_sampler.py:420-455 without the dense ray tensors, the two boolean-mask gathers and their scatter-add
+    backward: one launch each way."""
+    return _ReflectFiltered.apply(allmap, ray_o, ray_d, viewmatrix, depth_ratio, sel)
+
+
+class _BlendFiltered(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, img, rgb_env, sel):
+        lib = _lib.load()
+        if img.device.type != "cuda":
+            raise RuntimeError("envgs_amd.fused needs tensors on the GPU; there is no CPU path")
+        img, rgb_env = _f32c(img), _f32c(rgb_env)
+        C, H, W = img.shape
+        _check_selection(sel, H, W, img.device)
+        if rgb_env.shape not in ((1, sel.count, 3), (sel.count, 3)):
+            raise RuntimeError("blend_filtered: rgb_env must be (1,%d,3) or (%d,3), got %s" % (sel.count, sel.count, tuple(rgb_env.shape)))
+        rgb = torch.empty(H, W, 3, dtype=torch.float32, device=img.device); ref_rgb = torch.empty_like(rgb)
+        p = _lib.ptr
+        _lib.check(lib.envgs_blend_filtered_forward(H, W, C, sel.count, p(img), p(rgb_env), p(sel.keep), p(sel.positions), p(rgb), p(ref_rgb),
+                                                    _stream(img.device)), "envgs_blend_filtered_forward")
+        ctx.save_for_backward(img, rgb_env, sel.keep, sel.positions)
+        ctx.count = sel.count
+        ctx.mark_non_differentiable(ref_rgb)
+        return rgb, ref_rgb
+
+    @staticmethod
+    def backward(ctx, g, _g_ref):
+        lib = _lib.load()
+        img, rgb_env, keep, pos = ctx.saved_tensors
+        C, H, W = img.shape
+        g = _f32c(g)
+        dimg = torch.empty_like(img)
+        denv = torch.empty_like(rgb_env) if ctx.needs_input_grad[1] else None
+        p = _lib.ptr
+        _lib.check(lib.envgs_blend_filtered_backward(H, W, C, ctx.count, p(img), p(rgb_env), p(keep), p(pos), p(g), p(dimg), p(denv),
+                                                     _stream(img.device)), "envgs_blend_filtered_backward")
+        return dimg, denv, None
+
+
+def blend_filtered(img, rgb_env, sel):
+    """blend() for a filtered pass (envgs_sampler.py:465-476): rgb (H,W,3) = the blend at the pixels of `sel`, img[:3] elsewhere; ref_rgb (H,W,3)
+    = rgb_env * s * 2 scattered to the kept pixels, zero elsewhere (a visualisation output: not differentiable).  rgb_env: the traced colour
+    (1,S,3) or (S,3).  One launch each way instead of the masked assignment, the zero image + scatter and their scatter-add backward."""
+    return _BlendFiltered.apply(img, rgb_env, sel)
 
 
 class _BounceRays(torch.autograd.Function):

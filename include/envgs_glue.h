@@ -49,6 +49,27 @@ ENVGS_API int envgs_reflect_backward(int32_t H, int32_t W, float depth_ratio, co
                                      void *stream);
 
 /*
+ * FILTERED reflection (easyvolcap/models/samplers/envgs_sampler.py:433-455 and :461-476; configs/models/envgs_synth.yaml sets
+ * acc_filtering_start_iter): late in training only the pixels of a mask are traced.  keep (H*W) uint8 is the mask, positions (H*W) uint32 the
+ * exclusive prefix sum of it (envgs_compact_scan, include/envgs_densify.h, which also yields n_kept): kept pixel p owns row positions[p] of every
+ * COMPACT (n_kept,3) tensor, its rank among the kept pixels in row-major order -- the order of torch's x[mask].  One thread per pixel, no atomics.
+ *
+ * envgs_select_acc: keep[p] = allmap[1][p] > threshold, the acc filter (:443, strict).  Any other mask is the caller's own uint8 buffer.
+ * envgs_reflect_filtered_*: envgs_reflect_* with ref_o / ref_d (and their gradients dref_o / dref_d) as compact (n_kept,3) rows.  normal_world,
+ *   depth and dallmap are written for every pixel (a pixel that is not kept receives the dnormal_world / ddepth terms only); dray_o / dray_d
+ *   (H,W,3), optional, are zero at pixels that are not kept.  dnormal_world, ddepth, dref_o, dref_d may each be NULL.  n_kept = 0: ref_o / ref_d
+ *   may be NULL.
+ */
+ENVGS_API int envgs_select_acc(int32_t H, int32_t W, float threshold, const float *allmap, uint8_t *keep, void *stream);
+ENVGS_API int envgs_reflect_filtered_forward(int32_t H, int32_t W, float depth_ratio, int32_t n_kept, const float *allmap, const float *ray_o,
+                                             const float *ray_d, const float *viewmatrix, const uint8_t *keep, const uint32_t *positions,
+                                             float *normal_world, float *depth, float *ref_o, float *ref_d, void *stream);
+ENVGS_API int envgs_reflect_filtered_backward(int32_t H, int32_t W, float depth_ratio, int32_t n_kept, const float *allmap, const float *ray_o,
+                                              const float *ray_d, const float *viewmatrix, const uint8_t *keep, const uint32_t *positions,
+                                              const float *dnormal_world, const float *ddepth, const float *dref_o, const float *dref_d,
+                                              float *dallmap, float *dray_o, float *dray_d, void *stream);
+
+/*
  * The regulariser maps of render()'s tail (gaussian2d_utils.py:1125-1142): surf_depth (1,H,W) = expected depth (allmap[0] / allmap[1],
  * nan -> 0) mixed with the median depth (allmap[5]) by depth_ratio, and surf_normal (3,H,W) = dpt2norm(surf_depth) * alpha.detach()
  * (dpt2xyz / dpt2norm, :1158-1206: back-projection through the integer pixel grid with fx = W / (2 tan(FoVx/2)), central differences on
@@ -80,6 +101,19 @@ ENVGS_API int envgs_surfel_quads(int32_t P, const float *means3D, const float *s
 ENVGS_API int envgs_blend_forward(int32_t H, int32_t W, int32_t channels, const float *img, const float *rgb_env, float *rgb, void *stream);
 ENVGS_API int envgs_blend_backward(int32_t H, int32_t W, int32_t channels, const float *img, const float *rgb_env, const float *drgb,
                                    float *dimg, float *drgb_env, void *stream);
+
+/*
+ * The filtered blend (envgs_sampler.py:465-476; keep / positions / n_kept as for envgs_reflect_filtered_*): rgb_env (n_kept,3) is the traced
+ * colour of the kept pixels.  rgb (H,W,3) = (1 - s) img[:3] + s rgb_env[positions[p]] at kept pixels and img[:3], copied bit for bit, elsewhere;
+ * ref_rgb (H,W,3), optional, the visualisation image = rgb_env[positions[p]] * s * 2 at kept pixels and 0 elsewhere.  The backward writes dimg
+ * (C,H,W) for every pixel -- kept: (1 - s) g in the colour channels, sum g (env - rgb) in the specular channel(s); not kept: g and 0; roughness
+ * channel 0 -- and drgb_env (n_kept,3) = s g at the owning pixel (may be NULL).
+ */
+ENVGS_API int envgs_blend_filtered_forward(int32_t H, int32_t W, int32_t channels, int32_t n_kept, const float *img, const float *rgb_env,
+                                           const uint8_t *keep, const uint32_t *positions, float *rgb, float *ref_rgb, void *stream);
+ENVGS_API int envgs_blend_filtered_backward(int32_t H, int32_t W, int32_t channels, int32_t n_kept, const float *img, const float *rgb_env,
+                                            const uint8_t *keep, const uint32_t *positions, const float *drgb, float *dimg, float *drgb_env,
+                                            void *stream);
 
 /*
  * Bounce stages of a multi-depth trace (gaussian2d_sampler.py:413-426 / optix_utils.py:117-118; envgs_amd/tracing.py:_forward_bounces):
