@@ -9,30 +9,49 @@ from tests import reference_caller
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("deg,S,M", [(0, 1, 16), (2, 1, 16), (3, 3, 16), (2, 1, 9), (1, 3, 4)])
-def test_sh_colors_matches_torch(deg, S, M):
-    """M = 16: the four-lanes-per-surfel kernels; other coefficient counts: the one-lane-per-surfel ones."""
+def _sh_colors_cases():
+    """Every degree x M in {16, (D+1)^2} (plus M = 9 at degree 1) x P in {1, 3, 65, 5000}: partial quads, a partial wave and a partial workgroup of the
+    four-lanes-per-surfel kernels.  The P = 5000 cases that predate the ladder keep their ids."""
+    S_of = {(0, 16): 1, (2, 16): 1, (3, 16): 3, (2, 9): 1, (1, 4): 3, (0, 1): 3, (1, 16): 1, (1, 9): 1}
+    out = []
+    for (deg, M), S in S_of.items():
+        for P in (5000, 1, 3, 65):
+            out.append(pytest.param(deg, S, M, P, id="%d-%d-%d" % (deg, S, M) + ("" if P == 5000 else "-P%d" % P)))
+    return out
+
+
+@pytest.mark.parametrize("deg,S,M,P", _sh_colors_cases())
+def test_sh_colors_matches_torch(deg, S, M, P):
+    """M = 16: the four-lanes-per-surfel kernels; other coefficient counts: the one-lane-per-surfel ones.  The stored coefficients beyond the active degree
+    are large (tests/test_sh_degree_ladder.py:ladder_shs): they must reach no colour and receive exactly no gradient."""
     from envgs_amd import fused
+    from tests.test_sh_degree_ladder import ladder_shs
     dev = torch.device("cuda:0")
-    g = synth.base_gaussians(5000, seed=deg, device=dev)
-    g["shs"] = g["shs"][:, :M].contiguous()
+    nb = (deg + 1) ** 2
+    g = synth.base_gaussians(P, seed=deg)
+    g["shs"] = ladder_shs(g["shs"], deg)[:, :M].contiguous()       # (a sixth of the surfels: strongly negative DC -- the clamp and its zero gradient)
+    g = {k: v.to(dev) for k, v in g.items()}
     cam = synth.orbit_camera(1, device=dev)
-    spec = torch.rand(5000, S, device=dev)
-    g["shs"][:200, 0] = -3.0                            # strongly negative DC: exercises the clamp and its zero gradient
+    spec = torch.rand(P, S, device=dev)
     leaves = [g["means3D"].clone().requires_grad_(True), g["shs"].clone().requires_grad_(True), spec.clone().requires_grad_(True),
               g["roughness"].clone().requires_grad_(True)]
     out = fused.sh_colors(leaves[0], leaves[1], cam.camera_center, torch.tensor([deg], device=dev), leaves[2], leaves[3])
     ref_l = [t.detach().clone().requires_grad_(True) for t in leaves]
     d = ref_l[0] - cam.camera_center[None]; d = d / d.norm(dim=1, keepdim=True)
     ref = torch.cat([torch.clamp_min(envgs_step.eval_sh(deg, ref_l[1].transpose(1, 2), d) + 0.5, 0.0), ref_l[2], ref_l[3]], dim=-1)
-    assert out.shape == ref.shape == (5000, 3 + S + 1)
+    assert out.shape == ref.shape == (P, 3 + S + 1)
     torch.testing.assert_close(out, ref, rtol=1e-5, atol=1e-6)
     w = torch.randn_like(ref)
     (out * w).sum().backward(); (ref * w).sum().backward()
     for a, b in zip(leaves, ref_l):
         bg = b.grad if b.grad is not None else torch.zeros_like(b)          # degree 0 does not depend on the view direction
         torch.testing.assert_close(a.grad, bg, rtol=1e-4, atol=1e-6)
-    assert (out[:, :3] == 0).any()                        # the clamp (and its zero gradient) is exercised
+    assert leaves[1].grad.shape == (P, M, 3)
+    if M > nb:
+        assert float(leaves[1].grad[:, nb:].abs().max()) == 0.0
+    assert float(leaves[1].grad[:, :nb].abs().max()) > 0
+    if P >= 6:
+        assert (out[:P // 6, :3] == 0).any() and (out[P // 6:, :3] > 0).any()      # the clamp (and its zero gradient) is exercised
 
 
 @pytest.mark.parametrize("ratio", [0.0, 0.3])

@@ -4,7 +4,10 @@ order shared by the HIP kernels and the C oracle, so their tight agreement (1e-4
 order itself; the chain to ground truth ran HIP ~ C oracle (GPU) and C oracle ~ float64 autograd (CPU, tests/test_oracle_grad.py,
 tests/test_oracle_trace.py).  This file closes the triangle with the third side: dense float64 evaluation (every pixel x every surfel, no tiles, no
 lists, no atomics, true derivatives from autograd) against the HIP result.  Asserted: 5e-5 of the tensor's scale for values, 2e-4 for gradients
-(measured: values <= 6.7e-6, gradients <= 4.0e-5 -- the CPU leg C oracle ~ float64 asserts 2e-4 / 2e-3)."""
+(measured: values <= 6.7e-6, gradients <= 4.0e-5 -- the CPU leg C oracle ~ float64 asserts 2e-4 / 2e-3).
+
+The SH cases run at every degree 0..3 over 16 stored coefficients whose inactive part is large (tests/test_sh_degree_ladder.py:ladder_shs): float64 autograd
+never reads a coefficient beyond (D+1)^2 and gives it a zero gradient, so a leak in a kernel shows against ground truth, not only against the C oracle."""
 import numpy as np
 import pytest
 import torch
@@ -13,16 +16,25 @@ from envgs_amd import synth
 from oracle import eager, eager_trace
 from tests.util import small_scene, cam_args, rel_err, record
 from tests.test_oracle_trace import trace_scene
+from tests.test_sh_degree_ladder import ladder_shs
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("sh,C", [(True, 3), (False, 5), (False, 7)])
-def test_rasterizer_vs_float64_autograd(sh, C):
+def _sh_cases(lead, tail):
+    """The degree-3 case keeps its id; degrees 0..2 are added behind it."""
+    return [pytest.param(*lead, 3, id="-".join(str(x) for x in lead))] + [pytest.param(*lead, d, id="-".join(str(x) for x in lead) + "-D%d" % d) for d in (0, 1, 2)] + \
+           [pytest.param(*t, 0, id="-".join(str(x) for x in t)) for t in tail]
+
+
+@pytest.mark.parametrize("sh,C,deg", _sh_cases((True, 3), [(False, 5), (False, 7)]))
+def test_rasterizer_vs_float64_autograd(sh, C, deg):
     import importlib
     mod = importlib.import_module({3: "diff_surfel_rasterization_wet", 5: "diff_surfel_rasterization_wet_ch05", 7: "diff_surfel_rasterization_wet_ch07"}[C])
     dev = torch.device("cuda:0")
     g, cam = small_scene(P=300, H=48, W=64, seed=3, C=C, sh=sh)
+    if sh:
+        g["shs"] = ladder_shs(g["shs"], deg)
     ca = cam_args(cam)
     W, H = ca["W"], ca["H"]
     bg = torch.tensor([0.3, 0.6, 0.1])
@@ -34,11 +46,11 @@ def test_rasterizer_vs_float64_autograd(sh, C):
     names = ("means3D", "opacities", "scales", "rotations", "shs" if sh else "colors_precomp")
     L64 = {k: g[k].to(d).requires_grad_(True) for k in names}
     c64, r64, a64, w64 = eager.rasterize(L64["means3D"], L64["opacities"], ca["viewmatrix"].to(d), ca["projmatrix"].to(d), ca["campos"].to(d), W, H,
-                                         scales=L64["scales"], rotations=L64["rotations"], shs=L64.get("shs"), colors_precomp=L64.get("colors_precomp"), sh_degree=3, bg=bg)
+                                         scales=L64["scales"], rotations=L64["rotations"], shs=L64.get("shs"), colors_precomp=L64.get("colors_precomp"), sh_degree=deg, bg=bg)
     ((c64 * dcol.to(d)).sum() + (a64 * dall.to(d)).sum()).backward()
     # ---- HIP
     st = mod.GaussianRasterizationSettings(image_height=H, image_width=W, tanfovx=cam.tanfovx, tanfovy=cam.tanfovy, bg=bg.to(dev), scale_modifier=1.0,
-                                           viewmatrix=cam.world_view_transform.to(dev), projmatrix=cam.full_proj_transform.to(dev), sh_degree=torch.tensor([3], device=dev),
+                                           viewmatrix=cam.world_view_transform.to(dev), projmatrix=cam.full_proj_transform.to(dev), sh_degree=torch.tensor([deg], device=dev),
                                            campos=cam.camera_center.to(dev), prefiltered=False, debug=False)
     Lh = {k: g[k].to(dev).requires_grad_(True) for k in names}
     m2 = torch.zeros_like(Lh["means3D"], requires_grad=True)
@@ -47,7 +59,7 @@ def test_rasterizer_vs_float64_autograd(sh, C):
     ((color * dcol.to(dev)).sum() + (allmap * dall.to(dev)).sum()).backward()
     torch.cuda.synchronize()
     n = lambda t: t.detach().cpu().double().numpy()
-    test = "hip_vs_float64.raster_C%d" % C
+    test = "hip_vs_float64.raster_C%d" % C + ("_D%d" % deg if sh else "")
     np.testing.assert_array_equal(radii.cpu().numpy(), r64.numpy())
     errs = {"color": rel_err(n(color), n(c64)), "weight": rel_err(n(weight).reshape(-1), n(w64).reshape(-1))}
     for ch, nm in ((0, "depth"), (1, "alpha"), (2, "normal.x"), (3, "normal.y"), (4, "normal.z")):
@@ -65,14 +77,17 @@ def test_rasterizer_vs_float64_autograd(sh, C):
         e = rel_err(a.reshape(b.shape).numpy(), b.numpy())
         record(test, "d" + k, e, "(max|a-b|/max|b| against float64 autograd)")
         assert e < 2e-4, (k, e)
+    if sh and deg < 3:
+        assert float(Lh["shs"].grad[:, (deg + 1) ** 2:].abs().max()) == 0.0          # as in float64: exactly nothing beyond the active degree
 
 
-@pytest.mark.parametrize("use_sh,camera", [(True, True), (False, False)])
-def test_tracer_vs_float64_autograd(use_sh, camera):
+@pytest.mark.parametrize("use_sh,camera,deg", _sh_cases((True, True), [(False, False)]))
+def test_tracer_vs_float64_autograd(use_sh, camera, deg):
     import diff_surfel_tracing as tpkg
     dev = torch.device("cuda:0")
     g, ro, rd = trace_scene(P=200, R=400, seed=7, camera=camera)
-    deg = 3 if use_sh else 0
+    if use_sh:
+        g["shs"] = ladder_shs(g["shs"], deg)
     bg = torch.tensor([0.2, 0.5, 0.7])
     gen = torch.Generator().manual_seed(9)
     R = ro.shape[0]
@@ -96,7 +111,7 @@ def test_tracer_vs_float64_autograd(use_sh, camera):
     sum((outs[i].reshape(R, -1) * u.to(dev)).sum() for i, u in zip((0, 1, 2, 3, 5), ups)).backward()
     torch.cuda.synchronize()
     n = lambda x: x.detach().cpu().double().numpy()
-    test = "hip_vs_float64.tracer_%s" % ("sh" if use_sh else "rgb")
+    test = "hip_vs_float64.tracer_%s" % ("sh_D%d" % deg if use_sh else "rgb")
     for nm, a, b in (("rgb", outs[0], rgb), ("dpt", outs[1], dpt), ("acc", outs[2], acc), ("norm", outs[3], norm), ("aux", outs[5], aux), ("wet", outs[7], wet)):
         e = rel_err(n(a).reshape(n(b).shape), n(b))
         record(test, nm, e, "(against float64 eager)")
@@ -110,6 +125,8 @@ def test_tracer_vs_float64_autograd(use_sh, camera):
         e = rel_err(a.reshape(b.shape).numpy(), b.numpy())
         record(test, "d" + k, e, "(against float64 autograd)")
         assert e < 2e-4, (k, e)
+    if use_sh and deg < 3:
+        assert float(Lh["shs"].grad[:, (deg + 1) ** 2:].abs().max()) == 0.0
     for nm, a, b in (("dray_o", o.grad, o64.grad), ("dray_d", dd.grad, d64.grad)):
         e = rel_err(n(a), n(b))
         record(test, nm, e, "(against float64 autograd)")

@@ -146,7 +146,7 @@ def _parity(test, g, ro, rd, bg, deg, use_sh, sff, gr_scale=1.0, seed=9, which=G
     for k in which:
         if got[k] is None or want[k] is None: continue
         check_close(test, k, got[k].cpu().numpy(), want[k], excluded=nfr, cond=cond[k], unc=unc[k])
-    return dict(ref=ref, cnt=cnt, outs=outs, n_listed=n_listed, R=R, extra=extra, got=got, inputs=(ro, rd, gr))
+    return dict(ref=ref, rb=rb, cnt=cnt, outs=outs, n_listed=n_listed, R=R, extra=extra, got=got, inputs=(ro, rd, gr))
 
 
 @pytest.mark.parametrize("use_sh,camera,deg,P,R", [(True, True, 3, 150, 400), (False, False, 0, 150, 400), (True, False, 2, 2000, 1024),
