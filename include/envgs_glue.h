@@ -75,6 +75,9 @@ ENVGS_API int envgs_reflect_filtered_backward(int32_t H, int32_t W, float depth_
  * (dpt2xyz / dpt2norm, :1158-1206: back-projection through the integer pixel grid with fx = W / (2 tan(FoVx/2)), central differences on
  * interior pixels, zero border).  viewmatrix: world_view_transform (4,4) on the device; its upper 3x3 is the camera-to-world rotation
  * (the reference inverts the matrix; for a rigid camera that is the same).  The backward WRITES dallmap (7,H,W): channels 0, 1, 5; the rest zero.
+ * Non-finite depths: NaN, +inf AND -inf all become 0 (and pass no gradient).  The reference's nan_to_num(x, 0, 0) sends -inf to the lowest
+ * finite float instead; the rasterizer cannot produce one (depths are >= 0.2), so that value is not reproduced.  Either upstream pointer of
+ * the backward may be NULL (that output did not reach the loss).
  */
 ENVGS_API int envgs_surface_normal_forward(int32_t H, int32_t W, float depth_ratio, float fx, float fy, const float *allmap,
                                            const float *viewmatrix, float *surf_depth, float *surf_normal, void *stream);
