@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from envgs_amd import synth
+from tests.util import record
 
 pytestmark = pytest.mark.gpu
 
@@ -80,9 +81,14 @@ def test_rasterizer_on_a_side_stream_with_strided_views_double_parameters_and_de
     assert torch.equal(c, ref_c) and torch.equal(r, ref_r)
     # 5. scale_modifier: s * scales with modifier 1 == scales with modifier s
     s = 0.7
-    c1, r1, a1, _ = _fwd_bwd(mod, _settings(mod, cam, dev, scale_modifier=s), g)
-    c2, r2, a2, _ = _fwd_bwd(mod, _settings(mod, cam, dev), dict(g, scales=g["scales"] * s))
+    c1, r1, a1, g1 = _fwd_bwd(mod, _settings(mod, cam, dev, scale_modifier=s), g)
+    c2, r2, a2, g2 = _fwd_bwd(mod, _settings(mod, cam, dev), dict(g, scales=g["scales"] * s))
     assert _close(c1, c2, 2e-5) and int((r1 != r2).sum()) <= 2
+    # ... and the chain rule through the modifier: d/d(scales) of f(s * scales) is s times the gradient at the scaled surfels; nothing else moves
+    for k in ref_g:
+        record("boundary_variations.scale_modifier", "d" + k, float((g1[k] - (s if k == "scales" else 1.0) * g2[k]).abs().max()) / (float(g2[k].abs().max()) + 1e-30),
+               "(max|a-b|/max|b|: (scales, mod=%g) against (%g * scales, mod=1)%s)" % (s, s, ", dscales / %g" % s if k == "scales" else ""))
+        assert _close(g1[k], (s if k == "scales" else 1.0) * g2[k], 2e-5), k
 
 
 def test_rasterizer_random_covariances_do_not_crash():

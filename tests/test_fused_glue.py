@@ -1,12 +1,15 @@
 """GPU: the fused caller-side glue (envgs_amd.fused) against the torch expressions it replaces (the reference's own lines,
 re-derived in envgs_amd/envgs_step.py), forward and autograd backward.  Floating-point elementwise kernels: fp32 torch is the checker;
 the surface normals are also compared with a float64 twin of the same expressions (below), whose CPU pin is the one test here that needs no GPU."""
+import math
+
 import numpy as np
 import pytest
 import torch
 
 from envgs_amd import envgs_step, synth
 from tests import reference_caller
+from tests.util import look_at_camera
 
 
 
@@ -275,13 +278,32 @@ def _twin_surface_maps(cam, allmap, depth_ratio=0.0):
 
 # (H, W, fx): today's input; the training focal length on a crop, and twice it; then fx scaled with W as tests/util.py:small_scene does --
 # one interior pixel, one interior row / column, a row longer than a workgroup, a width that is the tile of other kernels
-SURF_SHAPES = [(44, 60, 83.3), (44, 60, 1111.1), (20, 33, 2222.2), (3, 3, None), (3, 70, None), (70, 3, None), (4, 257, None), (17, 16, None)]
+# Then fx != fy (with fx == fy everywhere, exchanging the two in the kernels' pixel direction would pass), one of them rolled about the viewing axis
+# as well: there the third entry is (fx, fy, roll), fx = None scaling with W as above.
+SURF_ANISO = (44, 60, (83.3, 50.0, 0.0))
+SURF_SHAPES = [(44, 60, 83.3), (44, 60, 1111.1), (20, 33, 2222.2), (3, 3, None), (3, 70, None), (70, 3, None), (4, 257, None), (17, 16, None),
+               pytest.param(*SURF_ANISO, id="44-60-fx83.3-fy50"), pytest.param(20, 33, (1111.1, 700.0, 0.5), id="20-33-fx1111.1-fy700-roll0.5"),
+               pytest.param(17, 16, (None, 0.6 * 1111.1 * 16 / 800.0, 0.0), id="17-16-scaled-fy0.6fx")]
+ORBIT_EYE_3 = (4.0 * math.cos(math.radians(20.0)) * math.cos(0.75 * math.pi), 4.0 * math.cos(math.radians(20.0)) * math.sin(0.75 * math.pi),
+               4.0 * math.sin(math.radians(20.0)))             # where synth.orbit_camera(3) stands
+
+
+def _surf_cam(H, W, focal, device="cpu"):
+    """View 3 of synth.orbit_camera through tests/util.py:look_at_camera (the same matrices when fy == fx and roll == 0)."""
+    fx, fy, roll = focal if isinstance(focal, tuple) else (focal, None, 0.0)
+    fx = fx if fx is not None else 1111.1 * W / 800.0
+    return look_at_camera(ORBIT_EYE_3, (0.0, 0.0, 0.0), H, W, fx, fy, roll=roll, device=device)
+
+
+def _focal_id(focal):
+    fx, fy, roll = focal if isinstance(focal, tuple) else (focal, None, 0.0)
+    return ("scaled" if fx is None else "%g" % fx) + ("" if fy is None else "-fy%g-roll%g" % (fy, roll))
 
 
 def _surf_input(H, W, fx, seed=5):
     """allmap (7,H,W) with a smooth depth under 1e-3 noise and, away from the border and on at most a tenth of the pixels: a block (8 x 8 where it fits)
     of empty pixels (allmap[0] = allmap[1] = 0: 0/0), pixels with allmap[0] > 0, allmap[1] = 0 (+inf) and pixels with a NaN median."""
-    cam = synth.orbit_camera(3, H=H, W=W, fx=fx if fx is not None else 1111.1 * W / 800.0)
+    cam = _surf_cam(H, W, fx)
     gen = torch.Generator().manual_seed(seed)
     yy, xx = torch.meshgrid(torch.arange(H).float(), torch.arange(W).float(), indexing="ij")
     allmap = torch.randn(7, H, W, generator=gen)
@@ -324,8 +346,9 @@ def _twin_run(cam, allmap, ratio, wd, wn, dtype):
 def test_surface_twin_is_reference_caller_in_float32():
     """The twin, in float32 on the CPU, is reference_caller.surface_maps bit for bit: values and gradients (NaN where torch's own backward of
     nan_to_num(0/0) gives NaN)."""
-    for H, W, fx in ((44, 60, 1111.1), (17, 16, None), (3, 3, None)):
+    for H, W, fx in ((44, 60, 1111.1), (17, 16, None), (3, 3, None), SURF_ANISO):
         cam, allmap, _, wd, wn = _surf_input(H, W, fx)
+        assert isinstance(fx, tuple) == (abs(float(cam.K[0, 0] - cam.K[1, 1])) > 1)
         for ratio in (0.0, 0.4, 1.0):
             a = allmap.clone().requires_grad_(True)
             sd, sn = reference_caller.surface_maps(cam, a, ratio)
@@ -347,7 +370,7 @@ def _surf_compare(name, H, W, fx, ratio, use_d=True, use_n=True):
     sd64, sn64, g64 = _twin_run(cam, allmap, ratio, wd, wn, torch.float64)
     sd32, sn32, g32 = _twin_run(cam, allmap, ratio, wd, wn, torch.float32)
     a1 = allmap.to(dev).detach().clone().requires_grad_(True)
-    camd = synth.orbit_camera(3, H=H, W=W, fx=fx if fx is not None else 1111.1 * W / 800.0, device=dev)
+    camd = _surf_cam(H, W, fx, device=dev)
     sd, sn = fused.surface_normal(a1, camd, ratio)
     loss = 0
     if use_d: loss = loss + (sd * wd.to(dev)).sum()
@@ -388,7 +411,7 @@ def _surf_compare(name, H, W, fx, ratio, use_d=True, use_n=True):
 @pytest.mark.parametrize("H,W,fx", SURF_SHAPES)
 def test_surface_normal_matches_float64_twin(H, W, fx, ratio):
     """Forward and dallmap[0, 1, 5] at every pixel that has a gradient, the neighbours of the holes (whose normals see a jump to depth 0) included."""
-    name = "test_surface_normal_matches_float64_twin[%d-%d-%s-%g]" % (H, W, "scaled" if fx is None else "%g" % fx, ratio)
+    name = "test_surface_normal_matches_float64_twin[%d-%d-%s-%g]" % (H, W, _focal_id(fx), ratio)
     _surf_compare(name, H, W, fx, ratio)
 
 

@@ -14,7 +14,7 @@ import torch
 
 from envgs_amd import synth
 from oracle import eager, eager_trace
-from tests.util import small_scene, cam_args, rel_err, record
+from tests.util import scene_for, small_fx, cam_args, rel_err, record
 from tests.test_oracle_trace import trace_scene
 from tests.test_sh_degree_ladder import ladder_shs
 
@@ -27,12 +27,26 @@ def _sh_cases(lead, tail):
            [pytest.param(*t, 0, id="-".join(str(x) for x in t)) for t in tail]
 
 
-@pytest.mark.parametrize("sh,C,deg", _sh_cases((True, 3), [(False, 5), (False, 7)]))
-def test_rasterizer_vs_float64_autograd(sh, C, deg):
+def _with_axes(cases, extra):
+    """The earlier cases keep their ids and get an empty `axes`; `extra` = (id, values, axes) are appended."""
+    return [pytest.param(*c.values, {}, id=c.id) for c in cases] + [pytest.param(*v, ax, id=i) for i, v, ax in extra]
+
+
+# cameras, scale modifiers and an image below one tile in each direction that the orbit camera at modifier 1 does not reach (tests/util.py: CAMERAS).
+# in_cloud at P=600, seed 3 and the others at P=300, seed 3: the float64 twin's radii equal the fp32 ones (tests/test_oracle_grad.py runs the same inputs)
+_RASTER_AXES = [("in_cloud", (True, 3, 3), dict(camera="in_cloud", P=600)), ("aniso", (True, 3, 3), dict(camera="aniso")),
+                ("mod0.5", (False, 5, 0), dict(scale_modifier=0.5)), ("mod1.7", (True, 3, 3), dict(scale_modifier=1.7)),
+                ("17x15", (True, 3, 2), dict(HW=(17, 15), fx=small_fx(15)))]
+
+
+@pytest.mark.parametrize("sh,C,deg,axes", _with_axes(_sh_cases((True, 3), [(False, 5), (False, 7)]), _RASTER_AXES))
+def test_rasterizer_vs_float64_autograd(sh, C, deg, axes, request):
     import importlib
     mod = importlib.import_module({3: "diff_surfel_rasterization_wet", 5: "diff_surfel_rasterization_wet_ch05", 7: "diff_surfel_rasterization_wet_ch07"}[C])
     dev = torch.device("cuda:0")
-    g, cam = small_scene(P=300, H=48, W=64, seed=3, C=C, sh=sh)
+    sm = axes.get("scale_modifier", 1.0)
+    H, W = axes.get("HW", (48, 64))
+    g, cam = scene_for(axes.get("camera", "orbit"), P=axes.get("P", 300), H=H, W=W, seed=3, C=C, sh=sh, fx=axes.get("fx"))
     if sh:
         g["shs"] = ladder_shs(g["shs"], deg)
     ca = cam_args(cam)
@@ -46,10 +60,11 @@ def test_rasterizer_vs_float64_autograd(sh, C, deg):
     names = ("means3D", "opacities", "scales", "rotations", "shs" if sh else "colors_precomp")
     L64 = {k: g[k].to(d).requires_grad_(True) for k in names}
     c64, r64, a64, w64 = eager.rasterize(L64["means3D"], L64["opacities"], ca["viewmatrix"].to(d), ca["projmatrix"].to(d), ca["campos"].to(d), W, H,
-                                         scales=L64["scales"], rotations=L64["rotations"], shs=L64.get("shs"), colors_precomp=L64.get("colors_precomp"), sh_degree=deg, bg=bg)
+                                         scales=L64["scales"], rotations=L64["rotations"], shs=L64.get("shs"), colors_precomp=L64.get("colors_precomp"), sh_degree=deg, bg=bg,
+                                         scale_modifier=sm)
     ((c64 * dcol.to(d)).sum() + (a64 * dall.to(d)).sum()).backward()
     # ---- HIP
-    st = mod.GaussianRasterizationSettings(image_height=H, image_width=W, tanfovx=cam.tanfovx, tanfovy=cam.tanfovy, bg=bg.to(dev), scale_modifier=1.0,
+    st = mod.GaussianRasterizationSettings(image_height=H, image_width=W, tanfovx=cam.tanfovx, tanfovy=cam.tanfovy, bg=bg.to(dev), scale_modifier=sm,
                                            viewmatrix=cam.world_view_transform.to(dev), projmatrix=cam.full_proj_transform.to(dev), sh_degree=torch.tensor([deg], device=dev),
                                            campos=cam.camera_center.to(dev), prefiltered=False, debug=False)
     Lh = {k: g[k].to(dev).requires_grad_(True) for k in names}
@@ -59,7 +74,7 @@ def test_rasterizer_vs_float64_autograd(sh, C, deg):
     ((color * dcol.to(dev)).sum() + (allmap * dall.to(dev)).sum()).backward()
     torch.cuda.synchronize()
     n = lambda t: t.detach().cpu().double().numpy()
-    test = "hip_vs_float64.raster_C%d" % C + ("_D%d" % deg if sh else "")
+    test = "hip_vs_float64.raster_C%d" % C + ("_D%d" % deg if sh else "") + ("." + request.node.callspec.id if axes else "")
     np.testing.assert_array_equal(radii.cpu().numpy(), r64.numpy())
     errs = {"color": rel_err(n(color), n(c64)), "weight": rel_err(n(weight).reshape(-1), n(w64).reshape(-1))}
     for ch, nm in ((0, "depth"), (1, "alpha"), (2, "normal.x"), (3, "normal.y"), (4, "normal.z")):
@@ -81,8 +96,11 @@ def test_rasterizer_vs_float64_autograd(sh, C, deg):
         assert float(Lh["shs"].grad[:, (deg + 1) ** 2:].abs().max()) == 0.0          # as in float64: exactly nothing beyond the active degree
 
 
-@pytest.mark.parametrize("use_sh,camera,deg", _sh_cases((True, True), [(False, False)]))
-def test_tracer_vs_float64_autograd(use_sh, camera, deg):
+@pytest.mark.parametrize("use_sh,camera,deg,axes", _with_axes(_sh_cases((True, True), [(False, False)]),
+                                                                [("True-True-mod1.7", (True, True, 3), dict(scale_modifier=1.7)),
+                                                                 ("False-False-mod1.7", (False, False, 0), dict(scale_modifier=1.7))]))
+def test_tracer_vs_float64_autograd(use_sh, camera, deg, axes):
+    sm = axes.get("scale_modifier", 1.0)
     import diff_surfel_tracing as tpkg
     dev = torch.device("cuda:0")
     g, ro, rd = trace_scene(P=200, R=400, seed=7, camera=camera)
@@ -97,21 +115,22 @@ def test_tracer_vs_float64_autograd(use_sh, camera, deg):
     L64 = {k: g[k].to(d).requires_grad_(True) for k in names}
     o64, d64 = ro.to(d).requires_grad_(True), rd.to(d).requires_grad_(True)
     rgb, dpt, acc, norm, aux, wet = eager_trace.trace(o64, d64, L64["means3D"], L64["scales"], L64["rotations"], L64["opacities"], shs=L64.get("shs"),
-                                                      colors_precomp=L64.get("colors_precomp"), others=L64["others"], sh_degree=deg, bg=bg.to(d), start_from_first=camera)
+                                                      colors_precomp=L64.get("colors_precomp"), others=L64["others"], sh_degree=deg, bg=bg.to(d), start_from_first=camera,
+                                                      scale_modifier=sm)
     sum((x.reshape(R, -1) * u.to(d)).sum() for x, u in zip((rgb, dpt, acc, norm, aux), ups)).backward()
-    ts = tpkg.SurfelTracingSettings(image_height=1, image_width=1, tanfovx=1.0, tanfovy=1.0, bg=bg.to(dev), scale_modifier=1.0, viewmatrix=torch.eye(4, device=dev),
+    ts = tpkg.SurfelTracingSettings(image_height=1, image_width=1, tanfovx=1.0, tanfovy=1.0, bg=bg.to(dev), scale_modifier=sm, viewmatrix=torch.eye(4, device=dev),
                                     projmatrix=torch.eye(4, device=dev), sh_degree=torch.tensor([deg], device=dev), campos=torch.zeros(3, device=dev), prefiltered=False,
                                     debug=False, max_trace_depth=0, specular_threshold=0.0)
     Lh = {k: g[k].to(dev).requires_grad_(True) for k in names}
     o, dd = ro.to(dev).requires_grad_(True), rd.to(dev).requires_grad_(True)
-    v, f = synth.get_disks(Lh["means3D"].detach(), Lh["scales"].detach(), Lh["rotations"].detach())
+    v, f = synth.get_disks(Lh["means3D"].detach(), Lh["scales"].detach() * sm, Lh["rotations"].detach())      # the 3-sigma quads of the MODIFIED surfels
     t = tpkg.SurfelTracer(); t.build_acceleration_structure(v, f, rebuild=True)
     outs = t(o, dd, v, means3D=Lh["means3D"], grads3D=None, shs=Lh.get("shs"), colors_precomp=Lh.get("colors_precomp"), others_precomp=Lh["others"], opacities=Lh["opacities"],
              scales=Lh["scales"], rotations=Lh["rotations"], cov3D_precomp=None, tracer_settings=ts, start_from_first=camera)
     sum((outs[i].reshape(R, -1) * u.to(dev)).sum() for i, u in zip((0, 1, 2, 3, 5), ups)).backward()
     torch.cuda.synchronize()
     n = lambda x: x.detach().cpu().double().numpy()
-    test = "hip_vs_float64.tracer_%s" % ("sh_D%d" % deg if use_sh else "rgb")
+    test = "hip_vs_float64.tracer_%s" % ("sh_D%d" % deg if use_sh else "rgb") + (".mod%g" % sm if axes else "")
     for nm, a, b in (("rgb", outs[0], rgb), ("dpt", outs[1], dpt), ("acc", outs[2], acc), ("norm", outs[3], norm), ("aux", outs[5], aux), ("wet", outs[7], wet)):
         e = rel_err(n(a).reshape(n(b).shape), n(b))
         record(test, nm, e, "(against float64 eager)")

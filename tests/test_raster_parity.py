@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.util import small_scene, cam_args, rel_err, check_close, record, record_fragile, FRAGILE_PX_MAX
+from tests.util import small_scene, scene_for, small_fx, SMALL_IMAGES, cam_args, rel_err, check_close, record, record_fragile, FRAGILE_PX_MAX
 
 pytestmark = pytest.mark.gpu
 
@@ -41,7 +41,19 @@ CASES = [
     dict(P=500, H=64, W=64, C=5, sh=False, deg=0, seed=2),         # ch05 with a 3-entry bg
     dict(P=500, H=48, W=100, C=7, sh=False, deg=0, seed=3),
     dict(P=3000, H=128, W=128, C=3, sh=True, deg=3, seed=4, scale_mul=6.0),   # long per-tile lists (> 256 per batch)
-]
+    # cameras and settings the orbit camera at scale_modifier 1 never reaches (tests/util.py: CAMERAS).  Seed 0 on the CPU oracle: no audited pixel at
+    # the three cameras, at modifier 0.5 and in the six small images; 1 of 5120 at modifier 1.7 (re-check with the oracle's audit if a seed changes)
+    dict(P=600, H=64, W=80, C=3, sh=True, deg=3, seed=0, camera="in_cloud"),       # 359 surfels culled at the near plane, radii up to ~2000 px: rectangles clamped on all sides
+    dict(P=1500, H=64, W=80, C=5, sh=False, deg=0, seed=0, camera="at_origin"),    # 1172 culled, radii up to ~6700 px, campos == 0
+    dict(P=600, H=70, W=90, C=3, sh=True, deg=1, seed=0, camera="aniso"),          # fx != fy, rolled
+    dict(P=600, H=64, W=80, C=5, sh=False, deg=0, seed=0, scale_modifier=0.5),
+    dict(P=600, H=64, W=80, C=3, sh=True, deg=3, seed=0, scale_modifier=1.7),
+] + [dict(P=300, H=h, W=w, C=3, sh=True, deg=2, seed=0, fx=small_fx(w)) for h, w in SMALL_IMAGES]      # below one tile, exactly one, ragged against both tile borders
+
+
+def _case_scene(case):
+    return scene_for(case.get("camera", "orbit"), P=case["P"], H=case["H"], W=case["W"], seed=case["seed"], C=case["C"], sh=case["sh"],
+                     scale_mul=case.get("scale_mul", 4.0), fx=case.get("fx"))
 
 
 
@@ -131,19 +143,21 @@ def test_forward_stages_vs_oracle(case, request):
     from envgs_amd import raster
     from oracle import raster as orc
     dev = torch.device("cuda:0")
-    g, cam = small_scene(P=case["P"], H=case["H"], W=case["W"], seed=case["seed"], C=case["C"], sh=case["sh"],
-                         scale_mul=case.get("scale_mul", 4.0))
+    g, cam = _case_scene(case)
     bg = torch.tensor([0.2, 0.5, 0.9])
     C = case["C"]
+    sm = case.get("scale_modifier", 1.0)
     mod = _mod_for(C)
-    st = _settings(mod, cam, bg, case["deg"], dev)
+    st = _settings(mod, cam, bg, case["deg"], dev, scale_modifier=sm)
     gd = {k: v.to(dev) for k, v in g.items()}
     outs, saved = raster.rasterize_forward(C, gd["means3D"], gd["shs"] if case["sh"] else None,
                                            None if case["sh"] else gd["colors_precomp"], gd["opacities"], gd["scales"],
                                            gd["rotations"], None, st, keep_binning=True)
     torch.cuda.synchronize()
-    ref = _oracle(g, cam, bg, case["deg"], C, case["sh"])
+    ref = _oracle(g, cam, bg, case["deg"], C, case["sh"], scale_modifier=sm)
     aud = orc.raster_audit(ref, want_contrib=True)
+    if case.get("camera") in ("in_cloud", "at_origin"):
+        assert int((ref["radii"] == 0).sum()) > 200 and int(ref["radii"].max()) > 1500      # the near-plane cull and the clamped rectangles ARE reached
     _compare_forward(request.node.name, outs, saved, ref, aud, case["sh"], check_sets=True)
 
 
@@ -171,14 +185,15 @@ def test_backward_vs_oracle(case, request):
     from oracle import raster as orc
     dev = torch.device("cuda:0")
     C = case["C"]
-    g, cam = small_scene(P=case["P"], H=case["H"], W=case["W"], seed=case["seed"], C=C, sh=case["sh"],
-                         scale_mul=case.get("scale_mul", 4.0))
+    g, cam = _case_scene(case)
     bg = torch.tensor([0.2, 0.5, 0.9])
+    sm = case.get("scale_modifier", 1.0)
     mod = _mod_for(C)
-    st = _settings(mod, cam, bg, case["deg"], dev)
+    st = _settings(mod, cam, bg, case["deg"], dev, scale_modifier=sm)
     H, W = case["H"], case["W"]
-    ref = _oracle(g, cam, bg, case["deg"], C, case["sh"])
+    ref = _oracle(g, cam, bg, case["deg"], C, case["sh"], scale_modifier=sm)
     aud = orc.raster_audit(ref)
+    record_fragile(request.node.name, "fragile_px", aud["fragile"], FRAGILE_PX_MAX)
     dcol, dall = _masked_upstream(C, H, W, case["seed"] + 100, aud["fragile"])
 
     leaves = {k: g[k].to(dev).requires_grad_(True) for k in ("means3D", "opacities", "scales", "rotations")}
@@ -242,32 +257,38 @@ def test_backward_sparse_distortion_gradient():
 
 
 def test_precomputed_transmat_path():
-    """cov3D_precomp (the python transMat of gaussian2d_utils.py:1050-1061) instead of scales/rotations."""
+    """cov3D_precomp (the python transMat of gaussian2d_utils.py:1050-1061) instead of scales/rotations.  The second run passes a transMat built with
+    scale_modifier 1.7 next to settings.scale_modifier = 1.7, as the reference caller does: the modifier is already in the matrix and the kernel
+    must not apply it a second time (the oracle gets the same pair)."""
     from envgs_amd import synth
     from oracle import raster as orc
     import diff_surfel_rasterization_wet as mod
     dev = torch.device("cuda:0")
     g, cam = small_scene(P=500, H=64, W=64, seed=9, C=3, sh=True)
     bg = torch.zeros(3)
-    tm = synth.transmat_python(cam, g["means3D"], g["scales"], g["rotations"])
-    st = _settings(mod, cam, bg, 2, dev)
-    tmd = tm.to(dev).requires_grad_(True)
-    m3 = g["means3D"].to(dev).requires_grad_(True)
-    shs = g["shs"].to(dev).requires_grad_(True)
-    op = g["opacities"].to(dev).requires_grad_(True)
-    means2D = torch.zeros_like(m3, requires_grad=True) + 0
-    color, radii, allmap, weight = mod.GaussianRasterizer(raster_settings=st)(
-        means3D=m3, means2D=means2D, shs=shs, colors_precomp=None, opacities=op, scales=None, rotations=None, cov3D_precomp=tmd)
-    ref = _oracle(g, cam, bg, 2, 3, True, precomp_T=tm)
-    aud = orc.raster_audit(ref)
-    dcol, dall = _masked_upstream(3, 64, 64, 5, aud["fragile"])
-    ((color * dcol.to(dev)).sum() + (allmap * dall.to(dev)).sum()).backward()
-    rb = orc.raster_backward(ref, dcol.numpy(), dall.numpy(), want_cond=True)
-    ok = ~aud["fragile"]
-    check_close("precomputed_transmat", "color", color.detach().cpu().numpy()[:, ok], ref["out_color"][:, ok], excluded=int((~ok).sum()))
-    check_close("precomputed_transmat", "dtransmat", tmd.grad.cpu().numpy(), rb["dtransmat_precomp"], cond=rb["cond"]["dtransmat_precomp"], unc=rb["unc"]["dtransmat_precomp"])
-    check_close("precomputed_transmat", "dmeans3D", m3.grad.cpu().numpy(), rb["dmeans3D"], cond=rb["cond"]["dmeans3D"], unc=rb["unc"]["dmeans3D"])          # SH view-direction term only
-    check_close("precomputed_transmat", "dshs", shs.grad.cpu().numpy(), rb["dshs"], cond=rb["cond"]["dshs"], unc=rb["unc"]["dshs"])
+    for sm, test in ((1.0, "precomputed_transmat"), (1.7, "precomputed_transmat.mod1.7")):
+        tm = synth.transmat_python(cam, g["means3D"], g["scales"], g["rotations"], scale_modifier=sm)
+        st = _settings(mod, cam, bg, 2, dev, scale_modifier=sm)
+        tmd = tm.to(dev).requires_grad_(True)
+        m3 = g["means3D"].to(dev).requires_grad_(True)
+        shs = g["shs"].to(dev).requires_grad_(True)
+        op = g["opacities"].to(dev).requires_grad_(True)
+        means2D = torch.zeros_like(m3, requires_grad=True) + 0
+        color, radii, allmap, weight = mod.GaussianRasterizer(raster_settings=st)(
+            means3D=m3, means2D=means2D, shs=shs, colors_precomp=None, opacities=op, scales=None, rotations=None, cov3D_precomp=tmd)
+        ref = _oracle(g, cam, bg, 2, 3, True, precomp_T=tm, scale_modifier=sm)
+        aud = orc.raster_audit(ref)
+        if sm != 1.0:
+            record_fragile(test, "fragile_px", aud["fragile"], FRAGILE_PX_MAX)
+            np.testing.assert_array_equal(radii.cpu().numpy(), ref["radii"])
+        dcol, dall = _masked_upstream(3, 64, 64, 5, aud["fragile"])
+        ((color * dcol.to(dev)).sum() + (allmap * dall.to(dev)).sum()).backward()
+        rb = orc.raster_backward(ref, dcol.numpy(), dall.numpy(), want_cond=True)
+        ok = ~aud["fragile"]
+        check_close(test, "color", color.detach().cpu().numpy()[:, ok], ref["out_color"][:, ok], excluded=int((~ok).sum()))
+        check_close(test, "dtransmat", tmd.grad.cpu().numpy(), rb["dtransmat_precomp"], cond=rb["cond"]["dtransmat_precomp"], unc=rb["unc"]["dtransmat_precomp"])
+        check_close(test, "dmeans3D", m3.grad.cpu().numpy(), rb["dmeans3D"], cond=rb["cond"]["dmeans3D"], unc=rb["unc"]["dmeans3D"])          # SH view-direction term only
+        check_close(test, "dshs", shs.grad.cpu().numpy(), rb["dshs"], cond=rb["cond"]["dshs"], unc=rb["unc"]["dshs"])
 
 
 def test_edge_cases():

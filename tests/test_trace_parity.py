@@ -6,25 +6,33 @@ Threshold / ordering flips are separated from arithmetic error instead of being 
 removed from the test input (a ray's result does not depend on the other rays), counted, and then on every remaining ray
   * the sorted per-ray hit-id list the GPU composited must equal the brute-force list bit for bit (index parity),
   * every output, the per-surfel weights and every gradient must be within 1e-4 elementwise."""
+import math
+
 import numpy as np
 import pytest
 import torch
 
 from envgs_amd import synth
-from tests.test_oracle_trace import trace_scene
+from tests.test_oracle_trace import trace_scene, FRAME_ROUND_TRIP
 from tests.util import check_close, record, record_fragile, FRAGILE_RAYS_MAX
 
 pytestmark = pytest.mark.gpu
 
 
-def _settings(mod, bg, deg, dev, depth=0, thr=0.0, H=1, W=1):
+def _settings(mod, bg, deg, dev, depth=0, thr=0.0, H=1, W=1, scale_modifier=1.0):
     I = torch.eye(4, device=dev)
-    return mod.SurfelTracingSettings(image_height=H, image_width=W, tanfovx=1.0, tanfovy=1.0, bg=bg.to(dev), scale_modifier=1.0,
+    return mod.SurfelTracingSettings(image_height=H, image_width=W, tanfovx=1.0, tanfovy=1.0, bg=bg.to(dev), scale_modifier=scale_modifier,
                                      viewmatrix=I, projmatrix=I, sh_degree=torch.tensor([deg], device=dev), campos=torch.zeros(3, device=dev),
                                      prefiltered=False, debug=False, max_trace_depth=depth, specular_threshold=thr)
 
 
-def _run_hip(g, ro, rd, bg, deg, use_sh, sff, grads=None, depth=0, thr=0.0, shape=None, others=True):
+def _run_hip(g, ro, rd, bg, deg, use_sh, sff, grads=None, depth=0, thr=0.0, shape=None, others=True, scale_modifier=1.0, quad_modifier=None):
+    """quad_modifier: what the scales are multiplied by for the BVH's 3-sigma quads (default: scale_modifier, so that the quads are those of the surfels
+    the kernel and the oracle evaluate).  The reference caller builds them from the unmodified scales (optix_utils.py:39-69 next to :110): with a modifier
+    below 1 they are larger than needed and every hit is still found -- that is a case of test_trace_forward_backward_vs_oracle.  The reverse, a modifier
+    ABOVE 1 over unmodified quads, is not asserted anywhere: the quads are then smaller than the modified surfels, so whatever part of a surfel's
+    3-sigma extent lies outside its quad is not found by the traversal and the image differs from the brute-force oracle's; the reference's extension
+    sources are not available to say that it does otherwise."""
     import diff_surfel_tracing as mod
     dev = torch.device("cuda:0")
     L = {k: g[k].to(dev).requires_grad_(True) for k in ("means3D", "scales", "rotations", "opacities")}
@@ -33,14 +41,14 @@ def _run_hip(g, ro, rd, bg, deg, use_sh, sff, grads=None, depth=0, thr=0.0, shap
     else: L["colors_precomp"] = g["colors_precomp"].to(dev).requires_grad_(True)
     o = ro.to(dev).requires_grad_(True); d = rd.to(dev).requires_grad_(True)
     oo, dd = (o, d) if shape is None else (o.reshape(shape + (3,)), d.reshape(shape + (3,)))
-    v, f = synth.get_disks(L["means3D"].detach(), L["scales"].detach(), L["rotations"].detach())
+    v, f = synth.get_disks(L["means3D"].detach(), L["scales"].detach() * (scale_modifier if quad_modifier is None else quad_modifier), L["rotations"].detach())
     tracer = mod.SurfelTracer()
     tracer.build_acceleration_structure(v.detach().clone(), f.detach().clone(), rebuild=True)
     g3 = torch.zeros_like(L["means3D"], requires_grad=True) + 0
     g3.retain_grad()
     outs = tracer(oo, dd, v, means3D=L["means3D"], grads3D=g3, shs=L.get("shs"), colors_precomp=L.get("colors_precomp"),
                   others_precomp=L.get("others"), opacities=L["opacities"], scales=L["scales"], rotations=L["rotations"],
-                  cov3D_precomp=None, tracer_settings=_settings(mod, bg, deg, dev, depth, thr), start_from_first=sff)
+                  cov3D_precomp=None, tracer_settings=_settings(mod, bg, deg, dev, depth, thr, scale_modifier=scale_modifier), start_from_first=sff)
     if grads is not None:
         rgb, dpt, acc, norm, dist, aux, mid, wet = outs
         R = ro.shape[0]
@@ -54,11 +62,11 @@ def _np(g, k):
     return g[k].numpy()
 
 
-def _drop_fragile(test, g, ro, rd, sff, others=True, max_frac=FRAGILE_RAYS_MAX, sh_degree=None):
+def _drop_fragile(test, g, ro, rd, sff, others=True, max_frac=FRAGILE_RAYS_MAX, sh_degree=None, scale_modifier=1.0):
     """The oracle's audit of the stage: returns the non-fragile rays and their brute-force sorted hit-id lists."""
     from oracle import trace as otr
     a = otr.trace_audit(ro.numpy(), rd.numpy(), _np(g, "means3D"), _np(g, "scales"), _np(g, "rotations"), _np(g, "opacities"),
-                        others=_np(g, "others") if others else None, start_from_first=sff,
+                        others=_np(g, "others") if others else None, start_from_first=sff, scale_modifier=scale_modifier,
                         shs=(g["shs"].float().numpy() if sh_degree is not None else None), sh_degree=(sh_degree or 0))
     keep = ~a["fragile"]
     record_fragile(test, "fragile_rays", a["fragile"], max_frac)
@@ -92,11 +100,11 @@ GRADS_ALL = ("dmeans3D", "grads3D", "dscales", "drots", "dopacities", "dothers",
 
 
 def _parity(test, g, ro, rd, bg, deg, use_sh, sff, gr_scale=1.0, seed=9, which=GRADS_ALL, others=True, hip_ctx=None, require_lists=True,
-            zero_geo_grads=False, after_hip=None):
+            zero_geo_grads=False, after_hip=None, scale_modifier=1.0, quad_modifier=None):
     """Audit -> drop fragile rays -> HIP forward + backward -> oracle forward + backward -> index parity + the 1e-4 contract."""
     from oracle import trace as otr
     from envgs_amd import tracing
-    ro, rd, ids_ref, nhit_ref, nfr = _drop_fragile(test, g, ro, rd, sff, others=others, sh_degree=(deg if use_sh else None))
+    ro, rd, ids_ref, nhit_ref, nfr = _drop_fragile(test, g, ro, rd, sff, others=others, sh_degree=(deg if use_sh else None), scale_modifier=scale_modifier)
     R = ro.shape[0]
     gen = torch.Generator().manual_seed(seed)
     gr = [torch.randn(R, 3, generator=gen) * gr_scale, torch.randn(R, generator=gen) * gr_scale, torch.randn(R, generator=gen) * gr_scale,
@@ -108,7 +116,7 @@ def _parity(test, g, ro, rd, bg, deg, use_sh, sff, gr_scale=1.0, seed=9, which=G
     try:
         if hip_ctx is not None: hip_ctx.__enter__()
         try:
-            outs, L, o, d, g3 = _run_hip(g, ro, rd, bg, deg, use_sh, sff, grads=gr, others=others)
+            outs, L, o, d, g3 = _run_hip(g, ro, rd, bg, deg, use_sh, sff, grads=gr, others=others, scale_modifier=scale_modifier, quad_modifier=quad_modifier)
             cnt = tracing.last_trace_counts()
             extra = after_hip() if after_hip is not None else None
             n_listed = _check_index_parity(test, ids_ref, nhit_ref, require_lists=require_lists)
@@ -120,7 +128,7 @@ def _parity(test, g, ro, rd, bg, deg, use_sh, sff, gr_scale=1.0, seed=9, which=G
     rgb, dpt, acc, norm, dist, aux, mid, wet = [x.detach().cpu().numpy() for x in outs]
     ckw = dict(shs=_np(g, "shs"), sh_degree=deg) if use_sh else dict(colors_precomp=_np(g, "colors_precomp"))
     ref = otr.trace_forward(ro.numpy(), rd.numpy(), _np(g, "means3D"), _np(g, "scales"), _np(g, "rotations"), _np(g, "opacities"),
-                            others=_np(g, "others") if others else None, bg=bg.numpy(), start_from_first=sff, **ckw)
+                            others=_np(g, "others") if others else None, bg=bg.numpy(), start_from_first=sff, scale_modifier=scale_modifier, **ckw)
     np.testing.assert_array_equal(ref["nhits"], nhit_ref)
     for a, b, nm in ((rgb, ref["rgb"], "rgb"), (dpt[:, 0], ref["dpt"], "dpt"), (acc[:, 0], ref["acc"], "acc"), (norm, ref["norm"], "norm"),
                      (aux, ref["aux"], "aux"), (wet[:, 0], ref["wet"], "wet")):
@@ -149,13 +157,21 @@ def _parity(test, g, ro, rd, bg, deg, use_sh, sff, gr_scale=1.0, seed=9, which=G
     return dict(ref=ref, rb=rb, cnt=cnt, outs=outs, n_listed=n_listed, R=R, extra=extra, got=got, inputs=(ro, rd, gr))
 
 
-@pytest.mark.parametrize("use_sh,camera,deg,P,R", [(True, True, 3, 150, 400), (False, False, 0, 150, 400), (True, False, 2, 2000, 1024),
-                                                   (True, False, 1, 1, 64), (False, True, 0, 40, 130)])
-def test_trace_forward_backward_vs_oracle(use_sh, camera, deg, P, R, request):
+_FB_CASES = [(True, True, 3, 150, 400), (False, False, 0, 150, 400), (True, False, 2, 2000, 1024), (True, False, 1, 1, 64), (False, True, 0, 40, 130)]
+# scale_modifier != 1 (never run before: surfel_record, hit_geometry_grad's gw[12], gw[13] *= mod): (case, modifier, quad modifier).  The quads are
+# those of the modified surfels, except in the last case, which builds them from the unmodified scales as the reference caller does (_run_hip).
+# (True, False, 2, 2000, 1024) at 1.7: 53 hits per ray on average, 79 at most -- the longest lists of this test.  Fragile rays on the CPU: <= 0.5 %.
+_FB_MOD_CASES = [(c, m, None) for c in _FB_CASES[:2] for m in (0.5, 1.7)] + [(_FB_CASES[2], 1.7, None), (_FB_CASES[0], 0.5, 1.0)]
+
+
+@pytest.mark.parametrize("use_sh,camera,deg,P,R,scale_modifier,quad_modifier",
+                         [pytest.param(*c, 1.0, None, id="-".join(str(x) for x in c)) for c in _FB_CASES] +           # (the ids from before the modifier)
+                         [pytest.param(*c, m, q, id="-".join(str(x) for x in c) + "-mod%g" % m + ("-unmodified_quads" if q is not None else "")) for c, m, q in _FB_MOD_CASES])
+def test_trace_forward_backward_vs_oracle(use_sh, camera, deg, P, R, scale_modifier, quad_modifier, request):
     g, ro, rd = trace_scene(P=P, R=R, seed=7, camera=camera)
     if P > 500:
         g["scales"] = g["scales"] * 0.35                       # many small surfels: deep tree, > K hits per ray for some
-    res = _parity(request.node.name, g, ro, rd, torch.tensor([0.3, 0.1, 0.7]), deg, use_sh, camera)
+    res = _parity(request.node.name, g, ro, rd, torch.tensor([0.3, 0.1, 0.7]), deg, use_sh, camera, scale_modifier=scale_modifier, quad_modifier=quad_modifier)
     if P > 1: assert res["ref"]["nhits"].mean() > 1
 
 
@@ -359,40 +375,120 @@ def test_trace_kbuffer_in_kernel_bounces_forward():
     check_close("kbuffer_in_kernel_bounces", "mid", outs[6].cpu().numpy()[same], ref["mid"][same], excluded=int((~same).sum()))
 
 
-def test_trace_cov3D_precomp_matches_scales_rotations():
+@pytest.mark.parametrize("scale_modifier", [1.0, 1.7])
+def test_trace_cov3D_precomp_matches_scales_rotations(scale_modifier):
     """pipe.compute_cov3D_python (optix_utils.py:143-154): the tracer accepts the screen-space transMat, recovers the world-space frame from
-    it and traces the same image; the gradient reaches the transMat (and, through the caller's own torch expressions, its parameters)."""
+    it and traces the same image; the gradient reaches the transMat (and, through the caller's own torch expressions, its parameters).
+    With scale_modifier m the caller's transMat already holds m * scales and settings.scale_modifier is m as well: frame_from_transmat's division
+    and the kernel's multiplication must cancel.  That is asserted on the recovered frame itself (tests/test_oracle_trace.py:
+    test_frame_from_transmat_round_trip, and here on the device) and on the image and the gradients of the frame path over m * scales.
+
+    At 1.7 a ray has 42 hits instead of 17, and on the MI355X one ray of 512 differed by 2e-3 of its colour: the hit distance t = n.(mu - o) / n.d comes
+    from the RECOVERED normal, whose fp32 rounding (asserted: quaternion within FRAME_ROUND_TRIP) exchanged two hits of that ray that are equally far away.
+    No model of that noise removes rays here.  At a modifier other than 1 the rays the oracle's audit marks are dropped as everywhere else; of the others,
+    the two calls' composited hit lists are compared ray by ray.  Rays with identical lists meet the bounds this test always had (the upstream gradient
+    is zero on the others, in both calls).  A ray whose lists differ must differ ONLY by what the rounding of the frame can decide, as in
+    test_fragile_rays_differ_from_the_oracle_by_threshold_hits_only: a symmetric difference of at most 2 entries (threshold hits), nothing listed twice,
+    and every pair of common surfels that the two lists order differently must be equally far away within the distance error of a normal that is off
+    by 4 FRAME_ROUND_TRIP (|dn| <= 4 |dq| for a unit quaternion):  |t_i - t_j| <= dt_i + dt_j,  dt = 4 FRAME_ROUND_TRIP (|mu - o| + |t| |d|) / |n.d|, in
+    float64.  A ray that differs by threshold hits alone (same order) also has a colour within exp(-4.5) * cmax of the frame path's: the largest blend
+    weight of a hit at a threshold (alpha = 1/255; |u| or |v| = 3: alpha <= 0.99 exp(-4.5) = 0.011; a terminating hit: T < 1e-4) times the largest colour
+    an SH degree-2 surfel of the scene can have.  Such rays are counted and bounded by FRAGILE_RAYS_MAX.  At 1.0 the test is what it always was: every
+    ray, no lists."""
+    from envgs_amd import tracing
+    m = scale_modifier
+    test = "cov3D_precomp" + ("" if m == 1.0 else ".mod%g" % m)
     import diff_surfel_tracing as mod
     dev = torch.device("cuda:0")
     g, ro, rd = trace_scene(P=200, R=512, seed=5, camera=False)
+    if m != 1.0:
+        gn = dict(g, rotations=g["rotations"] / g["rotations"].norm(dim=-1, keepdim=True))
+        ro, rd, _, _, _ = _drop_fragile(test, gn, ro, rd, False, others=False, sh_degree=2, scale_modifier=m)
     cam = synth.orbit_camera(1, H=64, W=80, fx=100.0)
     bg = torch.tensor([0.1, 0.2, 0.3])
-    st = mod.SurfelTracingSettings(image_height=64, image_width=80, tanfovx=cam.tanfovx, tanfovy=cam.tanfovy, bg=bg.to(dev), scale_modifier=1.0,
+    st = mod.SurfelTracingSettings(image_height=64, image_width=80, tanfovx=cam.tanfovx, tanfovy=cam.tanfovy, bg=bg.to(dev), scale_modifier=m,
                                    viewmatrix=cam.world_view_transform.to(dev), projmatrix=cam.full_proj_transform.to(dev), sh_degree=torch.tensor([2], device=dev),
                                    campos=cam.camera_center.to(dev), prefiltered=False, debug=False, max_trace_depth=0, specular_threshold=0.0)
+    run, lists = {}, {}
+    old_keep = tracing.KEEP_LISTS["on"]
+    tracing.KEEP_LISTS["on"] = m != 1.0
+    try:
+        for mode in ("frame", "precomp"):
+            L = {k: g[k].to(dev).requires_grad_(True) for k in ("means3D", "scales", "rotations", "opacities", "shs")}
+            rn = L["rotations"] / L["rotations"].norm(dim=-1, keepdim=True)                     # what get_rotation does
+            v, f = synth.get_disks(L["means3D"].detach(), L["scales"].detach() * m, rn.detach())
+            tracer = mod.SurfelTracer(); tracer.build_acceleration_structure(v, f, rebuild=True)
+            kw = dict(means3D=L["means3D"], grads3D=None, shs=L["shs"], colors_precomp=None, others_precomp=None, opacities=L["opacities"],
+                      tracer_settings=st, start_from_first=False)
+            if mode == "frame":
+                outs = tracer(ro.to(dev), rd.to(dev), v, scales=L["scales"], rotations=rn, cov3D_precomp=None, **kw)
+            else:
+                class _C: pass
+                c = _C(); c.__dict__.update(cam.__dict__)
+                c.world_view_transform = cam.world_view_transform.to(dev); c.full_proj_transform = cam.full_proj_transform.to(dev)
+                tm = synth.transmat_python(c, L["means3D"], L["scales"], rn, scale_modifier=m)  # the caller's torch expression
+                s_rec, q_rec = tracing.frame_from_transmat(tm.detach(), st)                     # what the tracer hands to the kernel
+                e_s = float(((s_rec - L["scales"].detach()).abs() / L["scales"].detach()).max())
+                e_q = float((q_rec * torch.sign((q_rec * rn.detach()).sum(-1, keepdim=True)) - rn.detach()).abs().max())
+                record(test, "recovered_frame.scales", e_s, "(relative; bound %.0e)" % FRAME_ROUND_TRIP)
+                record(test, "recovered_frame.quaternion", e_q, "(absolute, up to sign; bound %.0e)" % FRAME_ROUND_TRIP)
+                assert e_s <= FRAME_ROUND_TRIP and e_q <= FRAME_ROUND_TRIP, (e_s, e_q)
+                outs = tracer(ro.to(dev), rd.to(dev), v, scales=None, rotations=None, cov3D_precomp=tm, **kw)
+            torch.cuda.synchronize()
+            if m != 1.0:
+                ids, tb, n_used, hit_cnt = [x.cpu().numpy() for x in tracing.last_hit_lists()]
+                assert np.all(hit_cnt <= ids.shape[1]), "a ray was not served by the list path"
+                lists[mode] = [[int(x) for x in ids[r, :n_used[r]]] for r in range(ids.shape[0])]
+            run[mode] = (outs, L)
+    finally:
+        tracing.KEEP_LISTS["on"] = old_keep
+    R = ro.shape[0]
+    same = np.ones(R, bool)
+    if m != 1.0:
+        same = np.array([lists["frame"][r] == lists["precomp"][r] for r in range(R)])
+        record_fragile(test, "rays_with_differing_hit_lists", ~same, FRAGILE_RAYS_MAX)
+        rgb_f, rgb_p = run["frame"][0][0].detach().cpu().numpy(), run["precomp"][0][0].detach().cpu().numpy()
+        cmax = 0.5 + 1.1 * float(g["shs"][:, :9].abs().sum(dim=(1, 2)).max())                   # |SH basis of degree <= 2| <= 1.1 on unit directions
+        worst, swaps = 0, 0
+        d64 = torch.float64
+        nrm = synth.build_rotation(g["rotations"].to(d64))[:, :, 2]
+        for r in np.nonzero(~same)[0]:
+            a_, b_ = lists["frame"][r], lists["precomp"][r]
+            sd = set(a_) ^ set(b_)
+            worst = max(worst, len(sd))
+            assert len(a_) == len(set(a_)) and len(b_) == len(set(b_)), "ray %d: a surfel is listed twice" % r
+            ca, cb = [x for x in a_ if x not in sd], [x for x in b_ if x not in sd]
+            if ca == cb:
+                assert float(np.abs(rgb_p[r] - rgb_f[r]).max()) <= math.exp(-4.5) * cmax, (r, rgb_p[r], rgb_f[r])
+                continue
+            o_, d_ = ro[r].to(d64), rd[r].to(d64)
+            idx = torch.tensor(ca)
+            nd = nrm[idx] @ d_
+            t = ((g["means3D"][idx].to(d64) - o_) * nrm[idx]).sum(-1) / nd
+            dt = 4 * FRAME_ROUND_TRIP * ((g["means3D"][idx].to(d64) - o_).norm(dim=-1) + t.abs() * d_.norm()) / nd.abs()
+            pos_b = {x: k for k, x in enumerate(cb)}
+            for i in range(len(ca)):
+                for j in range(i + 1, len(ca)):
+                    if pos_b[ca[i]] > pos_b[ca[j]]:
+                        swaps += 1
+                        assert abs(float(t[i] - t[j])) <= float(dt[i] + dt[j]), "ray %d: surfels %d and %d change order at distances %.9g, %.9g (allowed %.3g)" % (
+                            r, ca[i], ca[j], float(t[i]), float(t[j]), float(dt[i] + dt[j]))
+        record(test, "differing_lists_exchanged_pairs", float(swaps), "(pairs of equally distant hits in the other order; each within its distance error)")
+        assert worst <= 2, "a ray's two hit lists differ by %d entries" % worst
+        record(test, "differing_lists_max_symmetric_difference", float(worst), "(%d rays; bound 2 entries)" % int((~same).sum()))
+        if (~same).any():
+            record(test, "differing_lists_rgb", float(np.abs(rgb_p[~same] - rgb_f[~same]).max()), "(absolute; bound exp(-4.5) * %.2f = %.3f)" % (cmax, math.exp(-4.5) * cmax))
     res = {}
+    up = torch.linspace(0.5, 1.5, 3, device=dev)[None] * torch.from_numpy(same).to(dev, torch.float32)[:, None]
     for mode in ("frame", "precomp"):
-        L = {k: g[k].to(dev).requires_grad_(True) for k in ("means3D", "scales", "rotations", "opacities", "shs")}
-        rn = L["rotations"] / L["rotations"].norm(dim=-1, keepdim=True)                     # what get_rotation does
-        v, f = synth.get_disks(L["means3D"].detach(), L["scales"].detach(), rn.detach())
-        tracer = mod.SurfelTracer(); tracer.build_acceleration_structure(v, f, rebuild=True)
-        kw = dict(means3D=L["means3D"], grads3D=None, shs=L["shs"], colors_precomp=None, others_precomp=None, opacities=L["opacities"],
-                  tracer_settings=st, start_from_first=False)
-        if mode == "frame":
-            outs = tracer(ro.to(dev), rd.to(dev), v, scales=L["scales"], rotations=rn, cov3D_precomp=None, **kw)
-        else:
-            class _C: pass
-            c = _C(); c.__dict__.update(cam.__dict__)
-            c.world_view_transform = cam.world_view_transform.to(dev); c.full_proj_transform = cam.full_proj_transform.to(dev)
-            tm = synth.transmat_python(c, L["means3D"], L["scales"], rn)                    # the caller's torch expression
-            outs = tracer(ro.to(dev), rd.to(dev), v, scales=None, rotations=None, cov3D_precomp=tm, **kw)
-        (outs[0] * torch.linspace(0.5, 1.5, 3, device=dev)).sum().backward()
+        outs, L = run[mode]
+        (outs[0] * up).sum().backward()
         torch.cuda.synchronize()
         res[mode] = (outs[0].detach().cpu().numpy(), {k: x.grad.cpu().numpy() for k, x in L.items()})
     assert np.abs(res["frame"][0] - bg.numpy()).max() > 0.05
-    check_close("cov3D_precomp", "rgb", res["precomp"][0], res["frame"][0], tol=2e-4)
+    check_close(test, "rgb", res["precomp"][0][same], res["frame"][0][same], tol=2e-4, excluded=int((~same).sum()))
     for k in ("scales", "rotations", "opacities", "shs"):
-        check_close("cov3D_precomp", "d" + k, res["precomp"][1][k], res["frame"][1][k], tol=2e-3)
+        check_close(test, "d" + k, res["precomp"][1][k], res["frame"][1][k], tol=2e-3, excluded=int((~same).sum()))
 
 
 def test_trace_edge_cases():

@@ -1,4 +1,5 @@
 """Shared helpers for the test-suite: small seeded scenes in the layout the reference call sites use."""
+import math
 import os
 
 import numpy as np
@@ -17,6 +18,55 @@ def small_scene(P=400, H=64, W=80, seed=0, view=1, C=3, sh=True, spread=1.0, sca
         gen = torch.Generator().manual_seed(seed + 7)
         g["colors_precomp"] = torch.rand(P, C, generator=gen)
     return g, cam
+
+
+def look_at_camera(eye, target, H, W, fx, fy=None, roll=0.0, n=2.0, f=6.0, device="cpu"):
+    """A pinhole camera at `eye` looking at `target` (up = +z, then rolled by `roll` radians about the viewing axis), with separate focal
+    lengths and the principal point at the image centre: K = [[fx,0,W/2],[0,fy,H/2],[0,0,1]], from which synth.make_camera derives FoVx / FoVy
+    the way the reference's prepare_gaussian_camera does (an off-centre principal point would not reach the kernels: the projection is built
+    from the two FoVs alone).  With roll = 0 and fy = fx this is synth.orbit_camera's frame for the same eye."""
+    eye = torch.as_tensor(eye, dtype=torch.float32)
+    fwd = torch.as_tensor(target, dtype=torch.float32) - eye
+    fwd = fwd / fwd.norm()                                  # camera +z
+    right = torch.linalg.cross(fwd, torch.tensor([0.0, 0.0, 1.0])); right = right / right.norm()
+    down = torch.linalg.cross(fwd, right)
+    c, s = math.cos(roll), math.sin(roll)
+    right, down = c * right + s * down, c * down - s * right
+    R = torch.stack([right, down, fwd], dim=0)              # rows = camera axes in world coords
+    T = -(R @ eye).reshape(3, 1)
+    fy = fx if fy is None else fy
+    K = torch.tensor([[fx, 0, W / 2.0], [0, fy, H / 2.0], [0, 0, 1.0]])
+    return synth.make_camera(K, R, T, H, W, n, f, device)
+
+
+# The cameras the orbit camera (radius 4, outside the cloud, up = +z, fx == fy) never is.  The first two stand INSIDE the base cloud (+-1.3), where
+# EnvGS's indoor captures put the camera: surfels at or behind the near plane are culled, and the surfels next
+# to the eye have radii of thousands of pixels, so their tile rectangles are clamped on all four sides.
+CAMERAS = {
+    "in_cloud": lambda H, W: look_at_camera((0.5, 0.1, 0.2), (0.0, 0.0, 0.0), H, W, 40.0),
+    "at_origin": lambda H, W: look_at_camera((0.0, 0.0, 0.0), (1.0, 0.3, 0.2), H, W, 40.0),                      # campos == 0
+    "aniso": lambda H, W: look_at_camera((3.0, 2.0, 1.5), (0.0, 0.0, 0.0), H, W, 1111.1 * W / 800.0, 0.6 * 1111.1 * W / 800.0, roll=0.5),
+}
+
+
+def scene_for(camera_kind, P=400, H=64, W=80, seed=0, C=3, sh=True, scale_mul=4.0, fx=None):
+    """small_scene's surfels (synth.base_gaussians(P, seed) x scale_mul) with one of the named cameras: "orbit" (small_scene's own; `fx` overrides
+    its 1111.1 W / 800), "in_cloud", "at_origin", "aniso"."""
+    g, cam = small_scene(P=P, H=H, W=W, seed=seed, C=C, sh=sh, scale_mul=scale_mul)
+    if camera_kind == "orbit":
+        if fx is not None:
+            cam = synth.orbit_camera(1, H=H, W=W, fx=fx)
+    else:
+        cam = CAMERAS[camera_kind](H, W)
+    return g, cam
+
+
+def small_fx(W):
+    """Focal length of the images smaller than a tile: 1111.1 max(W, 16) / 800 (a 1-pixel-wide image keeps a field of view that sees surfels)."""
+    return 1111.1 * max(W, 16) / 800.0
+
+
+SMALL_IMAGES = [(1, 1), (5, 7), (16, 16), (17, 15), (1, 40), (33, 16)]      # (H, W): below one 16x16 tile, exactly one, ragged against both tile borders
 
 
 def cam_args(cam):
