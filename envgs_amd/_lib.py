@@ -68,6 +68,16 @@ class SupervisorArgs(ctypes.Structure):
                 + [(n, ctypes.c_void_p) for n in ("g_norm_map", "g_surf_norm_map", "g_acc_map", "g_dist_map", "g_env_opacity", "partial")])
 
 
+class SurfelInputsArgs(ctypes.Structure):
+    """struct envgs_surfel_inputs_args (include/envgs_model.h)."""
+    _fields_ = ([(n, ctypes.c_int32) for n in ("P", "sh_degree", "sh_coeffs", "spec_channels")]
+                + [(n, ctypes.c_void_p) for n in ("xyz", "features_dc", "features_rest", "scaling", "rotation", "opacity", "specular", "roughness", "campos",
+                                                  "scales", "rotations", "opacities", "specular_act", "roughness_act", "shs", "colors", "others", "vertices",
+                                                  "clamped",
+                                                  "g_scales", "g_rotations", "g_opacities", "g_specular_act", "g_roughness_act", "g_shs", "g_colors", "g_others",
+                                                  "d_xyz", "d_features_dc", "d_features_rest", "d_scaling", "d_rotation", "d_opacity", "d_specular", "d_roughness")])
+
+
 # every symbol include/*.h declares: name -> (restype, argtypes)
 _P = c_void_p
 SYMBOLS = {
@@ -107,6 +117,8 @@ SYMBOLS = {
     "envgs_blend_filtered_backward": (c_int, [ctypes.c_int32] * 4 + [_P] * 7 + [_P]),
     "envgs_surface_normal_forward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float] + [_P] * 4 + [_P]),
     "envgs_surface_normal_backward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float] + [_P] * 5 + [_P]),
+    "envgs_surfel_inputs_forward": (c_int, [ctypes.POINTER(SurfelInputsArgs), _P]),
+    "envgs_surfel_inputs_backward": (c_int, [ctypes.POINTER(SurfelInputsArgs), _P]),
     "envgs_fused_adam": (c_int, [ctypes.c_int32, ctypes.POINTER(AdamTensor), ctypes.c_float, ctypes.c_float, ctypes.c_float, _P]),
     "envgs_compact_temp_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
     "envgs_compact_scan": (c_int, [ctypes.c_int64, _P, _P, _P, _P, ctypes.c_size_t, _P]),

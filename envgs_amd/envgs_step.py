@@ -55,7 +55,10 @@ def base_pass(pkg, cam, base, bg, sh_degree, scale_modifier=1.0):
         # (a gradient SINK: the extension never reads its values -- a zero leaf, one fill, instead of the reference's `zeros_like(...) + 0`, two launches;
         #  zeros rather than uninitialised memory: a debug dump or anomaly detection that reads the values must not see NaN)
         means2D = torch.zeros_like(base["means3D"]).requires_grad_(True)
-        colors = fused.sh_colors(base["means3D"], base["shs"], cam.camera_center, sh_degree, base["specular"], base["roughness"])
+        if "colors_precomp" in base:
+            colors = base["colors_precomp"]                    # envgs_amd.model.raster_inputs: the colours came with the activations, from the raw parameters
+        else:
+            colors = fused.sh_colors(base["means3D"], base["shs"], cam.camera_center, sh_degree, base["specular"], base["roughness"])
     else:
         means2D = torch.zeros_like(base["means3D"], requires_grad=True, device=dev) + 0
         shs_view = base["shs"].transpose(1, 2)
@@ -171,7 +174,10 @@ def env_prepare(tracer, env):
     """Fused caller only: the environment set's 3-sigma quads and the request + START of the structure build, issued BEFORE the base pass so
     that the build (its own stream, SurfelTracer.prepare) runs under the rasterizer's forward.  Returns the vertex buffer for env_pass."""
     from . import fused
-    v, f = fused.surfel_quads(env["means3D"], env["scales"], env["rotations"])
+    if "v" in env:
+        v, f = env["v"], env["f"]                              # envgs_amd.model.tracer_inputs: the quads came with the activations
+    else:
+        v, f = fused.surfel_quads(env["means3D"], env["scales"], env["rotations"])
     _apply_policy(tracer)
     tracer.build_acceleration_structure(v, f, rebuild=True)
     tracer.prepare(env["opacities"])
@@ -190,7 +196,10 @@ def env_pass(tracer, tpkg, cam, env, ref_o, ref_d, env_bg, sh_degree, prepared_v
         v = prepared_v                                                 # quads computed and the build started before the base pass (env_prepare)
     elif FUSED["on"] and not REFERENCE_FORMS["on"]:
         from . import fused
-        v, f = fused.surfel_quads(env["means3D"], env["scales"], env["rotations"])          # one launch instead of ~25 torch kernels in front of the trace
+        if "v" in env:
+            v, f = env["v"], env["f"]                                                       # (envgs_amd.model.tracer_inputs)
+        else:
+            v, f = fused.surfel_quads(env["means3D"], env["scales"], env["rotations"])      # one launch instead of ~25 torch kernels in front of the trace
         _apply_policy(tracer)
         tracer.build_acceleration_structure(v, f, rebuild=True)
     else:
@@ -208,7 +217,7 @@ def env_pass(tracer, tpkg, cam, env, ref_o, ref_d, env_bg, sh_degree, prepared_v
     else:
         grads3D = torch.zeros_like(env["means3D"], requires_grad=True) + 0
     return tracer(ref_o.contiguous(), ref_d.contiguous(), v, means3D=env["means3D"].contiguous(), grads3D=grads3D,
-                  shs=env["shs"].contiguous(), colors_precomp=None, others_precomp=env.get("others"), opacities=env["opacities"].contiguous(),
+                  shs=env["shs"].contiguous(), colors_precomp=None, others_precomp=env.get("others", env.get("others_precomp")), opacities=env["opacities"].contiguous(),
                   scales=env["scales"].contiguous(), rotations=env["rotations"].contiguous(), cov3D_precomp=None,
                   tracer_settings=ts, start_from_first=False)
 
