@@ -35,6 +35,27 @@ class RowsTensor(ctypes.Structure):
     _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("row_bytes", ctypes.c_int64)]
 
 
+class GrowTensor(ctypes.Structure):
+    """struct envgs_grow_tensor (include/envgs_densify.h)."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("row_bytes", ctypes.c_int64), ("kind", ctypes.c_int32), ("reserved0", ctypes.c_int32)]
+
+
+class DensifyPlanArgs(ctypes.Structure):
+    """struct envgs_densify_plan_args (include/envgs_densify.h)."""
+    _fields_ = ([("P", ctypes.c_int64), ("N", ctypes.c_int32), ("flags", ctypes.c_uint32)]
+                + [(n, ctypes.c_float) for n in ("grad_threshold", "size_limit", "split_screen_threshold", "min_opacity", "min_gradient", "r")]
+                + [(n, ctypes.c_void_p) for n in ("ga", "dn", "mr", "wa", "scal", "opac", "cls", "scan", "counters", "temp")]
+                + [("temp_bytes", ctypes.c_size_t)])
+
+
+class DensifyRewriteArgs(ctypes.Structure):
+    """struct envgs_densify_rewrite_args (include/envgs_densify.h)."""
+    _fields_ = ([("P", ctypes.c_int64), ("out_rows", ctypes.c_int64), ("n_samples", ctypes.c_int64), ("N", ctypes.c_int32), ("count", ctypes.c_int32),
+                 ("ratio_n", ctypes.c_double), ("r", ctypes.c_float), ("reserved0", ctypes.c_uint32)]
+                + [(n, ctypes.c_void_p) for n in ("cls", "scan", "counters", "scal", "rotation", "samples")]
+                + [("tensors", ctypes.POINTER(GrowTensor))])
+
+
 class TraceLists(ctypes.Structure):
     """struct envgs_trace_lists (include/envgs_trace.h)."""
     _fields_ = [("hit_lists", ctypes.c_void_p), ("hit_cnt", ctypes.c_void_p), ("n_used", ctypes.c_void_p), ("cap", ctypes.c_int32),
@@ -124,6 +145,11 @@ SYMBOLS = {
     "envgs_compact_scan": (c_int, [ctypes.c_int64, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "envgs_compact_gather": (c_int, [ctypes.c_int32, ctypes.POINTER(RowsTensor), ctypes.c_int64, _P, _P, _P]),
     "envgs_knn3_mean_dist2": (c_int, [ctypes.c_int32, _P, _P, _P]),
+    "envgs_densify_stats": (c_int, [ctypes.c_int64, ctypes.c_int32] + [_P] * 8 + [_P]),
+    "envgs_densify_plan_temp_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
+    "envgs_densify_plan": (c_int, [ctypes.POINTER(DensifyPlanArgs), _P]),
+    "envgs_densify_split_stds": (c_int, [ctypes.c_int64, ctypes.c_int32] + [_P] * 5 + [ctypes.c_int64, _P]),
+    "envgs_densify_rewrite": (c_int, [ctypes.POINTER(DensifyRewriteArgs), _P]),
     "envgs_l1_ssim_partial_count": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "envgs_l1_ssim_forward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P]),
     "envgs_l1_ssim_backward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, ctypes.c_float, ctypes.c_float, _P, _P]),

@@ -115,6 +115,15 @@ def torch_rows(tensors, keep):
     return [t.detach()[keep] for t in tensors]
 
 
+def normal_offsets(stds, generator=None):
+    """The values (and the generator advance) of `torch.normal(torch.zeros_like(stds), stds, generator=generator)`, the staged split's call, without
+    that call's host check of `stds >= 0` -- a `.item()`, i.e. a second queue drain in a pass whose point is to have one.  torch evaluates the
+    tensor-std form as a standard normal fill of the output followed by `mul_(std).add_(mean)`; these are the same three steps (the added zero
+    turns a -0 offset into the +0 the staged call returns).  `stds` here are exp() of the raw scales, never negative.
+    tests/test_densify_device.py holds the two forms to bit equality on the GPU."""
+    return torch.empty_like(stds).normal_(0.0, 1.0, generator=generator).mul_(stds).add_(0.0)
+
+
 class SurfelSet:
     """One Gaussian set's raw parameters, their optimizer groups and the densification statistics, with the densify / prune schedule of the
     reference's `GaussianModel` (easyvolcap/utils/gaussian2d_utils.py:622-909) rebuilt over the compaction kernels:
@@ -126,15 +135,21 @@ class SurfelSet:
 
     raw: {"_xyz", "_features_dc", "_features_rest", "_scaling", "_rotation", "_opacity"[, "_specular", "_roughness"]} (ckpt.PT_PARAMS).
     optimizer: groups named `prefix + name`, one parameter each (the reference's layout, gaussian2d_utils.py:562-588); may be None.
-    row_ops: the row gather; defaults to the HIP `prune_rows` (GPU tensors only)."""
+    row_ops: the row gather; defaults to the HIP `prune_rows` (GPU tensors only).
+    device_schedule: OPT-IN device-resident mode (GPU tensors only, no CPU path): `add_densification_stats` becomes one launch without a host
+        round trip, and `densify_and_prune` runs its first three stages as `grow_and_prune` -- one plan, one read-back, one rewrite.  Survivors,
+        clones, moments, statistics and `log` equal the staged path bit for bit; the split children's `_xyz` / `_scaling` are the same formulas
+        evaluated in a HIP kernel, so they agree with the staged torch expressions to rounding, not to the bit: hence opt-in."""
 
     STATS = ("xyz_gradient_accum", "denom", "max_radii2D", "xyz_weight_accum")
 
-    def __init__(self, raw, optimizer=None, prefix="", spatial_scale=1.0, max_gs=None, max_gs_threshold=1.0, row_ops=None, generator=None):
+    def __init__(self, raw, optimizer=None, prefix="", spatial_scale=1.0, max_gs=None, max_gs_threshold=1.0, row_ops=None, generator=None,
+                 device_schedule=False):
         self.names = [k for k in ("_xyz", "_features_dc", "_features_rest", "_scaling", "_rotation", "_opacity", "_specular", "_roughness") if k in raw]
         self.optimizer, self.prefix, self.spatial_scale = optimizer, prefix, float(spatial_scale)
         self.max_gs, self.max_gs_threshold = max_gs, max_gs_threshold
         self.rows = row_ops or prune_rows
+        self.device_schedule = bool(device_schedule)
         # split offsets are random: with data parallelism every rank must draw the SAME ones (SURVEY.md section 8e), i.e. pass generators seeded
         # identically on all ranks (or seed the global generator identically before every densification)
         self.generator = generator
@@ -143,6 +158,8 @@ class SurfelSet:
         for k in self.names:
             g = groups.get(prefix + k)
             self.p[k] = g["params"][0] if g is not None else nn.Parameter(raw[k].detach().clone().requires_grad_(True))
+        if self.device_schedule and self.device.type != "cuda":
+            raise RuntimeError("SurfelSet(device_schedule=True) needs GPU tensors; there is no CPU path")
         self.reset_stats()
         self.log = []                                # (event, count) pairs, the numbers the reference prints
 
@@ -173,6 +190,8 @@ class SurfelSet:
     def add_densification_stats(self, viewspace_grad, update_filter, weight_accumulate=None, radii=None):
         """viewspace_grad: the `.grad` of the rasterizer's means2D (P,3); update_filter: (P,) bool; radii (optional): the max-radius update the
         sampler does next to it (gaussian2d_sampler.py:330-332)."""
+        if self.device_schedule:
+            return self._device_stats(viewspace_grad, update_filter, weight_accumulate, radii)
         s = self.stats
         s["denom"][update_filter] += 1
         s["xyz_gradient_accum"][update_filter] += torch.norm(viewspace_grad[update_filter], dim=-1, keepdim=True)
@@ -180,6 +199,37 @@ class SurfelSet:
             s["xyz_weight_accum"][update_filter] += weight_accumulate[update_filter]
         if radii is not None:
             s["max_radii2D"][update_filter] = torch.max(s["max_radii2D"][update_filter], radii[update_filter].to(s["max_radii2D"].dtype))
+
+    def _device_stats(self, viewspace_grad, update_filter, weight_accumulate, radii):
+        """The same update as one launch of envgs_densify_stats: no boolean-mask indexing, hence no nonzero and no host read-back."""
+        lib = _lib.load()
+        s, P, dev = self.stats, self.number, self.device
+        grad = viewspace_grad.detach()
+        if grad.dim() != 2 or grad.shape[0] != P or grad.shape[1] not in (2, 3) or update_filter.shape != (P,):
+            raise RuntimeError("add_densification_stats: viewspace_grad must be (%d, 2 or 3) and update_filter (%d,)" % (P, P))
+        for t in (grad, update_filter, weight_accumulate, radii):
+            if t is not None and t.device != dev:
+                raise RuntimeError("add_densification_stats: device_schedule needs every tensor on %s; there is no CPU path" % dev)
+        if grad.dtype != torch.float32 or not grad.is_contiguous():
+            grad = grad.to(torch.float32).contiguous()
+        flt = update_filter.contiguous()
+        flt = flt.view(torch.uint8) if flt.dtype == torch.bool else (flt != 0).view(torch.uint8)
+        w = weight_accumulate
+        if w is not None:
+            if w.numel() != P:
+                raise RuntimeError("add_densification_stats: weight_accumulate must have %d elements" % P)
+            w = w.detach()
+            if w.dtype != torch.float32 or not w.is_contiguous():
+                w = w.to(torch.float32).contiguous()
+        r = radii
+        if r is not None:
+            if r.numel() != P:
+                raise RuntimeError("add_densification_stats: radii must have %d elements" % P)
+            if r.dtype != torch.int32 or not r.is_contiguous():
+                r = r.to(torch.int32).contiguous()                   # (the rasterizer's radii are int32 already)
+        p = _lib.ptr
+        _lib.check(lib.envgs_densify_stats(P, grad.shape[1], p(grad), p(flt), p(w), p(r), p(s["xyz_gradient_accum"]), p(s["denom"]),
+                                           p(s["max_radii2D"]), p(s["xyz_weight_accum"]), _stream(dev)), "envgs_densify_stats")
 
     def _avg(self, key):
         avg = self.stats[key] / self.stats["denom"]
@@ -342,6 +392,81 @@ class SurfelSet:
         if n > 0:
             self.remove(mask)
 
+    _GROW_KINDS = {"_xyz": 2, "_scaling": 3}                  # ENVGS_GROW_XYZ / _SCALING; every other parameter is ENVGS_GROW_COPY
+    _GROW_STATS = {"xyz_gradient_accum": 4, "denom": 5, "max_radii2D": 6, "xyz_weight_accum": 7}
+
+    def grow_and_prune(self, min_opacity, min_gradient, grad_threshold, size_threshold, split_screen_threshold=None, N=2, ratio=0.8):
+        """densify_and_clone -> densify_and_split -> prune_min_opacity_and_gradients as ONE pass (device_schedule only).  A clone child inherits
+        the scale, opacity and statistics its parent is judged by, so what the later stages decide for it is known from the parent, and the
+        three stages' result is a closed-form function of the set before the pass: one plan launch + scan decides and places every row, ONE
+        read-back brings the counts (the pass's only host sync), the split offsets are the staged path's own `torch.normal` draw (`normal_offsets`),
+        and one launch writes every parameter, both Adam moments and the four statistics at their final size.  Rows, moments, statistics and
+        `log` equal the staged result; the split children's `_xyz` / `_scaling` agree with it to rounding (see the class docstring)."""
+        if not self.device_schedule:
+            raise RuntimeError("grow_and_prune is the device-resident pass: build the SurfelSet with device_schedule=True")
+        lib = _lib.load()
+        P, dev, p = self.number, self.device, _lib.ptr
+        N = int(N)
+        if P == 0:
+            self.log += [("clone", 0), ("split", 0), ("prune_occ_grad", 0)]
+            return
+        scal = self.scaling().to(torch.float32).contiguous()
+        opac = self.opacity().to(torch.float32).contiguous() if min_opacity is not None else None
+        st = {k: self.stats[k].contiguous() for k in self.STATS}
+        cls = torch.empty(P, dtype=torch.uint8, device=dev)
+        scan = torch.empty(6 * P, dtype=torch.int32, device=dev)
+        counters = torch.empty(16, dtype=torch.int32, device=dev)
+        tb = lib.envgs_densify_plan_temp_bytes(P)
+        temp = torch.empty(max(tb, 1), dtype=torch.uint8, device=dev)
+        r = 1.0 / (ratio * N)
+        flags = (1 if min_opacity is not None else 0) | (2 if min_gradient is not None else 0) | (4 if split_screen_threshold is not None else 0)
+        plan = _lib.DensifyPlanArgs(P, N, flags, grad_threshold, size_threshold * self.spatial_scale, split_screen_threshold or 0.0, min_opacity or 0.0,
+                                    min_gradient or 0.0, r, st["xyz_gradient_accum"].data_ptr(), st["denom"].data_ptr(), st["max_radii2D"].data_ptr(),
+                                    st["xyz_weight_accum"].data_ptr(), scal.data_ptr(), opac.data_ptr() if opac is not None else None,
+                                    cls.data_ptr(), scan.data_ptr(), counters.data_ptr(), temp.data_ptr(), tb)
+        _lib.check(lib.envgs_densify_plan(plan, _stream(dev)), "envgs_densify_plan")
+        nA, nB, nD, nE, nS1, nS2, n_clone = [int(v) & 0xFFFFFFFF for v in counters.cpu().tolist()[:7]]          # the one host sync
+        nS = nS1 + nS2
+        total = nA + nB + N * (nD + nE)
+        self.log += [("clone", n_clone), ("split", nS), ("prune_occ_grad", P + n_clone + (N - 1) * nS - total)]
+        if n_clone == 0 and nS == 0 and nA == P:
+            return                                                   # nothing selected: nothing installed, nothing drawn
+        samples = None
+        if nS > 0:
+            stds = torch.empty(N * nS, 3, dtype=torch.float32, device=dev)
+            _lib.check(lib.envgs_densify_split_stds(P, N, p(cls), p(scan), p(counters), p(scal), p(stds), N * nS, _stream(dev)), "envgs_densify_split_stds")
+            samples = normal_offsets(stds, self.generator)
+        items, desc, keep = self._groups(), [], []
+
+        def add(src, kind):
+            src = src.detach().contiguous()
+            if src.shape[0] != P or src.dtype != torch.float32:
+                raise RuntimeError("grow_and_prune: every tensor must be float32 with %d rows" % P)
+            dst = torch.empty((total,) + tuple(src.shape[1:]), dtype=src.dtype, device=dev)
+            keep.append(src)
+            desc.append(_lib.GrowTensor(src.data_ptr(), dst.data_ptr(), 4 * (src[0].numel()), kind, 0))
+            return dst
+
+        new = []
+        for k, g, prm, ost in items:
+            data = add(prm.data, self._GROW_KINDS.get(k, 0))
+            if ost is not None and "exp_avg" in ost:
+                new.append((data, add(ost["exp_avg"], 1), add(ost["exp_avg_sq"], 1)))
+            else:
+                new.append((data, None, None))
+        new_stats = {k: add(st[k], self._GROW_STATS[k]) for k in self.STATS}
+        rot = self.p["_rotation"].detach().to(torch.float32).contiguous()
+        for i in range(0, len(desc), 32):
+            chunk = desc[i:i + 32]
+            arr = (_lib.GrowTensor * len(chunk))(*chunk)
+            args = _lib.DensifyRewriteArgs(P, total, N * nS, N, len(chunk), float(ratio * N), r, 0, cls.data_ptr(), scan.data_ptr(), counters.data_ptr(),
+                                           scal.data_ptr(), rot.data_ptr(), samples.data_ptr() if samples is not None else None, arr)
+            _lib.check(lib.envgs_densify_rewrite(args, _stream(dev)), "envgs_densify_rewrite")
+        for (k, g, prm, ost), (data, m, v) in zip(items, new):
+            self._install(k, g, prm, ost, data, m, v)
+        self.stats = new_stats
+        self._scene_changed()
+
     def prune_max_scene_and_screen(self, max_scene_threshold=None, max_screen_threshold=None, min_weight_threshold=None):
         P, dev = self.number, self.device
         none = torch.zeros(P, dtype=torch.bool, device=dev)
@@ -374,9 +499,12 @@ class SurfelSet:
     def densify_and_prune(self, min_opacity, min_gradient, densify_grad_threshold, densify_size_threshold, split_screen_threshold=None,
                           max_scene_threshold=None, max_screen_threshold=None, min_weight_threshold=None, prune_visibility=False, prune_large_gs=False):
         """:866-899, the same order: clone, split, prune by opacity / gradient, [prune or split the oversized], [prune the least visible], reset."""
-        self.densify_and_clone(densify_grad_threshold, densify_size_threshold)
-        self.densify_and_split(densify_grad_threshold, densify_size_threshold, split_screen_threshold)
-        self.prune_min_opacity_and_gradients(min_opacity, min_gradient)
+        if self.device_schedule:
+            self.grow_and_prune(min_opacity, min_gradient, densify_grad_threshold, densify_size_threshold, split_screen_threshold)
+        else:
+            self.densify_and_clone(densify_grad_threshold, densify_size_threshold)
+            self.densify_and_split(densify_grad_threshold, densify_size_threshold, split_screen_threshold)
+            self.prune_min_opacity_and_gradients(min_opacity, min_gradient)
         if prune_large_gs:
             self.prune_max_scene_and_screen(max_scene_threshold, max_screen_threshold, min_weight_threshold)
         if prune_visibility:
