@@ -15,8 +15,10 @@ Outputs are channels-last with the ray tensor's leading shape: rgb (...,3), dpt 
 dist (...,1), aux (...,2), mid (...,16*(max_trace_depth+1)), wet (P,1).  Differentiable inputs: ray_o, ray_d, means3D,
 grads3D (gradient sink for the densification signal), shs | colors_precomp, others_precomp, opacities, scales, rotations.
 
-OptiX is replaced by a hand-written HIP LBVH (Morton build every call with rebuild=True, like the reference rebuilds
-its GAS every training iteration) and a persistent-wavefront traversal.  No fallback path exists.
+OptiX is replaced by a hand-written HIP LBVH and a persistent-wavefront traversal.  The reference rebuilds its GAS every
+training iteration (rebuild=True); here such a request is a full Morton build only when the surfel count changed or the
+tree has aged or degraded -- otherwise an exact refit of the existing topology (SurfelTracer.set_structure_policy).
+rebuild=False is always a refit.  No fallback path exists.
 """
 from typing import NamedTuple
 

@@ -25,7 +25,9 @@
  *   - grads3D.grad (densification signal) = dL/dmeans3D;
  *   - bounces (max_trace_depth > 0): stage k+1 starts at o + d*dpt_k/acc_k along d - 2(d.n)n with n = normalised
  *     accumulated normal, is traced when aux[0] (specular) > specular_threshold and acc_k > 0.5; stage radiance is
- *     blended rgb_k <- (1-s_k)*rgb_k + s_k*rgb_{k+1}; secondary rays are DETACHED (gradients only through stage 0).
+ *     blended rgb_k <- (1-s_k)*rgb_k + s_k*rgb_{k+1}.  trc_forward runs the whole chain; trc_backward differentiates ONE stage.  The chain's
+ *     gradient is not detached: the drop-in module traces every bounce stage as a call of its own (start_from_first == 2) and
+ *     differentiates the glue between the calls, so each stage is compared with trc_backward on the rays and upstream gradients it was given.
  */
 #include <math.h>
 #include <stdint.h>
@@ -83,25 +85,29 @@ typedef struct { float t, u, v, G, alpha, denom; } rhit_t;
  * in-line bounce stages of trc_forward */
 static float first_tmin(int start_from_first) { return start_from_first == 1 ? NEAR_N : (start_from_first == 2 ? 1.0e-3f : 0.0f); }
 
-/* ray / surfel: returns 1 when the hit counts (inside the 3-sigma quad, alpha >= 1/255, t > tmin) */
-static int hit_surfel(const surfel_t *s, const float *o, const float *d, float tmin, rhit_t *h)
+/* ray / surfel: returns 1 when the hit counts (inside the 3-sigma quad, alpha >= 1/255, t > tmin).  exits == 0 (a surfel of a FORCED hit list,
+ * trc_set_forced_lists): the same float code without the early exits -- *h is always filled and the verdict only returned. */
+static int hit_surfel_x(const surfel_t *s, const float *o, const float *d, float tmin, rhit_t *h, int exits)
 {
+    int ok = 1;
     float denom = s->n[0] * d[0] + s->n[1] * d[1] + s->n[2] * d[2];
-    if (denom == 0.0f) return 0;
+    if (denom == 0.0f) { if (exits) return 0; ok = 0; }
     float num = s->n[0] * (s->mu[0] - o[0]) + s->n[1] * (s->mu[1] - o[1]) + s->n[2] * (s->mu[2] - o[2]);
     float t = num / denom;
-    if (!(t > tmin)) return 0;
+    if (!(t > tmin)) { if (exits) return 0; ok = 0; }
     float qx = o[0] + t * d[0] - s->mu[0], qy = o[1] + t * d[1] - s->mu[1], qz = o[2] + t * d[2] - s->mu[2];
     float u = (s->a[0] * qx + s->a[1] * qy + s->a[2] * qz) / s->su;
     float v = (s->b[0] * qx + s->b[1] * qy + s->b[2] * qz) / s->sv;
-    if (!(fabsf(u) <= UV_MAX && fabsf(v) <= UV_MAX)) return 0;
+    if (!(fabsf(u) <= UV_MAX && fabsf(v) <= UV_MAX)) { if (exits) return 0; ok = 0; }
     float G = expf(-0.5f * (u * u + v * v));
     float a = s->opa * G;
     float alpha = a < ALPHA_CAP ? a : ALPHA_CAP;
-    if (alpha < ALPHA_MIN) return 0;
+    if (alpha < ALPHA_MIN) { if (exits) return 0; ok = 0; }
     h->t = t; h->u = u; h->v = v; h->G = G; h->alpha = alpha; h->denom = denom;
-    return 1;
+    return ok;
 }
+
+static int hit_surfel(const surfel_t *s, const float *o, const float *d, float tmin, rhit_t *h) { return hit_surfel_x(s, o, d, tmin, h, 1); }
 
 static void sh_basis(int D, const float *dir, float basis[16])
 {
@@ -176,19 +182,57 @@ static int ent_cmp(const void *a, const void *b)
     return x->id < y->id ? -1 : (x->id > y->id);
 }
 
-typedef struct { float rgb[3], dpt, acc, nrm[3], dist, aux[2], T; int nhit; double dist64, distb; } stage_t;     /* dist64 / distb: the distortion shadow, see trc_set_dist_shadow */
+/*
+ * Forced hit lists (test infrastructure, set before a call of trc_forward / trc_backward / trc_audit and cleared by it, like trc_set_dist_shadow):
+ * ids (R, cap), n (R), mask (R).  For a ray with mask[r] != 0, stage 0 composites exactly the surfels ids[r, 0:n[r]] -- each evaluated by the same
+ * float code without the |u|,|v|, alpha and t > tmin exits, sorted by (t, id), all of them blended with no T_EPS break.  This is how a ray whose
+ * decisions lie within fp32 noise of their thresholds is compared under the decisions ANOTHER implementation took (tests/test_trace_parity.py).
+ * Rays with mask[r] == 0 run as always.  gather_hits is the ONE place that builds a ray's sorted hit list, for the forward, the backward and the audit.
+ */
+typedef struct { const int32_t *ids, *n; const uint8_t *mask; int cap; } forced_t;
+static forced_t g_forced = {NULL, NULL, NULL, 0};
+void trc_set_forced_lists(const int32_t *ids, const int32_t *n, const uint8_t *mask, int cap)
+{
+    g_forced.ids = ids; g_forced.n = n; g_forced.mask = mask; g_forced.cap = cap;
+}
+static forced_t take_forced(void) { forced_t f = g_forced; if (!(f.ids && f.n && f.mask)) { f.ids = NULL; f.n = NULL; f.mask = NULL; f.cap = 0; } return f; }
+static void clear_forced(void) { g_forced.ids = NULL; g_forced.n = NULL; g_forced.mask = NULL; g_forced.cap = 0; }
+/* scratch entries a ray may need: every surfel, or a whole forced list */
+static size_t ents_cap(const trc_cfg *cfg, const forced_t *F) { size_t n = (size_t)(cfg->P > 0 ? cfg->P : 1); return n > (size_t)F->cap ? n : (size_t)F->cap; }
 
-/* one stage: trace ray (o,d), composite front to back.  ents is scratch of size P. */
-static void trace_stage(const trc_cfg *cfg, const surfel_t *S, const float *shs, const float *colors_precomp,
-                        const float *others, const float *bg, const float *o, const float *d, float tmin, ent_t *ents,
-                        stage_t *out, double *wet)
+/* the sorted (t, id) hit list of ray r (r < 0: a bounce stage, never forced) into ents; *forced = the list was given, composite all of it */
+static int gather_hits(const trc_cfg *cfg, const surfel_t *S, const float *o, const float *d, float tmin, const forced_t *F, int r, ent_t *ents, int *forced)
 {
     int n = 0;
-    for (int i = 0; i < cfg->P; i++) {
-        rhit_t h;
-        if (hit_surfel(&S[i], o, d, tmin, &h)) { ents[n].t = h.t; ents[n].id = i; ents[n].h = h; n++; }
+    *forced = (F && F->mask && r >= 0 && F->mask[r]) ? 1 : 0;
+    if (*forced) {
+        const int m = F->n[r] < F->cap ? F->n[r] : F->cap;
+        for (int k = 0; k < m; k++) {
+            const int i = F->ids[(size_t)r * F->cap + k];
+            if (i < 0 || i >= cfg->P) continue;
+            rhit_t h;
+            hit_surfel_x(&S[i], o, d, tmin, &h, 0);
+            ents[n].t = h.t; ents[n].id = i; ents[n].h = h; n++;
+        }
+    } else {
+        for (int i = 0; i < cfg->P; i++) {
+            rhit_t h;
+            if (hit_surfel(&S[i], o, d, tmin, &h)) { ents[n].t = h.t; ents[n].id = i; ents[n].h = h; n++; }
+        }
     }
     qsort(ents, n, sizeof(ent_t), ent_cmp);
+    return n;
+}
+
+typedef struct { float rgb[3], dpt, acc, nrm[3], dist, aux[2], T; int nhit; double dist64, distb; } stage_t;     /* dist64 / distb: the distortion shadow, see trc_set_dist_shadow */
+
+/* one stage: trace ray (o,d) = ray r of the call (r < 0: a bounce stage), composite front to back.  ents is scratch of size ents_cap(). */
+static void trace_stage(const trc_cfg *cfg, const surfel_t *S, const float *shs, const float *colors_precomp,
+                        const float *others, const float *bg, const float *o, const float *d, float tmin, const forced_t *F, int r, ent_t *ents,
+                        stage_t *out, double *wet)
+{
+    int forced;
+    const int n = gather_hits(cfg, S, o, d, tmin, F, r, ents, &forced);
     float dl = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
     float dir[3] = {d[0] / dl, d[1] / dl, d[2] / dl};
     float basis[16];
@@ -201,7 +245,7 @@ static void trace_stage(const trc_cfg *cfg, const surfel_t *S, const float *shs,
         const rhit_t *h = &ents[k].h;
         const int g = ents[k].id;
         float test_T = T * (1.0f - h->alpha);
-        if (test_T < T_EPS) break;
+        if (!forced && test_T < T_EPS) break;
         float w = h->alpha * T;
         float col[3]; int cl[3];
         surfel_color(cfg, g, shs, colors_precomp, basis, col, cl);
@@ -251,13 +295,14 @@ void trc_forward(const trc_cfg *cfg, const float *ray_o, const float *ray_d, con
                  double *wet, float *final_T, int32_t *nhits)
 {
     const int P = cfg->P, R = cfg->R, ND = cfg->max_trace_depth + 1;
+    const forced_t F = take_forced();
     surfel_t *S = (surfel_t *)malloc(sizeof(surfel_t) * (P ? P : 1));
     for (int i = 0; i < P; i++) make_surfel(cfg, i, means, scales, rots, opac, &S[i]);
     memset(wet, 0, sizeof(double) * P);
     memset(mid, 0, sizeof(float) * (size_t)R * MID_CH * ND);
 #pragma omp parallel
     {
-        ent_t *ents = (ent_t *)malloc(sizeof(ent_t) * (P ? P : 1));
+        ent_t *ents = (ent_t *)malloc(sizeof(ent_t) * ents_cap(cfg, &F));
 #pragma omp for schedule(dynamic, 16)
         for (int r = 0; r < R; r++) {
             float o[3] = {ray_o[3 * r], ray_o[3 * r + 1], ray_o[3 * r + 2]};
@@ -266,7 +311,7 @@ void trc_forward(const trc_cfg *cfg, const float *ray_o, const float *ray_d, con
             int ns = 0;
             float tmin = first_tmin(cfg->start_from_first);
             for (int k = 0; k < ND && k < 8; k++) {
-                trace_stage(cfg, S, shs, colors_precomp, others, bg, o, d, tmin, ents, &st[k], wet);     /* wet: summed over ALL stages (a surfel blended only by bounce rays is visible too) */
+                trace_stage(cfg, S, shs, colors_precomp, others, bg, o, d, tmin, &F, k == 0 ? r : -1, ents, &st[k], wet);     /* wet: summed over ALL stages (a surfel blended only by bounce rays is visible too) */
                 float *m = mid + ((size_t)r * ND + k) * MID_CH;
                 m[0] = o[0]; m[1] = o[1]; m[2] = o[2]; m[3] = d[0]; m[4] = d[1]; m[5] = d[2];
                 m[6] = st[k].dpt; m[7] = st[k].acc; m[8] = st[k].nrm[0]; m[9] = st[k].nrm[1]; m[10] = st[k].nrm[2];
@@ -301,6 +346,7 @@ void trc_forward(const trc_cfg *cfg, const float *ray_o, const float *ray_d, con
     }
     free(S);
     g_dist64 = NULL; g_distb = NULL;
+    clear_forced();
 }
 
 /*
@@ -334,15 +380,67 @@ static void make_surfel64(const trc_cfg *cfg, int i, const float *means, const f
     s->opa = opac[i];
 }
 
-typedef struct { float t; int id; float alpha; double t64, alpha64; } aent_t;
-static int aent_cmp(const void *a, const void *b)
+/* the double shadow of one ray / surfel pair from the raw parameters (tf, uf, vf, af: the float values, kept where the double ray is parallel to the plane) */
+static void shadow64(const surfel64_t *s, const double *o64, const double *d64, float tf, float uf, float vf, float af, double *t64, double *u64, double *v64, double *a64)
 {
-    const aent_t *x = (const aent_t *)a, *y = (const aent_t *)b;
+    const double den = s->n[0] * d64[0] + s->n[1] * d64[1] + s->n[2] * d64[2];
+    *t64 = tf; *u64 = uf; *v64 = vf; *a64 = af;
+    if (den != 0.0) {
+        *t64 = (s->n[0] * (s->mu[0] - o64[0]) + s->n[1] * (s->mu[1] - o64[1]) + s->n[2] * (s->mu[2] - o64[2])) / den;
+        const double qx = o64[0] + *t64 * d64[0] - s->mu[0], qy = o64[1] + *t64 * d64[1] - s->mu[1], qz = o64[2] + *t64 * d64[2] - s->mu[2];
+        *u64 = (s->a[0] * qx + s->a[1] * qy + s->a[2] * qz) / s->su;
+        *v64 = (s->b[0] * qx + s->b[1] * qy + s->b[2] * qz) / s->sv;
+        const double a = s->opa * exp(-0.5 * (*u64 * *u64 + *v64 * *v64));
+        *a64 = a < (double)ALPHA_CAP ? a : (double)ALPHA_CAP;
+    }
+}
+
+static int near_thr(double q32, double q64, double thr) { return fabs(q64 - thr) <= AUD_K * fabs(q32 - q64) + AUD_M0 * fabs(thr); }
+
+/* a candidate of a ray: a float-accepted hit (the natural list N) or an ambiguous surfel (the set A), or both */
+typedef struct { float t; int id; float alpha; double alpha64; int flags; } cand_t;
+static int cand_cmp(const void *a, const void *b)
+{
+    const cand_t *x = (const cand_t *)a, *y = (const cand_t *)b;
     if (x->t != y->t) return x->t < y->t ? -1 : 1;
     return x->id < y->id ? -1 : (x->id > y->id);
 }
 
-static int near_thr(double q32, double q64, double thr) { return fabs(q64 - thr) <= AUD_K * fabs(q32 - q64) + AUD_M0 * fabs(thr); }
+/*
+ * Optional outputs of trc_audit (set before the call, cleared by it): WHY a ray is fragile and WHERE.
+ *   kind (R) u8      : TRC_KIND_* bits; kind != 0 <=> fragile.
+ *   amb_ids (R, acap), namb (R): the ambiguous set A -- every surfel whose |u|, |v| or alpha test fires near_thr or whose float and double verdicts
+ *                      differ; namb is the true count (namb > acap: the set overflowed its capacity).
+ *   the candidates N u A of every FRAGILE ray in (t, id) order, in a pool shared by the rays (row r: pool[cand_off[r] .. + ncand[r]); cand_off = -1: the
+ *   pool was full): pool_ids, pool_tbits (float bits of t), pool_alpha (the float alpha), pool_flags:
+ *       TRC_CAND_HIT    float-accepted (in N: N is what the ray would composite without the termination test)
+ *       TRC_CAND_AMB    ambiguous (in A)
+ *       TRC_CAND_BEHIND (forced rays) sorts behind the last entry of the forced list
+ *       TRC_CAND_STOPS  (forced rays, behind) with the forced list's final T this candidate's termination test is below or near the threshold
+ *   go (R, lcap) u8  : per composited entry k of ids[r]: 1 = going on was decided (test_T >= T_EPS), | 2 = the test is near the threshold.  On a forced
+ *                      ray every entry is composited, so an entry with go == 0 was composited behind a decisive stop.
+ */
+#define TRC_KIND_DISAGREE 1
+#define TRC_KIND_GEOM 2
+#define TRC_KIND_TERM 4
+#define TRC_KIND_CLAMP 8
+#define TRC_KIND_BOUNCE 16
+#define TRC_CAND_HIT 1
+#define TRC_CAND_AMB 2
+#define TRC_CAND_BEHIND 4
+#define TRC_CAND_STOPS 8
+typedef struct {
+    uint8_t *kind;
+    int32_t *amb_ids; int32_t acap; int32_t *namb;
+    int32_t *pool_ids; uint32_t *pool_tbits; float *pool_alpha; uint8_t *pool_flags; int64_t pool_cap;
+    int64_t *cand_off; int32_t *ncand;
+    uint8_t *go;
+} trc_audit_detail;
+static trc_audit_detail g_detail;
+static int g_have_detail = 0;
+void trc_set_audit_detail(const trc_audit_detail *d) { if (d) { g_detail = *d; g_have_detail = 1; } else g_have_detail = 0; }
+
+static uint32_t fbits(float f) { union { float f; uint32_t u; } cv; cv.f = f; return cv.u; }
 
 void trc_audit(const trc_cfg *cfg, const float *ray_o, const float *ray_d, const float *means, const float *scales,
                const float *rots, const float *opac, const float *others, const float *shs, float tmin_override, float bounce_thr,
@@ -351,18 +449,24 @@ void trc_audit(const trc_cfg *cfg, const float *ray_o, const float *ray_d, const
     /* shs (optional, with cfg->D / cfg->M): the colour clamp clamp_min(SH + 0.5, 0) is a decision too -- a blended colour channel within its
      * own fp32 rounding of zero flips the clamp and with it that hit's whole SH gradient; such rays are flagged like the other near-threshold ones. */
     const int P = cfg->P, R = cfg->R;
+    const forced_t F = take_forced();
+    trc_audit_detail D;
+    memset(&D, 0, sizeof(D));
+    if (g_have_detail) D = g_detail;
+    int64_t pool_used = 0;
     surfel_t *S = (surfel_t *)malloc(sizeof(surfel_t) * (P ? P : 1));
     surfel64_t *S64 = (surfel64_t *)malloc(sizeof(surfel64_t) * (P ? P : 1));
     for (int i = 0; i < P; i++) { make_surfel(cfg, i, means, scales, rots, opac, &S[i]); make_surfel64(cfg, i, means, scales, rots, opac, &S64[i]); }
     const float tmin = tmin_override >= 0.0f ? tmin_override : first_tmin(cfg->start_from_first);
 #pragma omp parallel
     {
-        aent_t *ents = (aent_t *)malloc(sizeof(aent_t) * (P ? P : 1));
+        ent_t *ents = (ent_t *)malloc(sizeof(ent_t) * ents_cap(cfg, &F));
+        cand_t *cand = (cand_t *)malloc(sizeof(cand_t) * (P ? P : 1));
 #pragma omp for schedule(dynamic, 16)
         for (int r = 0; r < R; r++) {
             const float *o = ray_o + 3 * r, *d = ray_d + 3 * r;
             const double o64[3] = {o[0], o[1], o[2]}, d64[3] = {d[0], d[1], d[2]};
-            int frag = 0, n = 0;
+            int frag = 0, kind = 0, namb = 0, nc = 0;
             float basis[16];
             if (shs && cfg->M > 0) {
                 const float il = 1.0f / sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
@@ -370,6 +474,7 @@ void trc_audit(const trc_cfg *cfg, const float *ray_o, const float *ray_d, const
                 for (int k = 0; k < 16; k++) basis[k] = 0.f;
                 sh_basis(cfg->D, dn, basis);
             }
+            /* every surfel's decisions, float next to double: the ambiguous set A and the candidates N u A */
             for (int i = 0; i < P; i++) {
                 rhit_t h;
                 const int ok = hit_surfel(&S[i], o, d, tmin, &h);
@@ -385,38 +490,40 @@ void trc_audit(const trc_cfg *cfg, const float *ray_o, const float *ray_d, const
                 const float af0 = f->opa * expf(-0.5f * (uf * uf + vf * vf));
                 const float af = af0 < ALPHA_CAP ? af0 : ALPHA_CAP;
                 /* the double shadow, from the raw parameters */
-                const surfel64_t *s = &S64[i];
-                const double den = s->n[0] * d64[0] + s->n[1] * d64[1] + s->n[2] * d64[2];
-                double t64 = tf, u64 = uf, v64 = vf, a64 = af;
-                if (den != 0.0) {
-                    t64 = (s->n[0] * (s->mu[0] - o64[0]) + s->n[1] * (s->mu[1] - o64[1]) + s->n[2] * (s->mu[2] - o64[2])) / den;
-                    const double qx = o64[0] + t64 * d64[0] - s->mu[0], qy = o64[1] + t64 * d64[1] - s->mu[1], qz = o64[2] + t64 * d64[2] - s->mu[2];
-                    u64 = (s->a[0] * qx + s->a[1] * qy + s->a[2] * qz) / s->su;
-                    v64 = (s->b[0] * qx + s->b[1] * qy + s->b[2] * qz) / s->sv;
-                    const double a = s->opa * exp(-0.5 * (u64 * u64 + v64 * v64));
-                    a64 = a < (double)ALPHA_CAP ? a : (double)ALPHA_CAP;
-                }
+                double t64, u64, v64, a64;
+                shadow64(&S64[i], o64, d64, tf, uf, vf, af, &t64, &u64, &v64, &a64);
+                int amb = 0;
                 const int ok64 = fabs(u64) <= (double)UV_MAX && fabs(v64) <= (double)UV_MAX && a64 >= (double)ALPHA_MIN;
-                if (ok != ok64) frag = 1;
+                if (ok != ok64) { frag = 1; kind |= TRC_KIND_DISAGREE; amb = 1; }
                 /* only surfels that could make a difference: roughly inside the quad, roughly visible */
                 if (fabs(u64) <= UV_MAX + 0.5 && fabs(v64) <= UV_MAX + 0.5 && a64 >= 0.5 * (double)ALPHA_MIN) {
-                    if (near_thr(fabsf(uf), fabs(u64), (double)UV_MAX)) frag = 1;
-                    if (near_thr(fabsf(vf), fabs(v64), (double)UV_MAX)) frag = 1;
-                    if (near_thr(af, a64, (double)ALPHA_MIN)) frag = 1;
+                    if (near_thr(fabsf(uf), fabs(u64), (double)UV_MAX)) { frag = 1; kind |= TRC_KIND_GEOM; amb = 1; }
+                    if (near_thr(fabsf(vf), fabs(v64), (double)UV_MAX)) { frag = 1; kind |= TRC_KIND_GEOM; amb = 1; }
+                    if (near_thr(af, a64, (double)ALPHA_MIN)) { frag = 1; kind |= TRC_KIND_GEOM; amb = 1; }
                 }
-                if (ok) { ents[n].t = h.t; ents[n].id = i; ents[n].alpha = h.alpha; ents[n].t64 = t64; ents[n].alpha64 = a64; n++; }
+                if (amb) {
+                    if (D.amb_ids && namb < D.acap) D.amb_ids[(size_t)r * D.acap + namb] = i;
+                    namb++;
+                }
+                if (ok || amb) { cand[nc].t = tf; cand[nc].id = i; cand[nc].alpha = af; cand[nc].alpha64 = a64; cand[nc].flags = (ok ? TRC_CAND_HIT : 0) | (amb ? TRC_CAND_AMB : 0); nc++; }
             }
-            qsort(ents, n, sizeof(aent_t), aent_cmp);
+            /* the replay: the ray's own sorted list, or the forced one */
+            int forced;
+            const int n = gather_hits(cfg, S, o, d, tmin, &F, r, ents, &forced);
             float T = 1.0f, acc = 0.f, aux0 = 0.f;
             double T64 = 1.0, acc64 = 0.0, aux064 = 0.0;
             int nh = 0;
             for (int k = 0; k < n; k++) {
-                const float test_T = T * (1.0f - ents[k].alpha);
-                const double test_T64 = T64 * (1.0 - ents[k].alpha64);
-                if (near_thr(test_T, test_T64, (double)T_EPS) || ((test_T < T_EPS) != (test_T64 < (double)T_EPS))) frag = 1;
-                if (test_T < T_EPS) break;
-                const float w = ents[k].alpha * T;
-                const double w64 = ents[k].alpha64 * T64;
+                const rhit_t *h = &ents[k].h;
+                double t64, u64, v64, alpha64;
+                shadow64(&S64[ents[k].id], o64, d64, h->t, h->u, h->v, h->alpha, &t64, &u64, &v64, &alpha64);
+                const float test_T = T * (1.0f - h->alpha);
+                const double test_T64 = T64 * (1.0 - alpha64);
+                const int tnear = near_thr(test_T, test_T64, (double)T_EPS), tdiff = (test_T < T_EPS) != (test_T64 < (double)T_EPS);
+                if (tnear || tdiff) { frag = 1; kind |= TRC_KIND_TERM | (tdiff ? TRC_KIND_DISAGREE : 0); }
+                if (!forced && test_T < T_EPS) break;
+                const float w = h->alpha * T;
+                const double w64 = alpha64 * T64;
                 acc += w; acc64 += w64;
                 if (others) { aux0 += w * others[2 * ents[k].id]; aux064 += w64 * (double)others[2 * ents[k].id]; }
                 if (shs && cfg->M > 0) {
@@ -427,26 +534,58 @@ void trc_audit(const trc_cfg *cfg, const float *ray_o, const float *ray_d, const
                         for (int kk = 0; kk < nbas; kk++) { rr += basis[kk] * sh[kk * 3 + c]; mag += fabsf(basis[kk] * sh[kk * 3 + c]); }
                         rr += 0.5f;
                         /* rounding of a (nbas + 1)-term fp32 sum whose terms carry a few ulp themselves (basis polynomials, summation order) */
-                        if (fabsf(rr) <= (float)AUD_K * 8.0f * 1.1920929e-7f * mag) frag = 1;
+                        if (fabsf(rr) <= (float)AUD_K * 8.0f * 1.1920929e-7f * mag) { frag = 1; kind |= TRC_KIND_CLAMP; }
                     }
                 }
-                if (nh < lcap) { ids[(size_t)r * lcap + nh] = ents[k].id; union { float f; uint32_t u; } cv; cv.f = ents[k].t; tbits[(size_t)r * lcap + nh] = cv.u; }
+                if (nh < lcap) {
+                    ids[(size_t)r * lcap + nh] = ents[k].id; tbits[(size_t)r * lcap + nh] = fbits(ents[k].t);
+                    if (D.go) D.go[(size_t)r * lcap + nh] = (uint8_t)((test_T >= T_EPS ? 1 : 0) | ((tnear || tdiff) ? 2 : 0));
+                }
                 nh++;
                 T = test_T; T64 = test_T64;
             }
             if (bounce_thr >= 0.0f) {
-                if (near_thr(aux0, aux064, (double)bounce_thr) || near_thr(acc, acc64, 0.5)) frag = 1;
+                if (near_thr(aux0, aux064, (double)bounce_thr) || near_thr(acc, acc64, 0.5)) { frag = 1; kind |= TRC_KIND_BOUNCE; }
             }
             fragile[r] = (uint8_t)frag;
             nhit[r] = nh;
+            if (D.kind) D.kind[r] = (uint8_t)kind;
+            if (D.namb) D.namb[r] = namb;
+            if (D.cand_off) { D.cand_off[r] = -1; D.ncand[r] = 0; }
+            if (D.cand_off && D.pool_ids && (frag || forced)) {
+                qsort(cand, nc, sizeof(cand_t), cand_cmp);
+                int64_t off;
+#pragma omp atomic capture
+                { off = pool_used; pool_used += nc; }
+                if (off + nc <= D.pool_cap) {
+                    D.cand_off[r] = off; D.ncand[r] = nc;
+                    for (int k = 0; k < nc; k++) {
+                        int fl = cand[k].flags;
+                        if (forced) {
+                            const int behind = n == 0 || cand[k].t > ents[n - 1].t || (cand[k].t == ents[n - 1].t && cand[k].id > ents[n - 1].id);
+                            if (behind) {
+                                const float test_T = T * (1.0f - cand[k].alpha);
+                                const double test_T64 = T64 * (1.0 - cand[k].alpha64);
+                                fl |= TRC_CAND_BEHIND;
+                                if (test_T < T_EPS || test_T64 < (double)T_EPS || near_thr(test_T, test_T64, (double)T_EPS)) fl |= TRC_CAND_STOPS;
+                            }
+                        }
+                        D.pool_ids[off + k] = cand[k].id; D.pool_tbits[off + k] = fbits(cand[k].t); D.pool_alpha[off + k] = cand[k].alpha;
+                        D.pool_flags[off + k] = (uint8_t)fl;
+                    }
+                }
+            }
         }
-        free(ents);
+        free(ents); free(cand);
     }
     free(S); free(S64);
+    g_have_detail = 0;
+    clear_forced();
 }
 
 /*
- * Backward of stage 0 (max_trace_depth == 0 semantics; secondary rays are detached).
+ * Backward of ONE stage (max_trace_depth == 0 semantics: the stage the call's rays start).  A bounce chain is differentiated stage by stage,
+ * each stage a call of its own on the rays and upstream gradients the chain gave it; nothing is detached (see the header).
  * Upstream: dL_drgb (R,3) dL_ddpt (R) dL_dacc (R) dL_dnorm (R,3) dL_daux (R,2).   (dist carries no gradient here.)
  * Outputs (double, zeroed here): dmeans (P,3) dscales (P,2) drots (P,4) dopac (P) dshs (P,M,3) | dcolors (P,3),
  * dothers (P,2), dray_o (R,3), dray_d (R,3).
@@ -472,6 +611,7 @@ void trc_backward(const trc_cfg *cfg, const float *ray_o, const float *ray_d, co
      * ulp of THOSE magnitudes into each hit's gradient, so this -- not the (possibly tiny) gradient itself -- is what its error is
      * measured against (tests/util.py: condition-aware floor).  The oracle itself keeps all per-ray sums in double. */
     const int P = cfg->P, R = cfg->R, M = cfg->M;
+    const forced_t F = take_forced();
     surfel_t *S = (surfel_t *)malloc(sizeof(surfel_t) * (P ? P : 1));
     for (int i = 0; i < P; i++) make_surfel(cfg, i, means, scales, rots, opac, &S[i]);
     double *dA = (double *)calloc((size_t)3 * P + 1, sizeof(double)), *dB = (double *)calloc((size_t)3 * P + 1, sizeof(double)),
@@ -507,17 +647,16 @@ void trc_backward(const trc_cfg *cfg, const float *ray_o, const float *ray_d, co
                                if (u_c_means) { double w__ = rho * v__; _Pragma("omp atomic") u_##arr[idx] += w__; } } } while (0)
 #pragma omp parallel
     {
-        ent_t *ents = (ent_t *)malloc(sizeof(ent_t) * (P ? P : 1));
+        ent_t *ents = (ent_t *)malloc(sizeof(ent_t) * ents_cap(cfg, &F));
 #pragma omp for schedule(dynamic, 16)
         for (int r = 0; r < R; r++) {
             const float o[3] = {ray_o[3 * r], ray_o[3 * r + 1], ray_o[3 * r + 2]};
             const float d[3] = {ray_d[3 * r], ray_d[3 * r + 1], ray_d[3 * r + 2]};
             const float tmin = first_tmin(cfg->start_from_first);
             stage_t fin;
-            trace_stage(cfg, S, shs, colors_precomp, others, bg, o, d, tmin, ents, &fin, NULL);   /* final sums; ents sorted */
-            int n = 0;
-            for (int i = 0; i < P; i++) { rhit_t h; if (hit_surfel(&S[i], o, d, tmin, &h)) { ents[n].t = h.t; ents[n].id = i; ents[n].h = h; n++; } }
-            qsort(ents, n, sizeof(ent_t), ent_cmp);
+            trace_stage(cfg, S, shs, colors_precomp, others, bg, o, d, tmin, &F, r, ents, &fin, NULL);   /* final sums */
+            int forced;
+            const int n = gather_hits(cfg, S, o, d, tmin, &F, r, ents, &forced);
             const float dl2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2], dl = sqrtf(dl2);
             const float dir[3] = {d[0] / dl, d[1] / dl, d[2] / dl};
             float basis[16], bgx[16], bgy[16], bgz[16];
@@ -538,7 +677,7 @@ void trc_backward(const trc_cfg *cfg, const float *ray_o, const float *ray_d, co
                     const rhit_t *h = &ents[k].h;
                     const int g = ents[k].id;
                     const float tt = Tt * (1.0f - h->alpha);
-                    if (tt < T_EPS) break;
+                    if (!forced && tt < T_EPS) break;
                     const double w = (double)(h->alpha * Tt);
                     float col[3]; int cl[3];
                     surfel_color(cfg, g, shs, colors_precomp, basis, col, cl);
@@ -560,7 +699,7 @@ void trc_backward(const trc_cfg *cfg, const float *ray_o, const float *ray_d, co
                 const surfel_t *s = &S[g];
                 const float alpha = h->alpha;
                 const float test_T = T * (1.0f - alpha);
-                if (test_T < T_EPS) break;
+                if (!forced && test_T < T_EPS) break;
                 const float w = alpha * T;
                 if (S64) {
                     const surfel64_t *z = &S64[g];
@@ -712,4 +851,5 @@ void trc_backward(const trc_cfg *cfg, const float *ray_o, const float *ray_d, co
     free(dA); free(dB); free(dN); free(S);
     if (cA_) { free(cA_); free(cB_); free(cN_); }
     if (u_cA_) { free(u_cA_); free(u_cB_); free(u_cN_); free(S64); }
+    clear_forced();
 }

@@ -2,10 +2,12 @@
 
 Bar (BASELINE.json north_star): bit-exact index work, <= 1e-4 on values and gradients -- applied per ELEMENT (tests/util.py:check_close).
 Threshold / ordering flips are separated from arithmetic error instead of being absorbed by a tolerance: the oracle's audit
-(oracle/surfel_trace_oracle.c:trc_audit) marks the rays whose hit set or hit ORDER is not determined beyond rounding noise; those rays are
-removed from the test input (a ray's result does not depend on the other rays), counted, and then on every remaining ray
-  * the sorted per-ray hit-id list the GPU composited must equal the brute-force list bit for bit (index parity),
-  * every output, the per-surfel weights and every gradient must be within 1e-4 elementwise."""
+(oracle/surfel_trace_oracle.c:trc_audit) marks the FRAGILE rays, whose hit set or termination hangs on a threshold inside fp32 noise.  Every ray is
+traced, and then
+  * on a non-fragile ray the sorted per-ray hit-id list the GPU composited must equal the brute-force list bit for bit (index parity),
+  * on a fragile ray that list may differ from brute force only in decisions the audit itself marks ambiguous (tests/trace_lists.py:
+    validate_gpu_list), and the oracle replays the GPU's list (oracle/trace.py: forced=),
+  * every output, the per-surfel weights and every gradient must be within 1e-4 elementwise, fragile rays included (_parity)."""
 import math
 
 import numpy as np
@@ -14,7 +16,8 @@ import torch
 
 from envgs_amd import synth
 from tests.test_oracle_trace import trace_scene, FRAME_ROUND_TRIP
-from tests.util import check_close, record, record_fragile, FRAGILE_RAYS_MAX
+from tests.trace_lists import validate_gpu_list, replay_rows, fragile_scene
+from tests.util import check_close, record, record_fragile, FRAGILE_RAYS_MAX, CLAMP_RAYS_MAX
 
 pytestmark = pytest.mark.gpu
 
@@ -33,6 +36,13 @@ def _run_hip(g, ro, rd, bg, deg, use_sh, sff, grads=None, depth=0, thr=0.0, shap
     ABOVE 1 over unmodified quads, is not asserted anywhere: the quads are then smaller than the modified surfels, so whatever part of a surfel's
     3-sigma extent lies outside its quad is not found by the traversal and the image differs from the brute-force oracle's; the reference's extension
     sources are not available to say that it does otherwise."""
+    ctx = _hip_forward(g, ro, rd, bg, deg, use_sh, sff, depth=depth, thr=thr, shape=shape, others=others, scale_modifier=scale_modifier, quad_modifier=quad_modifier)
+    return _hip_backward(ctx, grads)
+
+
+def _hip_forward(g, ro, rd, bg, deg, use_sh, sff, depth=0, thr=0.0, shape=None, others=True, scale_modifier=1.0, quad_modifier=None):
+    """The forward half of _run_hip: (outs, L, o, d, g3), synchronised -- the hit lists can be read (tracing.last_hit_lists) before the upstream gradients
+    of _hip_backward are chosen."""
     import diff_surfel_tracing as mod
     dev = torch.device("cuda:0")
     L = {k: g[k].to(dev).requires_grad_(True) for k in ("means3D", "scales", "rotations", "opacities")}
@@ -49,9 +59,17 @@ def _run_hip(g, ro, rd, bg, deg, use_sh, sff, grads=None, depth=0, thr=0.0, shap
     outs = tracer(oo, dd, v, means3D=L["means3D"], grads3D=g3, shs=L.get("shs"), colors_precomp=L.get("colors_precomp"),
                   others_precomp=L.get("others"), opacities=L["opacities"], scales=L["scales"], rotations=L["rotations"],
                   cov3D_precomp=None, tracer_settings=_settings(mod, bg, deg, dev, depth, thr, scale_modifier=scale_modifier), start_from_first=sff)
+    torch.cuda.synchronize()
+    return outs, L, o, d, g3
+
+
+def _hip_backward(ctx, grads=None):
+    """The backward half: <outputs, grads> backpropagated (grads None: nothing); returns the forward's tuple."""
+    outs, L, o, d, g3 = ctx
+    dev = o.device
     if grads is not None:
         rgb, dpt, acc, norm, dist, aux, mid, wet = outs
-        R = ro.shape[0]
+        R = o.shape[0]
         loss = sum((x.reshape(R, -1) * y.to(dev).reshape(R, -1)).sum() for x, y in zip((rgb, dpt, acc, norm, aux), grads))
         loss.backward()
     torch.cuda.synchronize()
@@ -74,37 +92,89 @@ def _drop_fragile(test, g, ro, rd, sff, others=True, max_frac=FRAGILE_RAYS_MAX, 
     return ro[k].contiguous(), rd[k].contiguous(), (a["ids"][keep], a["tbits"][keep]), a["nhit"][keep], int(a["fragile"].sum())
 
 
-def _check_index_parity(test, ids_ref, nhit_ref, require_lists=True):
-    """Index work is bit-exact: the GPU's sorted, composited hit-id list of every ray served by the list path == the brute-force list."""
-    from envgs_amd import tracing
-    L = tracing.last_hit_lists()
-    if L is None:
-        assert not require_lists, "the list path did not run"
+def _check_index_parity(test, ids_ref, nhit_ref, lists, rays=None):
+    """Index work is bit-exact: the GPU's sorted, composited hit-id list of every ray served by the list path == the brute-force list.
+    lists: _read_lists(); rays: the (non-fragile) rays to compare, default all."""
+    if lists is None:
         return 0
-    ids, tb, n_used, hit_cnt = [x.cpu().numpy() for x in L]
+    ids, tb, n_used, hit_cnt = lists
     ids_ref, _ = ids_ref
     cap = ids.shape[1]
-    listed = hit_cnt <= cap
+    served = hit_cnt <= cap
+    listed = served if rays is None else served & rays
     np.testing.assert_array_equal(n_used[listed], nhit_ref[listed])
     valid = (np.arange(cap)[None] < n_used[:, None])[listed]
     w = min(cap, ids_ref.shape[1])
     assert nhit_ref[listed].max(initial=0) <= w
-    np.testing.assert_array_equal(np.where(valid, ids[listed], -1)[:, :w], ids_ref[listed][:, :w])                    # the same surfels, in the same order
+    np.testing.assert_array_equal(np.where(valid, ids[listed], -1)[:, :w], ids_ref[:, :w][listed])                    # the same surfels, in the same order
     # (word 0 of a list entry holds the hit distance only until the composite pass replaces it by the blend weight, so the distances
     #  themselves are not comparable here; identical ORDER of identical ids for every ray is what their bit-exactness buys)
     record(test, "hit_lists_bit_exact", 0.0, "(%d rays, %d composited (t, id) pairs compared)" % (int(listed.sum()), int(n_used[listed].sum())))
-    return int(listed.sum())
+    return int(served.sum())
 
 
 GRADS_ALL = ("dmeans3D", "grads3D", "dscales", "drots", "dopacities", "dothers", "dcolor", "dray_o", "dray_d")
 
 
+def _read_lists():
+    """The kept hit lists of the most recent forward as numpy, or None when the list path did not run."""
+    from envgs_amd import tracing
+    L = tracing.last_hit_lists()
+    return None if L is None else [x.cpu().numpy() for x in L]
+
+
+def _audit_fragile_lists(test, a, lists, g, ro, rd, sff, others, sh_degree, scale_modifier):
+    """Steps 4 of _parity: every fragile ray the GPU served from a list is validated against the audit's candidates and ambiguous set (a rejected list
+    is a kernel bug: ListRejected names the ray and both lists).  Returns (forced = (ids, n, mask) over all rays, left_out (R,) bool, kinds (R,) u8
+    = the audit's kinds of the natural list or-ed with those of the replay under the GPU's list, number of ambiguous decisions taken differently)."""
+    R = ro.shape[0]
+    frag = a["fragile"]
+    kinds = a["kind"].copy()
+    left_out = np.zeros(R, bool)
+    if lists is None:
+        return None, frag.copy(), kinds, 0
+    ids, tb, n_used, hit_cnt = lists
+    cap = ids.shape[1]
+    listed = hit_cnt <= cap
+    have = np.array([c is not None for c in a["cand"]])
+    val = frag & listed & ~a["amb_overflow"] & have
+    left_out = frag & ~val
+    fr = np.nonzero(val)[0]
+    flipped = 0
+    if fr.size:
+        gl = [[int(x) for x in ids[r, :n_used[r]]] for r in fr]
+        rows, a2 = replay_rows((ro.numpy()[fr], rd.numpy()[fr]), gl, (_np(g, "means3D"), _np(g, "scales"), _np(g, "rotations"), _np(g, "opacities")),
+                               others=_np(g, "others") if others else None, start_from_first=sff, scale_modifier=scale_modifier,
+                               shs=(g["shs"].float().numpy() if sh_degree is not None else None), sh_degree=(sh_degree or 0))
+        for r, row, G in zip(fr, rows, gl):
+            flipped += validate_gpu_list(row, G, ray=int(r))
+        kinds[fr] |= a2["kind"]
+    f_ids = np.where(np.arange(cap)[None] < n_used[:, None], ids, -1).astype(np.int32)
+    record(test, "fragile.lists_validated", float(fr.size), "(fragile rays served from a list, each list legitimate under the audit's ambiguous decisions; %d such "
+           "decisions taken differently from the float oracle)" % flipped)
+    return (f_ids, n_used.astype(np.int32), val), left_out, kinds, flipped
+
+
 def _parity(test, g, ro, rd, bg, deg, use_sh, sff, gr_scale=1.0, seed=9, which=GRADS_ALL, others=True, hip_ctx=None, require_lists=True,
-            zero_geo_grads=False, after_hip=None, scale_modifier=1.0, quad_modifier=None):
-    """Audit -> drop fragile rays -> HIP forward + backward -> oracle forward + backward -> index parity + the 1e-4 contract."""
+            zero_geo_grads=False, after_hip=None, scale_modifier=1.0, quad_modifier=None, all_listed=False):
+    """Audit -> HIP forward on ALL rays -> index parity (non-fragile rays) and list validation (fragile rays) -> HIP backward -> oracle forward + backward
+    with the fragile rays forced to the GPU's validated lists -> the 1e-4 contract on every output and gradient, fragile rays included.
+
+    Two kinds of ray cannot be fully replayed; their upstream gradients are zeroed on both sides before the backward:
+      * colour-clamp-fragile rays (a blended SH colour channel within rounding of zero: the clamp decision is in no list and flips that hit's whole SH
+        gradient): dL_drgb only; everything else of the ray, its forward rgb included, is compared.  At most CLAMP_RAYS_MAX of the rays.
+      * left-out rays (fragile, and served by the K-buffer kernels, so that there is no list to read -- or with more ambiguous surfels than the audit
+        keeps): every upstream gradient; their forward values are not compared, and `wet` only over the surfels outside their candidate sets.  Exactly 0
+        where every ray is list-served (all_listed=True asserts that they are); at most FRAGILE_RAYS_MAX where a test exceeds the list capacity.
+    The fragile rays' own rows are also recorded apart (`fragile.<tensor>`; for a per-surfel tensor: the surfels the fragile rays composited)."""
     from oracle import trace as otr
     from envgs_amd import tracing
-    ro, rd, ids_ref, nhit_ref, nfr = _drop_fragile(test, g, ro, rd, sff, others=others, sh_degree=(deg if use_sh else None), scale_modifier=scale_modifier)
+    sh_degree = deg if use_sh else None
+    a = otr.trace_audit(ro.numpy(), rd.numpy(), _np(g, "means3D"), _np(g, "scales"), _np(g, "rotations"), _np(g, "opacities"),
+                        others=_np(g, "others") if others else None, start_from_first=sff, scale_modifier=scale_modifier,
+                        shs=(g["shs"].float().numpy() if use_sh else None), sh_degree=(sh_degree or 0), detail=True)
+    frag = a["fragile"]
+    nfr = int(frag.sum())
     R = ro.shape[0]
     gen = torch.Generator().manual_seed(seed)
     gr = [torch.randn(R, 3, generator=gen) * gr_scale, torch.randn(R, generator=gen) * gr_scale, torch.randn(R, generator=gen) * gr_scale,
@@ -116,10 +186,26 @@ def _parity(test, g, ro, rd, bg, deg, use_sh, sff, gr_scale=1.0, seed=9, which=G
     try:
         if hip_ctx is not None: hip_ctx.__enter__()
         try:
-            outs, L, o, d, g3 = _run_hip(g, ro, rd, bg, deg, use_sh, sff, grads=gr, others=others, scale_modifier=scale_modifier, quad_modifier=quad_modifier)
+            ctx = _hip_forward(g, ro, rd, bg, deg, use_sh, sff, others=others, scale_modifier=scale_modifier, quad_modifier=quad_modifier)
+            lists = _read_lists()
+            assert lists is not None or not require_lists, "the list path did not run"
+            n_listed = _check_index_parity(test, (a["ids"], a["tbits"]), a["nhit"], lists, ~frag)
+            forced, left_out, kinds, flipped = _audit_fragile_lists(test, a, lists, g, ro, rd, sff, others, sh_degree, scale_modifier)
+            every_ray_listed = lists is not None and bool(np.all(lists[3] <= lists[0].shape[1]))
+            assert every_ray_listed or not all_listed, "a ray was not served by the list path"
+            clamp = ((kinds & otr.KIND_CLAMP) != 0) & ~left_out
+            record(test, "fragile_rays", float(frag.mean()) if R else 0.0, "(%d of %d rays are fragile: traced, validated and compared with the others)" % (nfr, R))
+            record_fragile(test, "fragile_rays.rgb_gradient_zeroed", clamp, CLAMP_RAYS_MAX, "(colour-clamp-fragile rays)")
+            record_fragile(test, "fragile_rays.left_out", left_out, 0.0 if every_ray_listed else FRAGILE_RAYS_MAX,
+                           "(fragile rays without a list or with an overflowed ambiguous set)")
+            if clamp.any() or left_out.any():
+                gr = [x.clone() for x in gr]
+                gr[0][torch.from_numpy(clamp | left_out)] = 0
+                for x in gr[1:]:
+                    x[torch.from_numpy(left_out)] = 0
+            outs, L, o, d, g3 = _hip_backward(ctx, gr)
             cnt = tracing.last_trace_counts()
             extra = after_hip() if after_hip is not None else None
-            n_listed = _check_index_parity(test, ids_ref, nhit_ref, require_lists=require_lists)
         finally:
             if hip_ctx is not None: hip_ctx.__exit__(None, None, None)
     finally:
@@ -128,15 +214,35 @@ def _parity(test, g, ro, rd, bg, deg, use_sh, sff, gr_scale=1.0, seed=9, which=G
     rgb, dpt, acc, norm, dist, aux, mid, wet = [x.detach().cpu().numpy() for x in outs]
     ckw = dict(shs=_np(g, "shs"), sh_degree=deg) if use_sh else dict(colors_precomp=_np(g, "colors_precomp"))
     ref = otr.trace_forward(ro.numpy(), rd.numpy(), _np(g, "means3D"), _np(g, "scales"), _np(g, "rotations"), _np(g, "opacities"),
-                            others=_np(g, "others") if others else None, bg=bg.numpy(), start_from_first=sff, scale_modifier=scale_modifier, **ckw)
-    np.testing.assert_array_equal(ref["nhits"], nhit_ref)
-    for a, b, nm in ((rgb, ref["rgb"], "rgb"), (dpt[:, 0], ref["dpt"], "dpt"), (acc[:, 0], ref["acc"], "acc"), (norm, ref["norm"], "norm"),
+                            others=_np(g, "others") if others else None, bg=bg.numpy(), start_from_first=sff, scale_modifier=scale_modifier, forced=forced, **ckw)
+    np.testing.assert_array_equal(ref["nhits"][~frag], a["nhit"][~frag])
+    fv = forced[2] if forced is not None else np.zeros(R, bool)                 # the fragile rays that were validated and replayed
+    np.testing.assert_array_equal(ref["nhits"][fv], forced[1][fv] if forced is not None else [])
+    keep = ~left_out
+    P = g["means3D"].shape[0]
+    keep_p = np.ones(P, bool)                                                     # wet: not over the candidate surfels of the left-out rays
+    for r in np.nonzero(left_out)[0]:
+        assert a["cand"][r] is not None, "the audit kept no candidates for the left-out ray %d" % r
+        keep_p[a["cand"][r]["ids"]] = False
+    frag_p = np.zeros(P, bool)                                                    # the surfels the replayed fragile rays composited
+    for r in np.nonzero(fv)[0]:
+        frag_p[forced[0][r, :forced[1][r]]] = True
+    nlo = int(left_out.sum())
+
+    def close(nm, x, y, per_ray, **kw):
+        """The contract on a tensor (left-out rays / their surfels apart), and once more on the fragile rays' own rows."""
+        k_all, k_fr = (keep, fv) if per_ray else (keep_p if nm == "wet" else None, frag_p)
+        check_close(test, nm, x, y, keep=k_all, excluded=nlo, **kw)
+        if k_fr.any():
+            check_close(test, "fragile." + nm, x, y, keep=k_fr, **kw)
+
+    for x, y, nm in ((rgb, ref["rgb"], "rgb"), (dpt[:, 0], ref["dpt"], "dpt"), (acc[:, 0], ref["acc"], "acc"), (norm, ref["norm"], "norm"),
                      (aux, ref["aux"], "aux"), (wet[:, 0], ref["wet"], "wet")):
         if nm == "aux" and not others: continue
-        check_close(test, nm, a, b, excluded=nfr)
+        close(nm, x, y, nm != "wet")
     # distortion cancels catastrophically in fp32 in any implementation of its moment form: compared with the oracle's evaluation in DOUBLE under the
     # DERIVED per-ray bound of that form's fp32 rounding (oracle/surfel_trace_oracle.c: dist64 / distb; round 6, VERDICT r5 item 6a) -- no mean-acc floor
-    check_close(test, "dist", dist[:, 0], ref["dist64"], excluded=nfr, cond=np.zeros_like(ref["dist_bound"]), unc=ref["dist_bound"], k_unc=1.0)
+    close("dist", dist[:, 0], ref["dist64"], True, cond=np.zeros_like(ref["dist_bound"]), unc=ref["dist_bound"], k_unc=1.0)
     np.testing.assert_array_equal(mid[:, 0:3], ro.numpy())
     check_close(test, "mid.rgb", mid[:, 13:16], rgb, tol=1e-6)
 
@@ -153,8 +259,13 @@ def _parity(test, g, ro, rd, bg, deg, use_sh, sff, gr_scale=1.0, seed=9, which=G
                 dothers=rb["dothers"], dcolor=(rb["dshs"] if use_sh else rb["dcolors"]), dray_o=rb["dray_o"], dray_d=rb["dray_d"])
     for k in which:
         if got[k] is None or want[k] is None: continue
-        check_close(test, k, got[k].cpu().numpy(), want[k], excluded=nfr, cond=cond[k], unc=unc[k])
-    return dict(ref=ref, rb=rb, cnt=cnt, outs=outs, n_listed=n_listed, R=R, extra=extra, got=got, inputs=(ro, rd, gr))
+        # (the left-out rays carry no upstream gradient on either side: every element of every gradient is compared)
+        check_close(test, k, got[k].cpu().numpy(), want[k], excluded=nlo, cond=cond[k], unc=unc[k])
+        k_fr = fv if k in ("dray_o", "dray_d") else frag_p
+        if k_fr.any():
+            check_close(test, "fragile." + k, got[k].cpu().numpy(), want[k], keep=k_fr, cond=cond[k], unc=unc[k])
+    return dict(ref=ref, rb=rb, cnt=cnt, outs=outs, n_listed=n_listed, R=R, extra=extra, got=got, inputs=(ro, rd, gr), audit=a, kinds=kinds,
+                validated=fv, left_out=left_out, flipped=flipped)
 
 
 _FB_CASES = [(True, True, 3, 150, 400), (False, False, 0, 150, 400), (True, False, 2, 2000, 1024), (True, False, 1, 1, 64), (False, True, 0, 40, 130)]
@@ -171,7 +282,8 @@ def test_trace_forward_backward_vs_oracle(use_sh, camera, deg, P, R, scale_modif
     g, ro, rd = trace_scene(P=P, R=R, seed=7, camera=camera)
     if P > 500:
         g["scales"] = g["scales"] * 0.35                       # many small surfels: deep tree, > K hits per ray for some
-    res = _parity(request.node.name, g, ro, rd, torch.tensor([0.3, 0.1, 0.7]), deg, use_sh, camera, scale_modifier=scale_modifier, quad_modifier=quad_modifier)
+    res = _parity(request.node.name, g, ro, rd, torch.tensor([0.3, 0.1, 0.7]), deg, use_sh, camera, scale_modifier=scale_modifier, quad_modifier=quad_modifier,
+                  all_listed=True)
     if P > 1: assert res["ref"]["nhits"].mean() > 1
 
 
@@ -387,8 +499,8 @@ def test_trace_cov3D_precomp_matches_scales_rotations(scale_modifier):
     from the RECOVERED normal, whose fp32 rounding (asserted: quaternion within FRAME_ROUND_TRIP) exchanged two hits of that ray that are equally far away.
     No model of that noise removes rays here.  At a modifier other than 1 the rays the oracle's audit marks are dropped as everywhere else; of the others,
     the two calls' composited hit lists are compared ray by ray.  Rays with identical lists meet the bounds this test always had (the upstream gradient
-    is zero on the others, in both calls).  A ray whose lists differ must differ ONLY by what the rounding of the frame can decide, as in
-    test_fragile_rays_differ_from_the_oracle_by_threshold_hits_only: a symmetric difference of at most 2 entries (threshold hits), nothing listed twice,
+    is zero on the others, in both calls).  A ray whose lists differ must differ ONLY by what the rounding of the frame can decide (two GPU
+    runs are compared here, so there is no audit row to validate a list against): a symmetric difference of at most 2 entries (threshold hits), nothing listed twice,
     and every pair of common surfels that the two lists order differently must be equally far away within the distance error of a normal that is off
     by 4 FRAME_ROUND_TRIP (|dn| <= 4 |dq| for a unit quaternion):  |t_i - t_j| <= dt_i + dt_j,  dt = 4 FRAME_ROUND_TRIP (|mu - o| + |t| |d|) / |n.d|, in
     float64.  A ray that differs by threshold hits alone (same order) also has a colour within exp(-4.5) * cmax of the frame path's: the largest blend
@@ -564,7 +676,11 @@ def test_trace_baseline_size_env_set_sample_vs_oracle():
                   which=("dmeans3D", "dscales", "drots", "dopacities", "dcolor", "dray_o", "dray_d"))
     cnt = res["cnt"]
     assert cnt["hits"] / res["R"] > 30 and cnt["max_list"] > 100            # a fog: long lists
-    assert int(res["ref"]["nhits"].sum()) == cnt["hits"]                     # the same composited hits, exactly
+    lo = res["left_out"]                                                     # (fragile rays the K-buffer kernels served: no list to replay)
+    if not lo.any():
+        assert int(res["ref"]["nhits"].sum()) == cnt["hits"]                 # the same composited hits, exactly (fragile rays: under the GPU's validated lists)
+    else:                                                                    # ... up to the ambiguous decisions (and the termination) of the left-out rays
+        assert abs(int(res["ref"]["nhits"].sum()) - cnt["hits"]) <= int((res["audit"]["namb"][lo] + 1).sum())
 
 
 def test_trace_clustered_surfels_deep_tree():
@@ -587,67 +703,32 @@ def test_trace_clustered_surfels_deep_tree():
     rd = tgt - ro; rd = rd / rd.norm(dim=-1, keepdim=True)
     res = _parity("clustered_deep_tree", g, ro, rd, torch.tensor([0.2, 0.2, 0.2]), 2, True, False, seed=22,
                   which=("dmeans3D", "dopacities", "dcolor", "dray_d"))
+    # (not all_listed: a ray through the cluster FINDS more than the 512 hits a fresh tracer's lists hold, although it composites ~200 of them -- on
+    #  the MI355X 510 of the 512 rays are served by the K-buffer kernels, so a fragile ray here has no list to replay and is left out under
+    #  FRAGILE_RAYS_MAX; the same kind of cluster with lists long enough for every ray is test_fragile_rays_differ_from_the_oracle_by_threshold_hits_only)
     assert res["ref"]["nhits"].max() > 200
 
 
 def test_fragile_rays_differ_from_the_oracle_by_threshold_hits_only():
-    """up to a few percent of the rays of the deep-list cases are audited OUT of the comparisons (a decided quantity within fp32
-    noise of its threshold).  Here they are traced WITH the others and what they do is asserted: a fragile ray's composited list may differ from
-    the brute-force list only by hits AT a threshold -- the symmetric difference of the two id lists is at most 2 entries (one alpha >= 1/255 or
-    |u|,|v| <= 3 decision, or the terminating hit and the one behind it), the common surfels are in the same order, and its outputs stay within
-    1e-3 of the oracle's (a flipped threshold hit carries a blend weight of that order at most; measured 1.2e-5).  An ordering bug, or a dropped / duplicated hit, fails this
-    on exactly the rays the other tests exclude."""
+    """The deep-list scene (P = 1200, R = 4096, ~207 composited hits per ray, up to 438): about 1 % of its rays have a decision within fp32 noise of its
+    threshold -- exactly the deep-list rays, where sorting, merging and termination are hardest.  They are traced WITH the others, and through
+    _parity's machinery each one's composited list must pass tests/trace_lists.py:validate_gpu_list (no id twice, only candidates of the ray, in
+    (t, id) order, no unambiguous hit skipped, going on and stopping legitimate at the thresholds the audit marks), and under that list the oracle's
+    replay must match every output and EVERY gradient at the 1e-4 contract -- the `fragile.*` rows.  An ordering bug, a dropped or duplicated hit or a
+    wrong gradient on a near-threshold ray fails here.  Every ray is list-served (1024-entry lists), so nothing may be left out."""
     from oracle import trace as otr
-    from envgs_amd import tracing
     test = "fragile_rays_included"
-    gen = torch.Generator().manual_seed(21)
-    Pc, Pf = 1000, 200                    # (lists of ~200, up to ~440 composited hits: within the 1024-entry list capacity, so the fragile rays ARE list-served)
-    means = torch.cat([torch.tensor([0.0, 0.0, 5.0]) + 0.02 * torch.randn(Pc, 3, generator=gen), (torch.rand(Pf, 3, generator=gen) * 2 - 1) * 30])
-    P = Pc + Pf
-    scales = torch.cat([0.3 + 0.3 * torch.rand(Pc, 2, generator=gen), 2 + 2 * torch.rand(Pf, 2, generator=gen)])
-    q = torch.randn(P, 4, generator=gen)
-    g = dict(means3D=means, scales=scales, rotations=q / q.norm(dim=-1, keepdim=True), opacities=torch.sigmoid(torch.randn(P, 1, generator=gen) - 2.5),
-             shs=torch.randn(P, 16, 3, generator=gen) * 0.3, others=torch.rand(P, 2, generator=gen))
-    R = 4096
-    ro = torch.randn(R, 3, generator=gen) * 0.2
-    tgt = torch.tensor([0.0, 0.0, 5.0]) + 0.3 * torch.randn(R, 3, generator=gen)
-    rd = tgt - ro; rd = rd / rd.norm(dim=-1, keepdim=True)
-    bg = torch.tensor([0.2, 0.2, 0.2])
-    a = otr.trace_audit(ro.numpy(), rd.numpy(), _np(g, "means3D"), _np(g, "scales"), _np(g, "rotations"), _np(g, "opacities"), others=_np(g, "others"),
-                        start_from_first=False, shs=g["shs"].numpy(), sh_degree=2)
-    frag = a["fragile"]
-    record_fragile(test, "fragile_rays", frag, FRAGILE_RAYS_MAX)
-    assert int(frag.sum()) >= 8, "the scene is meant to have fragile rays"
-    old_keep = tracing.KEEP_LISTS["on"]
-    tracing.KEEP_LISTS["on"] = True
-    try:
-        with _Switch(force_cap=1024, rows_per_ray=1024):         # (a fresh tracer's first call would use 512-entry lists and 192 rows per ray)
-            outs, L, o, d, g3 = _run_hip(g, ro, rd, bg, 2, True, False)
-            ids, tb, n_used, hit_cnt = [x.cpu().numpy() for x in tracing.last_hit_lists()]
-    finally:
-        tracing.KEEP_LISTS["on"] = old_keep
-    ref = otr.trace_forward(ro.numpy(), rd.numpy(), _np(g, "means3D"), _np(g, "scales"), _np(g, "rotations"), _np(g, "opacities"), others=_np(g, "others"),
-                            bg=bg.numpy(), start_from_first=False, shs=g["shs"].numpy(), sh_degree=2)
-    cap = ids.shape[1]
-    worst, checked, identical = 0, 0, 0
-    for r in np.nonzero(frag)[0]:
-        if hit_cnt[r] > cap:
-            continue                                            # (served by the K-buffer kernels: no list to look at)
-        mine = [int(x) for x in ids[r, :n_used[r]]]
-        theirs = [int(x) for x in a["ids"][r, :a["nhit"][r]]]
-        sd = set(mine) ^ set(theirs)
-        worst = max(worst, len(sd))
-        common_m = [x for x in mine if x not in sd]; common_t = [x for x in theirs if x not in sd]
-        assert common_m == common_t, "fragile ray %d: the common surfels are ordered differently" % r
-        assert len(mine) == len(set(mine)), "fragile ray %d: a surfel is listed twice" % r
-        identical += int(not sd)
-        checked += 1
-    assert checked >= 8 and worst <= 2, "a fragile ray differs from the brute-force list by %d entries" % worst
-    record(test, "fragile_lists_max_symmetric_difference", float(worst), "(%d fragile rays on the list path, %d of them identical to the brute-force list; bound 2 entries)" % (checked, identical))
-    rgb, dpt, acc, norm, dist, aux, mid, wet = [x.detach().cpu().numpy() for x in outs]
-    for nm, hip, orc in (("rgb", rgb, ref["rgb"]), ("acc", acc[:, 0], ref["acc"]), ("dpt", dpt[:, 0], ref["dpt"]), ("norm", norm, ref["norm"]), ("aux", aux, ref["aux"])):
-        check_close(test, "fragile." + nm, hip[frag], orc[frag], tol=1e-3)
-        check_close(test, "others." + nm, hip[~frag], orc[~frag])                      # (and the rest of the SAME launch meets the contract)
+    g, ro, rd, bg, deg = fragile_scene()
+    g["colors_precomp"] = torch.rand(g["means3D"].shape[0], 3, generator=torch.Generator().manual_seed(1))
+    # (a fresh tracer's first call would use 512-entry lists and 192 rows per ray)
+    res = _parity(test, g, ro, rd, bg, deg, True, False, seed=22, hip_ctx=_Switch(force_cap=1024, rows_per_ray=1024), all_listed=True)
+    kinds, val = res["kinds"], res["validated"]
+    n_geo = int((((kinds & (otr.KIND_GEOM | otr.KIND_DISAGREE)) != 0) & val).sum()); n_term = int((((kinds & otr.KIND_TERM) != 0) & val).sum())
+    record(test, "fragile.validated_by_kind", float(val.sum()), "(%d geometry / alpha, %d termination, %d colour clamp; %d ambiguous decisions taken differently)" % (
+        n_geo, n_term, int((((kinds & otr.KIND_CLAMP) != 0) & val).sum()), res["flipped"]))
+    assert not res["left_out"].any()
+    assert int(val.sum()) >= 8 and n_geo >= 1 and n_term >= 1, "the scene is meant to have list-served fragile rays of geometry and of termination kind"
+    assert res["ref"]["nhits"].max() > 400
 
 
 @pytest.mark.parametrize("sort_rays", [True, False])
@@ -1008,8 +1089,12 @@ def test_trace_very_long_lists(force_cap, request):
     means = torch.stack([torch.randn(P, generator=gen) * 0.15, torch.randn(P, generator=gen) * 0.15, 2.0 + torch.arange(P) * 0.01], dim=1)
     q = torch.tensor([1.0, 0, 0, 0]).expand(P, 4) + torch.randn(P, 4, generator=gen) * 0.05
     g = dict(means3D=means, scales=torch.full((P, 2), 0.3) + 0.3 * torch.rand(P, 2, generator=gen), rotations=q / q.norm(dim=-1, keepdim=True),
-             opacities=0.02 + 0.04 * torch.rand(P, 1, generator=gen), shs=torch.randn(P, 16, 3, generator=gen) * 0.3,
+             opacities=0.02 + 0.04 * torch.rand(P, 1, generator=gen), shs=torch.randn(P, 16, 3, generator=gen) * 0.2,
              others=torch.rand(P, 2, generator=gen))
+    # (SH coefficients of 0.2, not 0.3 as in the other scenes: a ray blends ~460 hits here, and with colours 0.5 +- 0.27 one ray in fifty -- 4 of these
+    #  192 by the oracle's audit alone -- has a blended colour channel within rounding of the clamp at zero, twice the share of rays whose dL/drgb _parity
+    #  may zero (CLAMP_RAYS_MAX).  This test is about the sort / composite pass of long lists; the clamp on deep lists is covered by the 4096 rays of
+    #  test_fragile_rays_differ_from_the_oracle_by_threshold_hits_only.)
     # rays through the middle of the stack terminate after a few hundred hits, rays near its rim see falloffs below 1/255: 14 .. 712 hits
     ro = torch.cat([(torch.rand(R, 2, generator=gen) - 0.5) * 1.6, torch.zeros(R, 1)], dim=1)
     rd = torch.cat([torch.randn(R, 2, generator=gen) * 0.03, torch.ones(R, 1)], dim=1)

@@ -118,8 +118,8 @@ def assert_close_frac(a, b, tol, max_bad_frac=1e-4, flip_bound=None, what=""):
 #              19 305 of 900 000 position-gradient elements are beyond 1e-4 without the unc term, 393 with K_UNC = 1, 33 with 4, 6 with 16.
 #              A last floor of 1e-2 * mean|b| (absolute error below 1e-6 of the tensor's typical magnitude) covers the rounding of the
 #              per-surfel chain R8 itself (e.g. an SH basis function near one of its zeros), which neither cond nor unc sees.
-# NO element may exceed the tolerance: threshold flips are not absorbed here, they are separated beforehand by the oracle's audit (fragile pixels / rays are
-# excluded from the comparison -- and counted).  Every comparison is recorded and printed at the end of the pytest run
+# NO element may exceed the tolerance: threshold flips are not absorbed here, they are separated beforehand by the oracle's audit (fragile pixels are
+# excluded from the comparison -- and counted; fragile RAYS are compared under the GPU's own validated decisions, see FRAGILE_RAYS_MAX below).  Every comparison is recorded and printed at the end of the pytest run
 # (tests/conftest.py), so the measured errors are part of the GPU test log.
 TOL = 1e-4
 KAPPA = 0.02
@@ -128,10 +128,19 @@ K_UNC = 1.0     # rounds 1-3: 16 (plus, at full size, a tail allowance); round 4
                 # measured for every comparison of the suite.  Round 6: the comparisons whose `unc` is an a-priori bound rather than a realised error
                 # (test_raster_parity.py: sparse_distortion_gradient, a one-ulp bound, k_unc=16 until round 5; the distortion maps under the derived
                 # fp32 bound of their moment form) are asserted at K_UNC = 1 too -- no comparison of the suite uses a larger multiple.
-FRAGILE_PX_MAX = 2e-3       # stated bounds on what the oracle's audit may exclude from a comparison (fail, do not only count): pixels whose
-FRAGILE_RAYS_MAX = 4e-2     # outcome hangs on a threshold inside fp32 noise (measured: <= 7.2e-4 of the pixels, <= 3.3e-2 of the rays of the deep-list cases;
-                            # round 6: 5e-2 -> 4e-2 = the measured maximum + margin, and what the excluded rays do is asserted too:
-                            # tests/test_trace_parity.py::test_fragile_rays_differ_from_the_oracle_by_threshold_hits_only)
+# Stated bounds on what the oracle's audits may take out of a comparison (fail, do not only count):
+FRAGILE_PX_MAX = 2e-3       # rasterizer: the share of PIXELS whose outcome hangs on a threshold inside fp32 noise and that are excluded from a comparison
+                            # (measured: <= 7.2e-4).
+FRAGILE_RAYS_MAX = 4e-2     # tracer: the share of rays a comparison LEAVES OUT.  In tests/test_trace_parity.py:_parity that is no longer the fragile rays:
+                            # they are traced, their composited lists validated (tests/trace_lists.py) and replayed by the oracle, and compared at TOL like
+                            # every other ray.  What this still bounds there is the fragile rays WITHOUT a list to replay, in the tests that exceed the list
+                            # capacity on purpose (rays served by the K-buffer kernels); where every ray is list-served the bound is exactly 0.  The tests
+                            # that still drop the audited rays beforehand (_drop_fragile: comparisons of two GPU runs, the bounce chain) keep it as the bound
+                            # on the dropped share (measured there: <= 3.3e-2 on the deep-list cases; 4e-2 = that maximum + margin).
+CLAMP_RAYS_MAX = 1e-2       # tracer: the share of rays whose dL/drgb is zeroed on both sides because a blended SH colour channel lies within its own fp32
+                            # rounding of the clamp at zero -- that decision is in no hit list and flips the hit's whole SH gradient.  Everything else of such
+                            # a ray, its forward colour included, is compared.  A stated bound, not a fitted one: 1 % of a test's rays (the oracle's audit
+                            # alone marks <= 0.5 % on every scene of the suite, 17 of 4096 on the deepest).
 TIMINGS = []                # device times recorded by tests (printed in the summary; never asserted under -m gpu)
 ERROR_TABLE = []
 
