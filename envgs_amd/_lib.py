@@ -144,12 +144,18 @@ SYMBOLS = {
     "envgs_compact_temp_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
     "envgs_compact_scan": (c_int, [ctypes.c_int64, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "envgs_compact_gather": (c_int, [ctypes.c_int32, ctypes.POINTER(RowsTensor), ctypes.c_int64, _P, _P, _P]),
+    "envgs_compact_gather_rows": (c_int, [ctypes.c_int32, ctypes.POINTER(RowsTensor), ctypes.c_int64, ctypes.c_int64, _P, _P, _P]),
     "envgs_knn3_mean_dist2": (c_int, [ctypes.c_int32, _P, _P, _P]),
     "envgs_densify_stats": (c_int, [ctypes.c_int64, ctypes.c_int32] + [_P] * 8 + [_P]),
     "envgs_densify_plan_temp_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
     "envgs_densify_plan": (c_int, [ctypes.POINTER(DensifyPlanArgs), _P]),
     "envgs_densify_split_stds": (c_int, [ctypes.c_int64, ctypes.c_int32] + [_P] * 5 + [ctypes.c_int64, _P]),
     "envgs_densify_rewrite": (c_int, [ctypes.POINTER(DensifyRewriteArgs), _P]),
+    "envgs_weight_select_temp_bytes": (ctypes.c_size_t, []),
+    "envgs_weight_select": (c_int, [ctypes.c_int64, _P, _P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, _P, _P, _P, ctypes.c_size_t, _P]),
+    "envgs_visibility_mask_temp_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
+    "envgs_visibility_mask": (c_int, [ctypes.c_int64, _P, _P, ctypes.c_int64, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "envgs_oversize_plan": (c_int, [ctypes.c_int64, c_uint32, ctypes.c_float, ctypes.c_float] + [_P] * 8 + [_P]),
     "envgs_l1_ssim_partial_count": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "envgs_l1_ssim_forward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P]),
     "envgs_l1_ssim_backward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, ctypes.c_float, ctypes.c_float, _P, _P]),

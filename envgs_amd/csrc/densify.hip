@@ -32,7 +32,7 @@ finish_positions(long long P, const uint8_t *__restrict__ keep, uint32_t *__rest
 // one launch for all tensors: a workgroup copies 256 consecutive 4-byte words of one tensor (coalesced reads; the writes of kept rows
 // are contiguous too, because kept rows stay in order)
 __global__ void __launch_bounds__(256)
-compact_gather(const CompactBatch B, const long long P, const uint8_t *__restrict__ keep, const uint32_t *__restrict__ pos)
+compact_gather(const CompactBatch B, const long long P, const long long out_rows, const uint8_t *__restrict__ keep, const uint32_t *__restrict__ pos)
 {
     const long long chunk = blockIdx.x;
     int ti = 0;
@@ -43,8 +43,9 @@ compact_gather(const CompactBatch B, const long long P, const uint8_t *__restric
     if (e >= P * w) return;
     const long long row = e / w;
     if (!keep[row]) return;
-    const long long col = e - row * w;
-    reinterpret_cast<uint32_t *>(T.dst)[(long long)pos[row] * w + col] = reinterpret_cast<const uint32_t *>(T.src)[e];
+    const long long col = e - row * w, to = pos[row];
+    if (to >= out_rows) return;                                      // (never, unless the caller's kept count was too small)
+    reinterpret_cast<uint32_t *>(T.dst)[to * w + col] = reinterpret_cast<const uint32_t *>(T.src)[e];
 }
 
 // exact 3 nearest neighbours by brute force: 256 query points per workgroup, candidates streamed through LDS in tiles of 256
@@ -106,8 +107,14 @@ int envgs_compact_scan(int64_t P, const uint8_t *keep, uint32_t *positions, uint
 
 int envgs_compact_gather(int32_t count, const envgs_rows_tensor *tensors, int64_t P, const uint8_t *keep, const uint32_t *positions, void *stream_)
 {
-    if (count < 0 || count > ENVGS_COMPACT_MAX_TENSORS || P < 0 || (count > 0 && !tensors)) return ENVGS_ERR_BAD_ARG;
-    if (P == 0 || count == 0) return 0;
+    return envgs_compact_gather_rows(count, tensors, P, P, keep, positions, stream_);
+}
+
+int envgs_compact_gather_rows(int32_t count, const envgs_rows_tensor *tensors, int64_t P, int64_t out_rows, const uint8_t *keep,
+                              const uint32_t *positions, void *stream_)
+{
+    if (count < 0 || count > ENVGS_COMPACT_MAX_TENSORS || P < 0 || out_rows < 0 || (count > 0 && !tensors)) return ENVGS_ERR_BAD_ARG;
+    if (P == 0 || count == 0 || out_rows == 0) return 0;
     if (!keep || !positions) return ENVGS_ERR_BAD_ARG;
     CompactBatch B;
     B.count = 0;
@@ -123,7 +130,7 @@ int envgs_compact_gather(int32_t count, const envgs_rows_tensor *tensors, int64_
     B.chunk_start[B.count] = chunks;
     if (chunks == 0) return 0;
     if (chunks >= (1ll << 31)) return ENVGS_ERR_BAD_ARG;
-    hipLaunchKernelGGL(compact_gather, dim3((unsigned)chunks), dim3(256), 0, (hipStream_t)stream_, B, (long long)P, keep, positions);
+    hipLaunchKernelGGL(compact_gather, dim3((unsigned)chunks), dim3(256), 0, (hipStream_t)stream_, B, (long long)P, (long long)out_rows, keep, positions);
     return (int)hipGetLastError();
 }
 

@@ -10,6 +10,11 @@
 //                     consecutive 4-byte words of one source tensor (compact_gather's shape) and stores each word to the 0 .. 2 + 2N rows it
 //                     becomes; kept rows stay in order inside every segment, so the stores are contiguous runs as well
 //
+//   weight_select     the pruning tail (device_schedule="all"): exact order statistics of the average weight by a three-pass radix select --
+//                     supervisor.hip's depth_select with the ranks as arguments, the key computed from two arrays and the count below each
+//                     selected value kept; visibility_mask turns a cut and a count into `prune_visibility`'s keep mask (ties by index order,
+//                     ranked with a scan); oversize_plan is `prune_max_scene_and_screen`'s masks and counts in one launch
+//
 // Compiled with -ffp-contract=off (build.py): the decisions repeat torch's compare / divide bit for bit and the gradient norm is a fixed
 // left-to-right sum, whatever the compiler would like to fuse.
 #include "common.h"
@@ -222,6 +227,156 @@ grow_rewrite(const GrowBatch B, const GrowCommon C)
     }
 }
 
+// ---- the pruning tail: order statistics of the average weight --------------------------------------------------------------------------
+// Three-pass radix select on the order-preserving uint32 image of the key, digits of 11 + 11 + 10 bits (supervisor.hip: depth_select_*).  Up to
+// two ranks share the passes: after pass 0 each has its own 11-bit prefix, passes 1 / 2 histogram only the keys under either prefix.  Integer
+// atomics only (LDS per workgroup, then one global add per non-empty bin).
+constexpr int WSEL_BINS0 = 2048, WSEL_BINS1 = 2048, WSEL_BINS2 = 1024;
+constexpr int WSEL_H0 = 0, WSEL_H1 = WSEL_H0 + WSEL_BINS0, WSEL_H2 = WSEL_H1 + 2 * WSEL_BINS1, WSEL_STATE = WSEL_H2 + 2 * WSEL_BINS2;   // uint32 offsets
+constexpr int WSEL_WORDS = WSEL_STATE + 4;          // state: prefix of either statistic, rank of either inside its prefix
+constexpr int WSEL_THREADS = 256;
+
+// get_xyz_weight_avg as an ordered word; -0 orders (and decodes) as +0
+__device__ __forceinline__ uint32_t weight_key(const float wa, const float dn)
+{
+    uint32_t b = __float_as_uint(stat_avg(wa, dn));
+    if (b == 0x80000000u) b = 0u;
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ uint32_t cut_key(const float cut) { return weight_key(cut, 1.0f); }        // (x / 1 = x: the key of a selected value)
+
+template <int PASS>
+__global__ void __launch_bounds__(WSEL_THREADS)
+weight_select_hist(const long long P, const float *__restrict__ wa, const float *__restrict__ dn, uint32_t *__restrict__ temp)
+{
+    constexpr int BINS = PASS == 2 ? WSEL_BINS2 : WSEL_BINS0, SETS = PASS == 0 ? 1 : 2;
+    __shared__ uint32_t h[SETS * BINS];
+    const int tid = threadIdx.x;
+    for (int b = tid; b < SETS * BINS; b += WSEL_THREADS) h[b] = 0u;
+    uint32_t p0 = 0u, p1 = 0u;
+    if (PASS > 0) { p0 = temp[WSEL_STATE]; p1 = temp[WSEL_STATE + 1]; }
+    __syncthreads();
+    for (long long i = (long long)blockIdx.x * WSEL_THREADS + tid; i < P; i += (long long)gridDim.x * WSEL_THREADS) {
+        const uint32_t k = weight_key(wa[i], dn[i]);
+        if (PASS == 0) {
+            atomicAdd(&h[k >> 21], 1u);
+        } else {
+            const uint32_t top = PASS == 1 ? (k >> 21) : (k >> 10), dig = PASS == 1 ? ((k >> 10) & 2047u) : (k & 1023u);
+            if (top == p0) atomicAdd(&h[dig], 1u);
+            if (top == p1) atomicAdd(&h[BINS + dig], 1u);
+        }
+    }
+    __syncthreads();
+    uint32_t *g = temp + (PASS == 0 ? WSEL_H0 : PASS == 1 ? WSEL_H1 : WSEL_H2);
+    for (int b = tid; b < SETS * BINS; b += WSEL_THREADS) {
+        const uint32_t v = h[b];
+        if (v) atomicAdd(&g[b], v);
+    }
+}
+
+// One workgroup: the bin that holds rank r of a histogram (the first bin whose inclusive prefix sum exceeds r), for either statistic.  The rank
+// left inside the last bin is the number of equal keys before the statistic, so what is below the selected value is the rank minus that.
+template <int PASS>
+__global__ void __launch_bounds__(WSEL_THREADS)
+weight_select_pick(const uint32_t rank0, const uint32_t rank1, const int n_ranks, uint32_t *__restrict__ temp, float *__restrict__ values,
+                   uint32_t *__restrict__ below)
+{
+    constexpr int BINS = PASS == 2 ? WSEL_BINS2 : WSEL_BINS0, PER = BINS / WSEL_THREADS;
+    __shared__ uint32_t sums[WSEL_THREADS];
+    const int tid = threadIdx.x;
+    uint32_t rank[2], prefix[2];
+    if (PASS == 0) { rank[0] = rank0; rank[1] = rank1; prefix[0] = prefix[1] = 0u; }
+    else { rank[0] = temp[WSEL_STATE + 2]; rank[1] = temp[WSEL_STATE + 3]; prefix[0] = temp[WSEL_STATE]; prefix[1] = temp[WSEL_STATE + 1]; }
+    __syncthreads();                                  // every lane holds the state before any lane replaces it
+    for (int which = 0; which < 2; which++) {
+        const uint32_t *hist = temp + (PASS == 0 ? WSEL_H0 : (PASS == 1 ? WSEL_H1 : WSEL_H2) + which * BINS);
+        uint32_t c[PER], s = 0u;
+#pragma unroll
+        for (int q = 0; q < PER; q++) { c[q] = hist[tid * PER + q]; s += c[q]; }
+        sums[tid] = s;
+        __syncthreads();
+        for (int off = 1; off < WSEL_THREADS; off <<= 1) {
+            const uint32_t v = tid >= off ? sums[tid - off] : 0u;
+            __syncthreads();
+            sums[tid] += v;
+            __syncthreads();
+        }
+        const uint32_t incl = sums[tid];
+        uint32_t run = incl - s;
+        const uint32_t r = rank[which];
+        if (r >= run && r < incl) {                   // true in exactly one lane (the total is the number of keys under the prefix, > r)
+            int bin = PER - 1;
+            bool found = false;
+#pragma unroll
+            for (int q = 0; q < PER; q++) {           // the first bin whose running total passes r; `run` ends as the count in the bins before it
+                if (!found) {
+                    if (r < run + c[q]) { bin = q; found = true; }
+                    else run += c[q];
+                }
+            }
+            const uint32_t digit = (uint32_t)(tid * PER + bin);
+            if (PASS == 0) { temp[WSEL_STATE + which] = digit; temp[WSEL_STATE + 2 + which] = r - run; }
+            if (PASS == 1) { temp[WSEL_STATE + which] = (prefix[which] << 11) | digit; temp[WSEL_STATE + 2 + which] = r - run; }
+            if (PASS == 2 && which < n_ranks) {
+                values[which] = unordered((prefix[which] << 10) | digit);
+                below[which] = (which ? rank1 : rank0) - (r - run);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// ---- prune_visibility's mask ------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+tie_flags(const long long P, const float *__restrict__ wa, const float *__restrict__ dn, const float *__restrict__ cut, uint32_t *__restrict__ flags)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < P) flags[i] = weight_key(wa[i], dn[i]) == cut_key(cut[0]) ? 1u : 0u;
+}
+
+// ties: the inclusive scan of tie_flags, i.e. the 1-based place of a tied key among the tied keys in index order
+__global__ void __launch_bounds__(256)
+visibility_mask(const long long P, const float *__restrict__ wa, const float *__restrict__ dn, const float *__restrict__ cut,
+                const uint32_t *__restrict__ cut_below, const uint32_t n_prune, const uint32_t *__restrict__ ties, uint8_t *__restrict__ keep)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= P) return;
+    const uint32_t k = weight_key(wa[i], dn[i]), kc = cut_key(cut[0]), below = cut_below[0];
+    const uint32_t tied_out = n_prune > below ? n_prune - below : 0u;
+    keep[i] = (k < kc || (k == kc && ties[i] <= tied_out)) ? 0 : 1;
+}
+
+// ---- prune_max_scene_and_screen's masks -------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+oversize_plan(const long long P, const uint32_t flags, const float max_screen, const float scene_limit, const float *__restrict__ mr,
+              const float *__restrict__ scal, const float *__restrict__ wa, const float *__restrict__ dn, const float *__restrict__ quantile,
+              uint8_t *__restrict__ keep, uint32_t *__restrict__ split, uint32_t *__restrict__ counts)
+{
+    __shared__ uint32_t s_red[4][2];
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    uint32_t n_prune = 0u, n_split = 0u;
+    if (i < P) {
+        const bool big = ((flags & ENVGS_OVERSIZE_SCREEN) && mr[i] > max_screen) ||
+                         ((flags & ENVGS_OVERSIZE_SCENE) && fmaxf(scal[2 * i], scal[2 * i + 1]) > scene_limit);
+        const bool light = !(flags & ENVGS_OVERSIZE_WEIGHT) || stat_avg(wa[i], dn[i]) < quantile[0];
+        n_prune = (big && light) ? 1u : 0u;
+        n_split = (big && !light) ? 1u : 0u;
+        keep[i] = n_prune ? 0 : 1;
+        split[i] = n_split;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { n_prune += __shfl_xor(n_prune, d, 64); n_split += __shfl_xor(n_split, d, 64); }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { s_red[wave][0] = n_prune; s_red[wave][1] = n_split; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t a = 0u, b = 0u;
+        for (int k = 0; k < 4; k++) { a += s_red[k][0]; b += s_red[k][1]; }
+        if (a) atomicAdd(&counts[0], a);
+        if (b) atomicAdd(&counts[1], b);
+    }
+}
+
 }  // namespace envgs
 
 using namespace envgs;
@@ -304,6 +459,69 @@ int envgs_densify_rewrite(const envgs_densify_rewrite_args *a, void *stream_)
     C.cls = a->cls; C.scan = a->scan; C.counters = a->counters;
     C.scal = a->scal; C.rotation = a->rotation; C.samples = a->samples;
     hipLaunchKernelGGL(grow_rewrite, dim3((unsigned)chunks), dim3(256), 0, (hipStream_t)stream_, B, C);
+    return (int)hipGetLastError();
+}
+
+size_t envgs_weight_select_temp_bytes(void) { return (size_t)WSEL_WORDS * sizeof(uint32_t); }
+
+int envgs_weight_select(int64_t P, const float *wa, const float *dn, int32_t n_ranks, int64_t rank0, int64_t rank1, float *values, uint32_t *below,
+                        void *temp, size_t temp_bytes, void *stream_)
+{
+    if (P < 1 || P >= (1ll << 31) || (n_ranks != 1 && n_ranks != 2) || !wa || !dn || !values || !below || !temp) return ENVGS_ERR_BAD_ARG;
+    if (n_ranks == 1) rank1 = rank0;
+    if (rank0 < 0 || rank0 >= P || rank1 < 0 || rank1 >= P) return ENVGS_ERR_BAD_ARG;
+    if (temp_bytes < envgs_weight_select_temp_bytes()) return ENVGS_ERR_TEMP_TOO_SMALL;
+    hipStream_t s = (hipStream_t)stream_;
+    uint32_t *t = (uint32_t *)temp;
+    hipError_t e = hipMemsetAsync(t, 0, (size_t)WSEL_WORDS * sizeof(uint32_t), s);
+    if (e != hipSuccess) return (int)e;
+    const int blocks = (int)min((long long)512, (long long)((P + WSEL_THREADS * 8 - 1) / (WSEL_THREADS * 8)));
+    const uint32_t r0 = (uint32_t)rank0, r1 = (uint32_t)rank1;
+    hipLaunchKernelGGL(weight_select_hist<0>, dim3(blocks), dim3(WSEL_THREADS), 0, s, (long long)P, wa, dn, t);
+    hipLaunchKernelGGL(weight_select_pick<0>, dim3(1), dim3(WSEL_THREADS), 0, s, r0, r1, (int)n_ranks, t, values, below);
+    hipLaunchKernelGGL(weight_select_hist<1>, dim3(blocks), dim3(WSEL_THREADS), 0, s, (long long)P, wa, dn, t);
+    hipLaunchKernelGGL(weight_select_pick<1>, dim3(1), dim3(WSEL_THREADS), 0, s, r0, r1, (int)n_ranks, t, values, below);
+    hipLaunchKernelGGL(weight_select_hist<2>, dim3(blocks), dim3(WSEL_THREADS), 0, s, (long long)P, wa, dn, t);
+    hipLaunchKernelGGL(weight_select_pick<2>, dim3(1), dim3(WSEL_THREADS), 0, s, r0, r1, (int)n_ranks, t, values, below);
+    return (int)hipGetLastError();
+}
+
+static size_t tie_flag_bytes(int64_t P) { return ((size_t)(P > 0 ? P : 1) * sizeof(uint32_t) + 255) & ~(size_t)255; }
+
+size_t envgs_visibility_mask_temp_bytes(int64_t P)
+{
+    const int64_t n = P > 0 && P < (1ll << 31) ? P : 1;
+    return tie_flag_bytes(n) + scan_temp_bytes((int)n);
+}
+
+int envgs_visibility_mask(int64_t P, const float *wa, const float *dn, int64_t n_prune, const float *cut, const uint32_t *cut_below, uint8_t *keep,
+                          void *temp, size_t temp_bytes, void *stream_)
+{
+    if (P < 1 || P >= (1ll << 31) || n_prune < 1 || n_prune > P || !wa || !dn || !cut || !cut_below || !keep || !temp) return ENVGS_ERR_BAD_ARG;
+    if (temp_bytes < envgs_visibility_mask_temp_bytes(P)) return ENVGS_ERR_TEMP_TOO_SMALL;
+    hipStream_t s = (hipStream_t)stream_;
+    uint32_t *flags = (uint32_t *)temp;
+    const size_t fb = tie_flag_bytes(P);
+    const dim3 grid((unsigned)((P + 255) / 256));
+    hipLaunchKernelGGL(tie_flags, grid, dim3(256), 0, s, (long long)P, wa, dn, cut, flags);
+    const int rc = launch_scan(flags, flags, (int)P, (char *)temp + fb, temp_bytes - fb, s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(visibility_mask, grid, dim3(256), 0, s, (long long)P, wa, dn, cut, cut_below, (uint32_t)n_prune, flags, keep);
+    return (int)hipGetLastError();
+}
+
+int envgs_oversize_plan(int64_t P, uint32_t flags, float max_screen, float scene_limit, const float *mr, const float *scal, const float *wa,
+                        const float *dn, const float *quantile, uint8_t *keep, uint32_t *split, uint32_t *counts, void *stream_)
+{
+    if (P < 0 || P >= (1ll << 31) || (flags & ~7u) || !counts) return ENVGS_ERR_BAD_ARG;
+    if (P > 0 && (!keep || !split)) return ENVGS_ERR_BAD_ARG;
+    if (P > 0 && (((flags & ENVGS_OVERSIZE_SCREEN) && !mr) || ((flags & ENVGS_OVERSIZE_SCENE) && !scal))) return ENVGS_ERR_BAD_ARG;
+    if (P > 0 && (flags & ENVGS_OVERSIZE_WEIGHT) && (!wa || !dn || !quantile)) return ENVGS_ERR_BAD_ARG;
+    hipStream_t s = (hipStream_t)stream_;
+    hipError_t e = hipMemsetAsync(counts, 0, 2 * sizeof(uint32_t), s);
+    if (e != hipSuccess || P == 0) return (int)e;
+    hipLaunchKernelGGL(oversize_plan, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, (long long)P, flags, max_screen, scene_limit, mr, scal, wa, dn,
+                       quantile, keep, split, counts);
     return (int)hipGetLastError();
 }
 

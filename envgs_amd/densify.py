@@ -15,8 +15,9 @@ def _stream(dev):
     return _lib.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
-def prune_rows(tensors, keep):
-    """[t[keep] for t in tensors] for tensors sharing their first dimension; keep: (P,) bool.  One host sync (the kept count)."""
+def prune_rows(tensors, keep, n_kept=None):
+    """[t[keep] for t in tensors] for tensors sharing their first dimension; keep: (P,) bool (or uint8, non-zero = keep).  One host sync (the
+    kept count) -- none when the caller knows the count and passes it as `n_kept`."""
     lib = _lib.load()
     if keep.device.type != "cuda":
         raise RuntimeError("prune_rows needs GPU tensors; there is no CPU path")
@@ -29,7 +30,7 @@ def prune_rows(tensors, keep):
     temp = torch.empty(max(tb, 1), dtype=torch.uint8, device=dev)
     p = _lib.ptr
     _lib.check(lib.envgs_compact_scan(P, p(keep8), p(pos), p(nk), p(temp), tb, _stream(dev)), "envgs_compact_scan")
-    n = int(nk.item()) & 0xFFFFFFFF
+    n = int(nk.item()) & 0xFFFFFFFF if n_kept is None else int(n_kept)
     outs, srcs = [], []
     for t in tensors:
         if t.shape[0] != P or t.device != dev:
@@ -45,7 +46,10 @@ def prune_rows(tensors, keep):
         arr = (_lib.RowsTensor * len(chunk))()
         for j, (s, o) in enumerate(chunk):
             arr[j] = _lib.RowsTensor(s.data_ptr(), o.data_ptr(), s.element_size() * (s[0].numel() if P else 0))
-        _lib.check(lib.envgs_compact_gather(len(chunk), arr, P, p(keep8), p(pos), _stream(dev)), "envgs_compact_gather")
+        if n_kept is None:
+            _lib.check(lib.envgs_compact_gather(len(chunk), arr, P, p(keep8), p(pos), _stream(dev)), "envgs_compact_gather")
+        else:                                                         # the caller's count sized the outputs: no row beyond it is written
+            _lib.check(lib.envgs_compact_gather_rows(len(chunk), arr, P, n, p(keep8), p(pos), _stream(dev)), "envgs_compact_gather_rows")
     return outs
 
 
@@ -110,9 +114,31 @@ def knn3_mean_dist2(xyz):
     return out
 
 
-def torch_rows(tensors, keep):
+def torch_rows(tensors, keep, n_kept=None):
     """`prune_rows` written with torch indexing.  NOT a product path: tests pass it as `row_ops` to exercise `SurfelSet`'s host logic on CPU."""
     return [t.detach()[keep] for t in tensors]
+
+
+def weight_order_statistics(weight_accum, denom, ranks):
+    """Exact order statistics of the average weight `weight_accum / denom` (NaN -> 0, -0 counted as +0; `get_xyz_weight_avg`,
+    gaussian2d_utils.py:628-631) for one or two 0-based ranks: (values (len(ranks),) float32, below (len(ranks),) int32 = the number of keys
+    strictly below each value), both on the device.  Three-pass radix select, no sort and no host synchronisation."""
+    lib = _lib.load()
+    if weight_accum.device.type != "cuda":
+        raise RuntimeError("weight_order_statistics needs GPU tensors; there is no CPU path")
+    dev, P = weight_accum.device, weight_accum.numel()
+    ranks = [int(r) for r in ranks]
+    if denom.numel() != P or denom.device != dev or len(ranks) not in (1, 2) or any(r < 0 or r >= P for r in ranks):
+        raise RuntimeError("weight_order_statistics: two tensors of the same size on one GPU and one or two ranks in [0, %d)" % P)
+    wa, dn = (t.detach().to(torch.float32).contiguous() for t in (weight_accum, denom))
+    values = torch.empty(len(ranks), dtype=torch.float32, device=dev)
+    below = torch.empty(len(ranks), dtype=torch.int32, device=dev)
+    tb = lib.envgs_weight_select_temp_bytes()
+    temp = torch.empty(tb, dtype=torch.uint8, device=dev)
+    p = _lib.ptr
+    _lib.check(lib.envgs_weight_select(P, p(wa), p(dn), len(ranks), ranks[0], ranks[-1], p(values), p(below), p(temp), tb, _stream(dev)),
+               "envgs_weight_select")
+    return values, below
 
 
 def normal_offsets(stds, generator=None):
@@ -139,7 +165,19 @@ class SurfelSet:
     device_schedule: OPT-IN device-resident mode (GPU tensors only, no CPU path): `add_densification_stats` becomes one launch without a host
         round trip, and `densify_and_prune` runs its first three stages as `grow_and_prune` -- one plan, one read-back, one rewrite.  Survivors,
         clones, moments, statistics and `log` equal the staged path bit for bit; the split children's `_xyz` / `_scaling` are the same formulas
-        evaluated in a HIP kernel, so they agree with the staged torch expressions to rounding, not to the bit: hence opt-in."""
+        evaluated in a HIP kernel, so they agree with the staged torch expressions to rounding, not to the bit: hence opt-in.  With True the
+        tail (`prune_max_scene_and_screen`, `prune_visibility`: global order statistics) stays staged torch.
+        device_schedule="all": the tail runs on the device as well.  The order statistics of the average weight come from a three-pass radix
+        select (`weight_order_statistics`) instead of `torch.quantile`'s sort / `torch.topk`; `prune_visibility` builds its mask and compacts
+        without any host synchronisation (the kept count is host arithmetic); `prune_max_scene_and_screen` builds both masks in one launch,
+        reads its two counts back (its only synchronisation), compacts with the split flags riding along and splits with the staged torch
+        expressions, so its result equals the staged path bit for bit.  One DEFINED difference, hence a value of its own: when several surfels
+        have exactly the cut-off weight of `prune_visibility`, the tied surfels of LOWEST INDEX are pruned (`torch.topk` leaves the choice
+        unspecified); exactly as many rows go as in the staged path.
+
+    The schedule edits between densifications -- `reset_opacity`, `reset_specular`, `enlarge_opacity`, `enlarge_scaling`, `distort_color`
+    (normal propagation and colour sabotage, gaussian2d_utils.py:482-515) and `set_learning_rate` (:916-919) -- are elementwise torch in every
+    mode, on CPU or GPU tensors, without a host synchronisation."""
 
     STATS = ("xyz_gradient_accum", "denom", "max_radii2D", "xyz_weight_accum")
 
@@ -149,7 +187,10 @@ class SurfelSet:
         self.optimizer, self.prefix, self.spatial_scale = optimizer, prefix, float(spatial_scale)
         self.max_gs, self.max_gs_threshold = max_gs, max_gs_threshold
         self.rows = row_ops or prune_rows
+        if isinstance(device_schedule, str) and device_schedule != "all":
+            raise ValueError("device_schedule is False, True or \"all\", not %r" % (device_schedule,))
         self.device_schedule = bool(device_schedule)
+        self.device_tail = isinstance(device_schedule, str)          # "all": the pruning tail on the device as well
         # split offsets are random: with data parallelism every rank must draw the SAME ones, i.e. pass generators seeded
         # identically on all ranks (or seed the global generator identically before every densification)
         self.generator = generator
@@ -159,7 +200,7 @@ class SurfelSet:
             g = groups.get(prefix + k)
             self.p[k] = g["params"][0] if g is not None else nn.Parameter(raw[k].detach().clone().requires_grad_(True))
         if self.device_schedule and self.device.type != "cuda":
-            raise RuntimeError("SurfelSet(device_schedule=True) needs GPU tensors; there is no CPU path")
+            raise RuntimeError("SurfelSet(device_schedule=%r) needs GPU tensors; there is no CPU path" % (device_schedule,))
         self.reset_stats()
         self.log = []                                # (event, count) pairs, the numbers the reference prints
 
@@ -267,15 +308,19 @@ class SurfelSet:
 
     def remove(self, mask):
         """prune_points + prune_stats (:553-560, :640-648): drop the rows where `mask` is set -- parameters, Adam moments and statistics, one gather."""
-        keep = ~mask
+        self._compact(~mask)
+
+    def _compact(self, keep, n_kept=None, extra=()):
+        """Keep the rows where `keep` is set.  n_kept: the kept count when the caller knows it (no read-back then); extra: further tensors of
+        P rows that go through the same gather -- their kept rows are returned."""
         items = self._groups()
         flat = []
         for k, g, prm, st in items:
             flat.append(prm.data)
             if st is not None and "exp_avg" in st:
                 flat += [st["exp_avg"], st["exp_avg_sq"]]
-        flat += [self.stats[s] for s in self.STATS]
-        outs = iter(self.rows(flat, keep))
+        flat += [self.stats[s] for s in self.STATS] + list(extra)
+        outs = iter(self.rows(flat, keep) if n_kept is None else self.rows(flat, keep, n_kept=n_kept))
         for k, g, prm, st in items:
             data = next(outs)
             if st is not None and "exp_avg" in st:
@@ -285,6 +330,7 @@ class SurfelSet:
         for s in self.STATS:
             self.stats[s] = next(outs)
         self._scene_changed()
+        return list(outs)
 
     @staticmethod
     def _scene_changed():
@@ -313,8 +359,9 @@ class SurfelSet:
         s["xyz_weight_accum"] = torch.cat([s["xyz_weight_accum"], wa.repeat(split, 1) * wmax], dim=0)
         self._scene_changed()
 
-    def _selected(self, mask):
-        outs = self.rows([self.p[k].data for k in self.names] + [self.stats[s] for s in self.STATS], mask)
+    def _selected(self, mask, n_selected=None):
+        flat = [self.p[k].data for k in self.names] + [self.stats[s] for s in self.STATS]
+        outs = self.rows(flat, mask) if n_selected is None else self.rows(flat, mask, n_kept=n_selected)
         return dict(zip(self.names, outs[:len(self.names)])), outs[len(self.names):]
 
     def clone(self, mask):
@@ -322,21 +369,26 @@ class SurfelSet:
         sel, st = self._selected(mask)
         self._append(sel, st, 1, 1.0)
 
-    def split(self, mask, N=2, ratio=0.8):
-        """:679-706: N children per selected surfel, offsets ~ N(0, diag(sx, sy, 0)) in the surfel's frame, scales / (ratio N); parents removed."""
+    def split(self, mask, N=2, ratio=0.8, n_selected=None):
+        """:679-706: N children per selected surfel, offsets ~ N(0, diag(sx, sy, 0)) in the surfel's frame, scales / (ratio N); parents removed.
+        n_selected: the number of set rows of `mask` when the caller knows it -- the two read-backs of that count are skipped."""
         from .synth import build_rotation
-        sel, st = self._selected(mask)
+        sel, st = self._selected(mask, n_selected)
         scal = torch.exp(sel["_scaling"])
         stds = scal.repeat(N, 1)
         stds = torch.cat([stds, torch.zeros_like(stds[:, :1])], dim=-1)
-        samples = torch.normal(torch.zeros_like(stds), stds, generator=self.generator)
+        if self.device_tail:
+            samples = normal_offsets(stds, self.generator)               # the same draw without torch.normal's host check, a sync
+        else:
+            samples = torch.normal(torch.zeros_like(stds), stds, generator=self.generator)
         rots = build_rotation(sel["_rotation"]).repeat(N, 1, 1)
         new = {k: v.repeat(*([N] + [1] * (v.dim() - 1))) for k, v in sel.items()}
         new["_xyz"] = torch.bmm(rots, samples.unsqueeze(-1)).squeeze(-1) + sel["_xyz"].repeat(N, 1)
         new["_scaling"] = torch.log(scal.repeat(N, 1) / (ratio * N))
         self._append(new, st, N, 1.0 / (ratio * N))
-        n_split = int(mask.sum().item())
-        self.remove(torch.cat((mask, torch.zeros(n_split * N, device=mask.device, dtype=torch.bool))))
+        n_split = int(mask.sum().item()) if n_selected is None else int(n_selected)
+        keep = ~torch.cat((mask, torch.zeros(n_split * N, device=mask.device, dtype=torch.bool)))
+        self._compact(keep, None if n_selected is None else mask.shape[0] + n_split * (N - 1))
 
     def replace(self, name, tensor):
         """replace_tensor_to_optimizer (:517-534): new values, zeroed moments."""
@@ -358,6 +410,37 @@ class SurfelSet:
         s = self.p["_specular"].detach()
         cap = torch.logit(torch.ones_like(s) * value)
         self.replace("_specular", cap if reset_all else torch.min(s, cap))
+
+    def enlarge_opacity(self, value=0.9):
+        """:499-503 (normal propagation): no opacity below `value`."""
+        o = self.p["_opacity"].detach()
+        self.replace("_opacity", torch.max(o, torch.logit(torch.ones_like(o) * value)))
+        self._scene_changed()           # (every box bounded by a raised opacity grows)
+
+    def _specular_peak(self):
+        return torch.sigmoid(self.p["_specular"].detach()).max(dim=-1).values.flatten()
+
+    def enlarge_scaling(self, ratio=1.5, threshold=0.02):
+        """:491-497 (normal propagation): the surfels whose specular reaches `threshold` grow by `ratio`; the others keep their raw scale."""
+        s = self.p["_scaling"].detach()
+        dull = (self._specular_peak() < threshold).unsqueeze(-1)
+        self.replace("_scaling", torch.where(dull, s, torch.log(torch.exp(s) * ratio)))
+        self._scene_changed()
+
+    def distort_color(self, range=0.4, threshold=0.05):
+        """:482-489 (colour sabotage): uniform noise of +-`range` on the base colour of every surfel whose specular does not exceed `threshold`.
+        The draw is `torch.rand_like` of the whole tensor, from the set's generator (the global one without)."""
+        f = self.p["_features_dc"].detach()
+        shiny = (self._specular_peak() > threshold).reshape([-1] + [1] * (f.dim() - 1))
+        u = torch.empty_like(f).uniform_(0.0, 1.0, generator=self.generator)
+        self.replace("_features_dc", torch.where(shiny, f, f + u * range * 2 - range))
+
+    def set_learning_rate(self, name, lr):
+        """update_learning_rate_by_name (:916-919): the group `prefix + name` trains at `lr` from now on; an unknown name changes nothing."""
+        if self.optimizer is not None:
+            for g in self.optimizer.param_groups:
+                if g.get("name") == self.prefix + name:
+                    g["lr"] = lr
 
     # ---- the schedule (gaussian2d_utils.py:718-899) ------------------------------------------------------------------------------------------------
     def densify_and_clone(self, grad_threshold, size_threshold):
@@ -468,6 +551,8 @@ class SurfelSet:
         self._scene_changed()
 
     def prune_max_scene_and_screen(self, max_scene_threshold=None, max_screen_threshold=None, min_weight_threshold=None):
+        if self.device_tail:
+            return self._device_prune_max(max_scene_threshold, max_screen_threshold, min_weight_threshold)
         P, dev = self.number, self.device
         none = torch.zeros(P, dtype=torch.bool, device=dev)
         screens = self.stats["max_radii2D"] > max_screen_threshold if max_screen_threshold is not None else none
@@ -487,9 +572,58 @@ class SurfelSet:
         if n_split > 0:
             self.split(split, 5, 0.5)
 
+    def _device_prune_max(self, max_scene_threshold, max_screen_threshold, min_weight_threshold):
+        """The same stage with the masks from one launch (envgs_oversize_plan) and `torch.quantile`'s value from two selected order statistics:
+        ranks floor / ceil of q (P - 1) in float32 and torch's own `lerp` between them, which is what `torch.quantile` does with its sorted
+        copy.  One read-back (the two counts); the split flags are compacted with the rows; the split itself is the staged one."""
+        lib = _lib.load()
+        P, dev, p = self.number, self.device, _lib.ptr
+        if P == 0:
+            self.log += [("prune_large", 0), ("split_large", 0)]
+            return
+        st = {k: self.stats[k].contiguous() for k in ("max_radii2D", "xyz_weight_accum", "denom")}
+        quant = None
+        if min_weight_threshold is not None:
+            rank = torch.tensor(min_weight_threshold, dtype=torch.float32) * (P - 1)                 # host tensors: torch.quantile's own arithmetic
+            lo = rank.floor()
+            values, _ = weight_order_statistics(st["xyz_weight_accum"], st["denom"], (int(lo), int(rank.ceil())))
+            quant = torch.lerp(values[0:1], values[1:2], torch.full((1,), float(rank - lo), dtype=torch.float32, device=dev))
+        scal = self.scaling().to(torch.float32).contiguous() if max_scene_threshold is not None else None
+        keep = torch.empty(P, dtype=torch.uint8, device=dev)
+        flags = torch.empty(P, dtype=torch.int32, device=dev)
+        counts = torch.empty(2, dtype=torch.int32, device=dev)
+        which = (1 if max_screen_threshold is not None else 0) | (2 if max_scene_threshold is not None else 0) | (4 if quant is not None else 0)
+        _lib.check(lib.envgs_oversize_plan(P, which, max_screen_threshold or 0.0, self.spatial_scale * (max_scene_threshold or 0.0), p(st["max_radii2D"]),
+                                           p(scal), p(st["xyz_weight_accum"]), p(st["denom"]), p(quant), p(keep), p(flags), p(counts), _stream(dev)),
+                   "envgs_oversize_plan")
+        n_prune, n_split = [int(v) & 0xFFFFFFFF for v in counts.cpu().tolist()]                      # the one host sync
+        self.log.append(("prune_large", n_prune)); self.log.append(("split_large", n_split))
+        if n_prune > 0:
+            flags, = self._compact(keep, P - n_prune, (flags,))
+        if n_split > 0:
+            self.split(flags != 0, 5, 0.5, n_selected=n_split)
+
+    def _device_prune_visibility(self, n_prune):
+        """The n_prune surfels of lowest average weight leave: one order statistic, the mask (ties by index order) and one compaction whose
+        kept count is known on the host -- no synchronisation at all."""
+        lib = _lib.load()
+        P, dev, p = self.number, self.device, _lib.ptr
+        if n_prune > P:
+            raise RuntimeError("prune_visibility: %d surfels cannot lose %d" % (P, n_prune))
+        wa, dn = (self.stats[k].to(torch.float32).contiguous() for k in ("xyz_weight_accum", "denom"))
+        cut, below = weight_order_statistics(wa, dn, (n_prune - 1,))
+        keep = torch.empty(P, dtype=torch.uint8, device=dev)
+        tb = lib.envgs_visibility_mask_temp_bytes(P)
+        temp = torch.empty(tb, dtype=torch.uint8, device=dev)
+        _lib.check(lib.envgs_visibility_mask(P, p(wa), p(dn), n_prune, p(cut), p(below), p(keep), p(temp), tb, _stream(dev)), "envgs_visibility_mask")
+        self._compact(keep, P - n_prune)
+
     def prune_visibility(self):
         n_prune = self.number - int(self.max_gs * self.max_gs_threshold)
-        if n_prune > 0:
+        if n_prune > 0 and self.device_tail:
+            self._device_prune_visibility(n_prune)
+            self.log.append(("prune_visibility", n_prune))
+        elif n_prune > 0:
             _, idx = torch.topk(self.weight_avg()[..., 0], n_prune, largest=False)
             mask = torch.zeros(self.number, dtype=torch.bool, device=self.device)
             mask[idx] = True

@@ -41,6 +41,11 @@ ENVGS_API int envgs_compact_scan(int64_t P, const uint8_t *keep, uint32_t *posit
 ENVGS_API int envgs_compact_gather(int32_t count, const envgs_rows_tensor *tensors, int64_t P, const uint8_t *keep, const uint32_t *positions,
                                    void *stream);
 
+/* The same gather for a caller that knows the kept count without reading *n_kept back: every dst has out_rows rows, and a kept row whose
+ * position is at or beyond out_rows is dropped, never written. */
+ENVGS_API int envgs_compact_gather_rows(int32_t count, const envgs_rows_tensor *tensors, int64_t P, int64_t out_rows, const uint8_t *keep,
+                                        const uint32_t *positions, void *stream);
+
 /* out[i] = mean of the squared distances from xyz[i] to its 3 nearest OTHER points (fewer if P < 4; 0 for P == 1).  xyz (P,3), out (P). */
 ENVGS_API int envgs_knn3_mean_dist2(int32_t P, const float *xyz, float *out, void *stream);
 
@@ -146,6 +151,42 @@ typedef struct envgs_densify_rewrite_args {
 } envgs_densify_rewrite_args;
 
 ENVGS_API int envgs_densify_rewrite(const envgs_densify_rewrite_args *args, void *stream);
+
+/* ---- the pruning tail on the device (SurfelSet(device_schedule="all")) ---------------------------------------------------------------------
+ *
+ * `prune_max_scene_and_screen` and `prune_visibility` (gaussian2d_utils.py:794-864) cut by order statistics of the per-surfel average weight
+ * (`get_xyz_weight_avg`, :628-631).  The KEY of surfel i is xyz_weight_accum[i] / denom[i]: IEEE division, NaN -> 0, -0 counted as +0.
+ */
+
+/* Scratch bytes of envgs_weight_select (histograms of the three passes; does not depend on P). */
+ENVGS_API size_t envgs_weight_select_temp_bytes(void);
+
+/* Exact order statistics of the keys: a three-pass radix select (11 + 11 + 10 bits) over the order-preserving uint32 image of the key, for
+ * n_ranks = 1 or 2 ranks in the same passes (rank1 is ignored when n_ranks == 1).  Per rank r (0-based, 0 <= r < P), on the device:
+ * values[k] = the (r + 1)-th smallest key, bit for bit one of the keys; below[k] = the number of keys strictly below it.  Integer atomics only:
+ * the result does not depend on the order of execution.  1 <= P < 2^31. */
+ENVGS_API int envgs_weight_select(int64_t P, const float *xyz_weight_accum, const float *denom, int32_t n_ranks, int64_t rank0, int64_t rank1,
+                                  float *values, uint32_t *below, void *temp, size_t temp_bytes, void *stream);
+
+ENVGS_API size_t envgs_visibility_mask_temp_bytes(int64_t P);
+
+/* keep (P bytes): 0 for the n_prune surfels of lowest key, 1 for the others.  cut / cut_below (device): envgs_weight_select's value and count
+ * for rank n_prune - 1.  Every key below the cut goes; of the keys equal to the cut, the first n_prune - *cut_below in index order go (ranked
+ * with a prefix scan, so the same rows whatever the launch order).  1 <= n_prune <= P < 2^31. */
+ENVGS_API int envgs_visibility_mask(int64_t P, const float *xyz_weight_accum, const float *denom, int64_t n_prune, const float *cut,
+                                    const uint32_t *cut_below, uint8_t *keep, void *temp, size_t temp_bytes, void *stream);
+
+/* envgs_oversize_plan flags: which thresholds are given */
+#define ENVGS_OVERSIZE_SCREEN 1u
+#define ENVGS_OVERSIZE_SCENE 2u
+#define ENVGS_OVERSIZE_WEIGHT 4u
+
+/* The masks of `prune_max_scene_and_screen` in one launch:  big = max_radii2D > max_screen (SCREEN) | max(scal) > scene_limit (SCENE);
+ * light = key < *quantile (WEIGHT; without it every surfel is light).  keep (P bytes) = !(big & light); split (P words) = big & !light;
+ * counts (device, 2 words) = {rows pruned, rows to split}.  scal: (P,2) activated scales; scene_limit = spatial_scale * max_scene_threshold. */
+ENVGS_API int envgs_oversize_plan(int64_t P, uint32_t flags, float max_screen, float scene_limit, const float *max_radii2D, const float *scal,
+                                  const float *xyz_weight_accum, const float *denom, const float *quantile, uint8_t *keep, uint32_t *split,
+                                  uint32_t *counts, void *stream);
 
 #ifdef __cplusplus
 }
