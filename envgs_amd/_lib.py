@@ -99,6 +99,24 @@ class SurfelInputsArgs(ctypes.Structure):
                                                   "d_xyz", "d_features_dc", "d_features_rest", "d_scaling", "d_rotation", "d_opacity", "d_specular", "d_roughness")])
 
 
+class TsdfVolume(ctypes.Structure):
+    """struct envgs_tsdf_volume (include/envgs_mesh.h)."""
+    _fields_ = ([(n, ctypes.c_int32) for n in ("nx", "ny", "nz")] + [(n, ctypes.c_float) for n in ("ox", "oy", "oz", "voxel")]
+                + [(n, ctypes.c_void_p) for n in ("tsdf", "weight", "rgb")])
+
+
+class TsdfView(ctypes.Structure):
+    """struct envgs_tsdf_view (include/envgs_mesh.h)."""
+    _fields_ = [("depth", ctypes.c_void_p), ("rgb", ctypes.c_void_p), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("R", ctypes.c_float * 9), ("T", ctypes.c_float * 3), ("depth_max", ctypes.c_float), ("trunc", ctypes.c_float)]
+
+
+class TsdfViews(ctypes.Structure):
+    """struct envgs_tsdf_views (include/envgs_mesh.h)."""
+    _fields_ = [("count", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("v", TsdfView * 8)]
+
+
 # every symbol include/*.h declares: name -> (restype, argtypes)
 _P = c_void_p
 SYMBOLS = {
@@ -156,6 +174,10 @@ SYMBOLS = {
     "envgs_visibility_mask_temp_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
     "envgs_visibility_mask": (c_int, [ctypes.c_int64, _P, _P, ctypes.c_int64, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "envgs_oversize_plan": (c_int, [ctypes.c_int64, c_uint32, ctypes.c_float, ctypes.c_float] + [_P] * 8 + [_P]),
+    "envgs_tsdf_integrate": (c_int, [ctypes.POINTER(TsdfVolume), ctypes.POINTER(TsdfViews), ctypes.c_float, _P]),
+    "envgs_mesh_temp_bytes": (c_size_t, [ctypes.c_int32] * 3),
+    "envgs_mesh_count": (c_int, [ctypes.POINTER(TsdfVolume), ctypes.c_float, ctypes.c_float, _P, c_size_t, _P, _P]),
+    "envgs_mesh_extract": (c_int, [ctypes.POINTER(TsdfVolume), ctypes.c_float, _P, c_size_t, c_uint32, c_uint32, _P, _P, _P, _P]),
     "envgs_l1_ssim_partial_count": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "envgs_l1_ssim_forward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P]),
     "envgs_l1_ssim_backward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, ctypes.c_float, ctypes.c_float, _P, _P]),

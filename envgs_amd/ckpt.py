@@ -169,3 +169,71 @@ def activate(raw):
     if "_roughness" in raw:
         out["roughness"] = torch.sigmoid(raw["_roughness"])
     return out
+
+
+# ---- triangle meshes (envgs_amd.mesh) -----------------------------------------------------------------------------------------------------------
+def save_mesh_ply(path, vertices, faces, colors=None):
+    """Binary little-endian PLY of a triangle mesh: vertices (V,3) as `x y z` float, plus `red green blue` uchar = round(clamp(c, 0, 1) 255) when
+    colors (V,3) are given; faces (F,3) as `list uchar int vertex_indices`.  Tensors or arrays, any device."""
+    arr = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    v = arr(vertices).astype("<f4").reshape(-1, 3)
+    f = arr(faces).astype("<i4").reshape(-1, 3)
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if colors is not None:
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    vt = np.empty(v.shape[0], dtype=fields)
+    vt["x"], vt["y"], vt["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if colors is not None:
+        c = np.rint(np.clip(arr(colors).astype(np.float64).reshape(-1, 3), 0.0, 1.0) * 255.0).astype("u1")
+        if c.shape[0] != v.shape[0]:
+            raise ValueError("save_mesh_ply: %d colours for %d vertices" % (c.shape[0], v.shape[0]))
+        vt["red"], vt["green"], vt["blue"] = c[:, 0], c[:, 1], c[:, 2]
+    ft = np.empty(f.shape[0], dtype=[("n", "u1"), ("i", "<i4", (3,))])
+    ft["n"] = 3
+    ft["i"] = f
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % v.shape[0]
+              + "".join("property %s %s\n" % ("float" if ty == "<f4" else "uchar", nm) for nm, ty in fields)
+              + "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % f.shape[0])
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        fh.write(vt.tobytes())
+        fh.write(ft.tobytes())
+
+
+def load_mesh_ply(path):
+    """-> (vertices (V,3) float32, faces (F,3) int32, colors (V,3) uint8 or None) numpy arrays, from a binary little-endian PLY whose vertex element
+    comes first and whose faces are triangles stored as `list uchar int`."""
+    with open(path, "rb") as fh:
+        if fh.readline().strip() != b"ply":
+            raise ValueError("%s is not a PLY file" % path)
+        fmt, counts, props, cur = None, {}, {"vertex": [], "face": []}, None
+        while True:
+            line = fh.readline()
+            if not line:
+                raise ValueError("PLY header of %s is not terminated" % path)
+            w = line.decode("ascii").split()
+            if not w or w[0] == "comment":
+                continue
+            if w[0] == "format":
+                fmt = w[1]
+            elif w[0] == "element":
+                cur = w[1]
+                counts[cur] = int(w[2])
+                props.setdefault(cur, [])
+            elif w[0] == "property":
+                props[cur].append(w[1:])
+            elif w[0] == "end_header":
+                break
+        if fmt != "binary_little_endian" or list(counts)[:2] != ["vertex", "face"]:
+            raise ValueError("load_mesh_ply reads binary little-endian files with a vertex element followed by a face element")
+        if any(p[0] == "list" for p in props["vertex"]) or [p[:3] for p in props["face"]] != [["list", "uchar", "int"]]:
+            raise ValueError("load_mesh_ply: unsupported vertex / face properties in %s" % path)
+        vdt = np.dtype([(p[1], ("<" + _PLY_TYPES[p[0]]) if _PLY_TYPES[p[0]][1] != "1" else _PLY_TYPES[p[0]]) for p in props["vertex"]])
+        vt = np.frombuffer(fh.read(vdt.itemsize * counts["vertex"]), dtype=vdt, count=counts["vertex"])
+        fdt = np.dtype([("n", "u1"), ("i", "<i4", (3,))])
+        ft = np.frombuffer(fh.read(fdt.itemsize * counts["face"]), dtype=fdt, count=counts["face"])
+    if counts["face"] and not (ft["n"] == 3).all():
+        raise ValueError("load_mesh_ply: %s has faces that are not triangles" % path)
+    vertices = np.stack([vt["x"], vt["y"], vt["z"]], axis=1).astype(np.float32)
+    colors = np.stack([vt["red"], vt["green"], vt["blue"]], axis=1) if "red" in vdt.names else None
+    return vertices, np.ascontiguousarray(ft["i"]).astype(np.int32).reshape(-1, 3), colors

@@ -1,0 +1,197 @@
+"""Mesh extraction (include/envgs_mesh.h, csrc/mesh.hip): TSDF fusion of rendered depth into a dense volume, marching tetrahedra over it.
+
+PARITY UNPINNED: the reference ships a fuser (easyvolcap/utils/tsdf_utils.py, fusion_utils.py, runners/visualizers/geometry_visualizer.py) that
+cannot run as it stands and leaves the marching step to libraries outside it, so the semantics are this project's ("Mesh extraction");
+tests/mesh_oracle.py restates them independently.  There is no CPU path: CPU tensors raise.
+
+    vol = TSDFVolume((-1, -1, -1), (1, 1, 1), voxel_size=0.01)
+    fuse_surfels(vol, cameras, base, sh_degree=3)
+    mesh = vol.extract()
+    ckpt.save_mesh_ply("scene.ply", mesh.vertices, mesh.faces, mesh.colors)
+"""
+import math
+from types import SimpleNamespace
+
+import torch
+
+from . import _lib
+
+MAX_VIEWS = 8                 # ENVGS_TSDF_MAX_VIEWS
+
+
+def _stream(dev):
+    return _lib.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _need_gpu(t, what):
+    if t.device.type != "cuda":
+        raise RuntimeError("%s needs tensors on the GPU; there is no CPU path" % what)
+
+
+def _host(t, shape):
+    """Camera parameters travel by value: a small host copy."""
+    return torch.as_tensor(t, dtype=torch.float32).detach().cpu().reshape(shape)
+
+
+class Mesh(SimpleNamespace):
+    """vertices (V,3) f32 world coordinates, faces (F,3) i32, colors (V,3) f32 or None: device tensors."""
+
+
+class TSDFVolume:
+    """A dense truncated-signed-distance volume over [bounds_min, bounds_max]: `tsdf` (Nz,Ny,Nx) in units of the truncation distance, initialised
+    to 1; `weight` (Nz,Ny,Nx), initialised to 0; `rgb` (3,Nz,Ny,Nx) when color=True.  Voxel (i,j,k) sits at origin + (i,j,k) voxel_size; the
+    dimensions are rounded up so that the grid covers the bounds.  trunc defaults to 5 voxel_size (the convention of the 2DGS mesh extraction,
+    adopted here as this project's choice)."""
+
+    def __init__(self, bounds_min, bounds_max, voxel_size, trunc=None, color=True, w_max=64.0, device="cuda"):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("TSDFVolume needs a GPU device; there is no CPU path")
+        lo = [float(v) for v in bounds_min]
+        hi = [float(v) for v in bounds_max]
+        voxel_size = float(voxel_size)
+        if not voxel_size > 0.0 or any(not h > l for l, h in zip(lo, hi)):
+            raise ValueError("TSDFVolume: voxel_size must be positive and bounds_max above bounds_min")
+        dims = [max(2, int(math.ceil((h - l) / voxel_size - 1e-9)) + 1) for l, h in zip(lo, hi)]
+        self._setup(dims, lo, voxel_size, trunc, w_max)
+        nx, ny, nz = dims
+        self.tsdf = torch.ones(nz, ny, nx, dtype=torch.float32, device=device)
+        self.weight = torch.zeros(nz, ny, nx, dtype=torch.float32, device=device)
+        self.rgb = torch.zeros(3, nz, ny, nx, dtype=torch.float32, device=device) if color else None
+
+    def _setup(self, dims, origin, voxel_size, trunc, w_max):
+        nx, ny, nz = dims
+        if min(dims) < 2 or max(dims) > 2048 or nx * ny * nz >= 2 ** 31:
+            raise ValueError("TSDFVolume: dimensions %s are outside 2..2048 per axis / 2^31 voxels" % (dims,))
+        self.dims = (nx, ny, nz)
+        self.origin = tuple(float(o) for o in origin)
+        self.voxel_size = float(voxel_size)
+        self.trunc = 5.0 * self.voxel_size if trunc is None else float(trunc)
+        self.w_max = float(w_max)
+
+    @classmethod
+    def from_tensors(cls, tsdf, weight, rgb, origin, voxel_size, trunc=None, w_max=64.0):
+        """A volume made elsewhere: tsdf, weight (Nz,Ny,Nx) and rgb (3,Nz,Ny,Nx) or None, contiguous float32 device tensors, used in place."""
+        _need_gpu(tsdf, "TSDFVolume.from_tensors")
+        for t, shape in ((tsdf, tuple(tsdf.shape)), (weight, tuple(tsdf.shape)), (rgb, (3,) + tuple(tsdf.shape))):
+            if t is None:
+                continue
+            if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape or t.device != tsdf.device or tsdf.dim() != 3:
+                raise ValueError("TSDFVolume.from_tensors: tensors must be contiguous float32, (Nz,Ny,Nx) / (3,Nz,Ny,Nx), on one device")
+        self = cls.__new__(cls)
+        nz, ny, nx = tsdf.shape
+        self._setup([nx, ny, nz], origin, voxel_size, trunc, w_max)
+        self.tsdf, self.weight, self.rgb = tsdf, weight, rgb
+        return self
+
+    def reset(self):
+        self.tsdf.fill_(1.0)
+        self.weight.zero_()
+        if self.rgb is not None:
+            self.rgb.zero_()
+
+    def _c_volume(self):
+        nx, ny, nz = self.dims
+        return _lib.TsdfVolume(nx, ny, nz, self.origin[0], self.origin[1], self.origin[2], self.voxel_size, self.tsdf.data_ptr(),
+                               self.weight.data_ptr(), None if self.rgb is None else self.rgb.data_ptr())
+
+    def integrate(self, depth, K, R, T, rgb=None, mask=None, depth_max=float("inf")):
+        """Fuses z-depth maps (H,W) or (B,H,W) (0 or negative = no measurement) seen through K (3,3), R (3,3) world -> camera and T (3,) --
+        each alone or one per view -- with optional colour maps (3,H,W) / (B,3,H,W).  mask: boolean, False = no measurement.  Views go to the
+        device 8 per launch, in the order given."""
+        lib = _lib.load()
+        _need_gpu(depth, "TSDFVolume.integrate")
+        dev = self.tsdf.device
+        if depth.dim() == 2:
+            depth = depth[None]
+            rgb = None if rgb is None else rgb[None]
+            mask = None if mask is None else mask.reshape((1,) + tuple(depth.shape[1:]))
+        B, H, W = depth.shape
+        depth = depth.to(device=dev, dtype=torch.float32)
+        if mask is not None:                                    # the one masked copy
+            depth = torch.where(mask.to(dev).reshape(B, H, W), depth, torch.zeros((), dtype=torch.float32, device=dev))
+        depth = depth.contiguous()
+        if rgb is not None:
+            rgb = rgb.to(device=dev, dtype=torch.float32).contiguous()
+            if tuple(rgb.shape) != (B, 3, H, W):
+                raise ValueError("TSDFVolume.integrate: rgb must be (B,3,H,W) for depth (B,H,W)")
+        K = _host(K, (-1, 3, 3)); R = _host(R, (-1, 3, 3)); T = _host(T, (-1, 3))
+        per_view = lambda a, b: a[b if a.shape[0] > 1 else 0]
+        vol = self._c_volume()
+        for b0 in range(0, B, MAX_VIEWS):
+            views = _lib.TsdfViews()
+            views.count = min(MAX_VIEWS, B - b0)
+            for q in range(views.count):
+                b = b0 + q
+                k, r, t = per_view(K, b), per_view(R, b), per_view(T, b)
+                v = views.v[q]
+                v.depth = depth[b].data_ptr()
+                v.rgb = None if rgb is None else rgb[b].data_ptr()
+                v.H, v.W = H, W
+                v.fx, v.fy, v.cx, v.cy = float(k[0, 0]), float(k[1, 1]), float(k[0, 2]), float(k[1, 2])
+                v.R = (_lib.ctypes.c_float * 9)(*[float(x) for x in r.reshape(-1)])
+                v.T = (_lib.ctypes.c_float * 3)(*[float(x) for x in t])
+                v.depth_max = float(depth_max)
+                v.trunc = self.trunc
+            _lib.check(lib.envgs_tsdf_integrate(vol, views, self.w_max, _stream(dev)), "envgs_tsdf_integrate")
+        return self
+
+    def extract(self, level=0.0, min_weight=1.0):
+        """Marching tetrahedra over the cells whose 8 corners all have weight >= min_weight -> Mesh.  One host sync: the read-back of (V, F)."""
+        lib = _lib.load()
+        dev = self.tsdf.device
+        nx, ny, nz = self.dims
+        tb = lib.envgs_mesh_temp_bytes(nx, ny, nz)
+        temp = torch.empty(tb, dtype=torch.uint8, device=dev)
+        totals = torch.empty(2, dtype=torch.int32, device=dev)
+        vol = self._c_volume()
+        p = _lib.ptr
+        _lib.check(lib.envgs_mesh_count(vol, float(level), float(min_weight), p(temp), tb, p(totals), _stream(dev)), "envgs_mesh_count")
+        V, F = [int(x) & 0xFFFFFFFF for x in totals.tolist()]
+        if V >= 2 ** 31 or F >= 2 ** 31:
+            raise RuntimeError("TSDFVolume.extract: %d vertices / %d faces do not fit int32 indices" % (V, F))
+        vertices = torch.empty(V, 3, dtype=torch.float32, device=dev)
+        faces = torch.empty(F, 3, dtype=torch.int32, device=dev)
+        colors = torch.empty(V, 3, dtype=torch.float32, device=dev) if self.rgb is not None else None
+        _lib.check(lib.envgs_mesh_extract(vol, float(level), p(temp), tb, V, F, p(vertices), p(colors), p(faces), _stream(dev)), "envgs_mesh_extract")
+        return Mesh(vertices=vertices, faces=faces, colors=colors)
+
+
+def surface_depth(allmap, depth_ratio=0.0):
+    """surf_depth of the reference's render() (gaussian2d_utils.py:1125-1131): the expected depth allmap[0] / alpha mixed with the median depth
+    allmap[5] by depth_ratio, non-finite values zeroed -- the expression of envgs_step.base_pass and of the surface_normal kernel."""
+    expected = torch.nan_to_num(allmap[0] / allmap[1], 0, 0)
+    median = torch.nan_to_num(allmap[5], 0, 0)
+    return expected * (1.0 - depth_ratio) + median * depth_ratio
+
+
+def fuse_surfels(volume, cameras, base, sh_degree, depth_ratio=0.0, alpha_min=0.5, scale_modifier=1.0):
+    """Renders `base` (means3D, shs, opacities, scales, rotations) from every camera (synth.make_camera namespaces) through
+    diff_surfel_rasterization_wet under no_grad, and integrates the surface depth and the rendered colour of the pixels with alpha > alpha_min.
+    Returns the per-view maps it integrated: [namespace(depth (H,W), alpha (H,W), rgb (3,H,W))]."""
+    import diff_surfel_rasterization_wet as pkg
+    _need_gpu(base["means3D"], "fuse_surfels")
+    dev = base["means3D"].device
+    maps = []
+    with torch.no_grad():
+        bg = torch.zeros(3, dtype=torch.float32, device=dev)
+        for cam in cameras:
+            st = pkg.GaussianRasterizationSettings(
+                image_height=cam.image_height, image_width=cam.image_width, tanfovx=cam.tanfovx, tanfovy=cam.tanfovy, bg=bg,
+                scale_modifier=scale_modifier, viewmatrix=cam.world_view_transform.to(dev), projmatrix=cam.full_proj_transform.to(dev),
+                sh_degree=sh_degree, campos=cam.camera_center.to(dev), prefiltered=False, debug=False)
+            color, _, allmap, _ = pkg.GaussianRasterizer(raster_settings=st)(
+                means3D=base["means3D"], means2D=torch.zeros_like(base["means3D"]), shs=base["shs"], colors_precomp=None,
+                opacities=base["opacities"], scales=base["scales"], rotations=base["rotations"], cov3D_precomp=None)
+            maps.append(SimpleNamespace(depth=surface_depth(allmap, depth_ratio), alpha=allmap[1], rgb=color[:3].contiguous()))
+        for b0 in range(0, len(maps), MAX_VIEWS):
+            chunk, cams = maps[b0:b0 + MAX_VIEWS], cameras[b0:b0 + MAX_VIEWS]
+            if len({tuple(m.depth.shape) for m in chunk}) == 1:
+                groups = [(chunk, cams)]
+            else:                                               # views of different sizes cannot share a (B,H,W) stack
+                groups = [([m], [c]) for m, c in zip(chunk, cams)]
+            for ms, cs in groups:
+                volume.integrate(torch.stack([m.depth for m in ms]), torch.stack([c.K.cpu() for c in cs]), torch.stack([c.R.cpu() for c in cs]),
+                                 torch.stack([c.T.cpu().reshape(3) for c in cs]), rgb=torch.stack([m.rgb for m in ms]),
+                                 mask=torch.stack([m.alpha > alpha_min for m in ms]))
+    return maps

@@ -1,0 +1,118 @@
+"""Device time of the mesh-extraction kernels (csrc/mesh.hip) next to their byte models:  python profiles/mesh_timing.py [--sizes 256 512] [--reps 20]
+
+Per volume size N^3 (bounds [-1,1]^3, colour on):
+  integrate   one launch fusing 8 views of 800x800 (analytic sphere depth + a colour map): median of `reps` launches, HIP events
+  torch       the same arithmetic written in torch on the device, one view at a time (the baseline the speed-up is quoted against)
+  extract     envgs_mesh_count + the read-back + envgs_mesh_extract of the fused volume
+The byte model of integrate: every voxel's tsdf, weight and rgb read once (20 B), and written back (20 B) in the 16 B granules where a voxel changed;
+of extract: 8 B read + 1 B written (classify), 1 B read + 3 B written (count), 4 B read (emit) per voxel, plus 24 B per vertex and 12 B per face
+written.  Fractions are of 6.3 TB/s (the achievable HBM rate, not the 8 TB/s peak).  Nothing is asserted; the table goes to DESIGN.md."""
+import os
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path[:] = [p for p in sys.path if os.path.abspath(p or ".") != HERE]          # profiles/numbers.py must not stand in for the standard library's
+sys.path.insert(0, os.path.dirname(HERE))
+
+import argparse  # noqa: E402
+
+import torch  # noqa: E402
+
+from envgs_amd import mesh, synth  # noqa: E402
+
+ACHIEVABLE = 6.3e12
+H = W = 800
+FX = 1111.1
+
+
+def sphere_depth(cam, radius, dev):
+    """z-depth of a sphere at the origin through the pixel centres, 0 where the ray misses."""
+    cc = cam.T.reshape(3).double()
+    py, px = torch.meshgrid(torch.arange(H, dtype=torch.float64) + 0.5, torch.arange(W, dtype=torch.float64) + 0.5, indexing="ij")
+    d = torch.stack([(px - W / 2) / FX, (py - H / 2) / FX, torch.ones_like(px)], dim=-1)
+    dd, dc = (d * d).sum(-1), d @ cc
+    disc = dc * dc - dd * (cc @ cc - radius ** 2)
+    t = (dc - disc.clamp_min(0).sqrt()) / dd
+    return torch.where(disc > 0, t, torch.zeros_like(t)).float().to(dev)
+
+
+def torch_integrate_view(vol, grid, depth, rgb, K, R, T):
+    """Steps 1-10 of include/envgs_mesh.h in torch ops, one view."""
+    X, Y, Z = grid
+    xc = R[0, 0] * X + R[0, 1] * Y + R[0, 2] * Z + T[0]
+    yc = R[1, 0] * X + R[1, 1] * Y + R[1, 2] * Z + T[1]
+    zc = R[2, 0] * X + R[2, 1] * Y + R[2, 2] * Z + T[2]
+    u = torch.floor(K[0, 0] * (xc / zc) + K[0, 2])
+    v = torch.floor(K[1, 1] * (yc / zc) + K[1, 2])
+    ok = (zc > 0) & (u >= 0) & (u < W) & (v >= 0) & (v < H)
+    pix = torch.where(ok, v * W + u, torch.zeros_like(u)).long()
+    d = depth.reshape(-1)[pix]
+    sdf = d - zc
+    ok = ok & (d > 0) & ~(sdf < -vol.trunc)
+    val = torch.clamp_max(sdf / vol.trunc, 1.0)
+    w1 = vol.weight + 1
+    vol.tsdf.copy_(torch.where(ok, (vol.weight * vol.tsdf + val) / w1, vol.tsdf))
+    for c in range(3):
+        vol.rgb[c].copy_(torch.where(ok, (vol.weight * vol.rgb[c] + rgb[c].reshape(-1)[pix]) / w1, vol.rgb[c]))
+    vol.weight.copy_(torch.where(ok, torch.clamp_max(w1, vol.w_max), vol.weight))
+
+
+def median_ms(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b))
+    return sorted(times)[len(times) // 2]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", type=int, nargs="+", default=[256, 512])
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--torch-reps", type=int, default=5)
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    cams = [synth.orbit_camera(v, n_views=8, radius=4.0, H=H, W=W, fx=FX) for v in range(8)]
+    depth = torch.stack([sphere_depth(c, 0.7, dev) for c in cams])
+    py, px = torch.meshgrid(torch.arange(H, dtype=torch.float32, device=dev), torch.arange(W, dtype=torch.float32, device=dev), indexing="ij")
+    rgb = torch.stack([torch.stack([0.5 + 0.5 * torch.sin(0.01 * px + v), 0.5 + 0.5 * torch.cos(0.013 * py), (px + py) / (H + W)]) for v in range(8)]).contiguous()
+    K, R, T = torch.stack([c.K for c in cams]), torch.stack([c.R for c in cams]), torch.stack([c.T.reshape(3) for c in cams])
+    print("%-6s %-10s %10s %12s %10s   %s" % ("N", "kernel", "ms", "model MB", "of 6.3TB/s", "note"))
+    for N in args.sizes:
+        voxel = 2.0 / (N - 1)
+        vol = mesh.TSDFVolume((-1, -1, -1), (-1 + voxel * (N - 1 - 1e-3),) * 3, voxel, device=dev)
+        assert vol.dims == (N, N, N), vol.dims
+        n = N ** 3
+        vol.integrate(depth, K, R, T, rgb=rgb)
+        changed = float((vol.weight > 0).float().mean())
+        t_int = median_ms(lambda: vol.integrate(depth, K, R, T, rgb=rgb), args.reps)
+        by = n * 20.0 * (1.0 + changed) + depth.numel() * 16.0
+        print("%-6d %-10s %10.3f %12.1f %9.1f%%   8 views per launch; %.1f %% of the voxels change" % (N, "integrate", t_int, by / 1e6, 100 * by / (t_int * 1e-3) / ACHIEVABLE, 100 * changed))
+        x = torch.arange(N, dtype=torch.float32, device=dev)
+        grid = tuple(vol.origin[a] + g * vol.voxel_size for a, g in enumerate(torch.meshgrid(x, x, x, indexing="ij")[::-1]))
+
+        def torch_all():
+            for b in range(8):
+                torch_integrate_view(vol, grid, depth[b], rgb[b], K[b], R[b], T[b])
+        t_torch = median_ms(torch_all, args.torch_reps)
+        print("%-6d %-10s %10.3f %12s %10s   same arithmetic in torch, 8 views one at a time: %.1fx the fused launch" % (N, "torch", t_torch, "-", "-", t_torch / t_int))
+        del grid
+        vol.reset()
+        vol.integrate(depth, K, R, T, rgb=rgb)
+        m = vol.extract()
+        V, F = m.vertices.shape[0], m.faces.shape[0]
+        t_ext = median_ms(lambda: vol.extract(), args.reps)
+        by = n * 17.0 + V * 24.0 + F * 12.0
+        print("%-6d %-10s %10.3f %12.1f %9.1f%%   V %d F %d; includes the (V, F) read-back and the output allocation" % (N, "extract", t_ext, by / 1e6, 100 * by / (t_ext * 1e-3) / ACHIEVABLE, V, F))
+        del vol, m
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
