@@ -59,7 +59,7 @@ class DensifyRewriteArgs(ctypes.Structure):
 class TraceLists(ctypes.Structure):
     """struct envgs_trace_lists (include/envgs_trace.h)."""
     _fields_ = [("hit_lists", ctypes.c_void_p), ("hit_cnt", ctypes.c_void_p), ("n_used", ctypes.c_void_p), ("cap", ctypes.c_int32),
-                ("stack_spill", ctypes.c_void_p), ("surf_acc", ctypes.c_void_p), ("surf_cnt", ctypes.c_void_p), ("surf_off", ctypes.c_void_p),
+                ("surf_acc", ctypes.c_void_p), ("surf_cnt", ctypes.c_void_p), ("surf_off", ctypes.c_void_p),
                 ("scan_temp", ctypes.c_void_p), ("scan_temp_bytes", ctypes.c_size_t), ("ray_keys", ctypes.c_void_p),
                 ("ray_order", ctypes.c_void_p), ("ray_sort_temp", ctypes.c_void_p), ("ray_sort_temp_bytes", ctypes.c_size_t),
                 ("records", ctypes.c_void_p),
@@ -131,7 +131,6 @@ SYMBOLS = {
     "envgs_bvh_build": (c_int, [ctypes.c_int32, _P, _P, _P, _P, c_size_t, ctypes.c_int32, _P]),
     "envgs_bvh_refit": (c_int, [ctypes.c_int32, _P, _P, _P, _P, _P, c_size_t, ctypes.c_int32, _P]),
     "envgs_bvh_quality": (c_int, [ctypes.c_int32, _P, _P, _P]),
-    "envgs_trace_stack_spill_ints": (c_size_t, [ctypes.c_int32]),
     "envgs_trace_ray_sort_temp_bytes": (c_size_t, [ctypes.c_int32]),
     "envgs_trace_ray_order": (c_int, [ctypes.c_int32, _P, _P, _P, ctypes.c_int32, _P, _P, _P, c_size_t, _P]),
     "envgs_trace_forward": (c_int, [ctypes.POINTER(TraceCfg)] + [_P] * 22 + [ctypes.POINTER(TraceLists), _P]),
@@ -226,8 +225,8 @@ def load():
 
 
 def select(kind):
-    """"product" (default) or "diag": the diagnostic build carries, behind envgs_debug_set, the superseded A/B kernels the product library was
-    trimmed of (csrc: ENVGS_DIAG).  Both export the same C-ABI; each keeps its own diagnostic switches and timers.  Returns the previous kind."""
+    """"product" (default) or "diag": the diagnostic build adds the exact-math raster kernels (ENVGS_DBG_RASTER_EXACT) and the LDS alignment trap
+    of the cooperative collection (csrc: ENVGS_DIAG).  Both export the same C-ABI; each keeps its own diagnostic switches and timers.  Returns the previous kind."""
     if kind not in ("product", "diag"):
         raise ValueError(kind)
     old = _selected["kind"]

@@ -12,11 +12,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_build")
 LIB = os.path.join(HERE, "libenvgs_hip.so")
-# Diagnostic build: the same library plus the superseded A/B kernels (three earlier collection kernels, the per-ray atomic-flush list
-# backward) behind envgs_debug_set -- compiled with -DENVGS_DIAG from the three sources that mention them; tests and `bench.py --diag` load it,
-# the product library does not contain them.
+# Diagnostic build: the same library plus the exact-math raster kernels (ENVGS_DBG_RASTER_EXACT: the attribution run of the parity tests) and
+# the LDS alignment trap of the cooperative collection -- compiled with -DENVGS_DIAG from the two sources that mention it; tests and
+# `bench.py --diag` load it, the product library contains neither.
 LIB_DIAG = os.path.join(HERE, "libenvgs_hip_diag.so")
-DIAG_SOURCES = ("trace_collect.hip", "trace_surfel_bwd.hip", "trace_api.hip", "raster_render.hip")
+DIAG_SOURCES = ("trace_collect.hip", "raster_render.hip")
 ARCH = "gfx950"
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++20", "-fPIC", "-munsafe-fp-atomics", "-fvisibility=hidden",
           "-Wall", "-Wno-unused-function"]

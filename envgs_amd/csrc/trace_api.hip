@@ -38,7 +38,7 @@ static bool lists_wanted(const envgs_trace_cfg *cfg, const envgs_trace_lists *L)
 }
 static bool lists_usable(const envgs_trace_cfg *cfg, const envgs_trace_lists *L)
 {
-    return lists_wanted(cfg, L) && L->hit_lists && L->hit_cnt && L->n_used && L->stack_spill && L->surf_cnt && L->surf_off && L->surf_acc && L->scan_temp;
+    return lists_wanted(cfg, L) && L->hit_lists && L->hit_cnt && L->n_used && L->surf_cnt && L->surf_off && L->surf_acc && L->scan_temp;
 }
 // The backward of the list path reads the hit COUNTS, the per-hit state, the entries / pairs and the per-surfel offsets -- not the lists
 // themselves (rays x capacity x 8 B, by far the largest buffer of a call) nor the forward's scratch: the caller may have released those
@@ -130,9 +130,6 @@ int envgs_trace_ray_order(int32_t num_rays, const float *ray_o, const float *ray
     return launch_ray_sort(num_rays, ray_o, ray_d, (const float4 *)nodes, P, pairs, order, temp, temp_bytes, (hipStream_t)stream);
 }
 
-// one slab per persistent wavefront of the collection kernels, for each of the (at most two) batch segments that run concurrently
-size_t envgs_trace_stack_spill_ints(int32_t num_rays) { return (size_t)2 * persistent_grid(num_rays, 24) * STACK * 64; }
-
 int envgs_trace_forward(const envgs_trace_cfg *cfg, const float *nodes, const float *ray_o, const float *ray_d,
                         const float *means3D, const float *scales, const float *rotations, const float *opacities,
                         const float *shs, const float *colors_precomp, const float *others_precomp, const float *bg,
@@ -172,9 +169,7 @@ int envgs_trace_forward(const envgs_trace_cfg *cfg, const float *nodes, const fl
     TraceArgs A = base_args(cfg, nodes, srec, shs, colors_precomp, others_precomp, bg, ray_o, ray_d, counters);
     A.ND = cfg->max_trace_depth + 1; A.stats = (unsigned long long *)(counters + 2);
     A.rgb = rgb; A.dpt = dpt; A.acc = acc; A.norm = norm; A.dist = dist; A.aux = aux; A.mid = mid; A.wet = wet; A.final_T = final_T;
-#ifndef ENVGS_DIAG
-    if (A.exp & (8 | 16 | 512 | 2048 | 4096 | 8192)) return ENVGS_ERR_BAD_ARG;      // A/B kernels of the diagnostic build (libenvgs_hip_diag.so) were requested
-#endif
+    if (A.exp & (8 | 16 | 512 | 2048 | 4096 | 8192)) return ENVGS_ERR_BAD_ARG;      // switches of deleted A/B kernels: refused, never silently ignored
     int rh, rw; ray_layout(cfg, &rh, &rw);
     const bool lists = lists_usable(cfg, L);
     if (lists_wanted(cfg, L) && !lists) return ENVGS_ERR_BAD_ARG;      // (see lists_usable_bwd: no silent fallback to the K-buffer path)
@@ -182,7 +177,7 @@ int envgs_trace_forward(const envgs_trace_cfg *cfg, const float *nodes, const fl
     ProfScope prof_(K_TRACE_FWD, stream);
     if (lists) {
         if (L->scan_temp_bytes < scan_temp_bytes(cfg->P * NCOPY)) return ENVGS_ERR_TEMP_TOO_SMALL;
-        A.hits = (uint2 *)L->hit_lists; A.hit_cnt = L->hit_cnt; A.n_used = L->n_used; A.cap = L->cap; A.stack_spill = L->stack_spill;
+        A.hits = (uint2 *)L->hit_lists; A.hit_cnt = L->hit_cnt; A.n_used = L->n_used; A.cap = L->cap;
         A.surf_cnt = L->surf_cnt; A.surf_off = L->surf_off; A.surf_acc = (unsigned long long *)L->surf_acc;
         const bool will_sort = L->ray_keys && L->ray_order && L->ray_sort_temp && !(A.exp & 64);
         {   // 40-bit fixed-point weight: enough integer bits that even a surfel seen with w = 1 by every ray cannot overflow
@@ -216,9 +211,6 @@ int envgs_trace_forward(const envgs_trace_cfg *cfg, const float *nodes, const fl
         int nseg = 2;                                         // measured (round 1): 1 -> 18.3 ms / step, 2 -> 17.5, 4 -> 19.4 (each collection launch lasts at least one batch)
         if (debug_switch(ENVGS_DBG_SEGMENTS) > 0) nseg = debug_switch(ENVGS_DBG_SEGMENTS);
         if (nseg > MAX_SEG) nseg = MAX_SEG;                   // (fetch counters: 8 words per segment from counters[32])
-        // the per-ray collection kernel (diagnostic: exp & 512, or no coherence sort) spills its stacks into a slab that is sized for two
-        // segments (envgs_trace_stack_spill_ints)
-        if (nseg > 2 && !(will_sort && !(A.exp & 512))) nseg = 2;
         while (nseg > 1 && nbatch_all / nseg < 256) nseg--;
         if (nseg < 1) nseg = 1;
         hipStream_t aux[MAX_SEG] = {};
@@ -269,7 +261,6 @@ int envgs_trace_forward(const envgs_trace_cfg *cfg, const float *nodes, const fl
             hipStream_t st = sg ? aux[sg] : stream;
             TraceArgs S = A;
             S.seg = sg;
-            S.spill_stride = persistent_grid(cfg->num_rays, 24);     // >= this segment's grid; matches envgs_trace_stack_spill_ints
             S.batch0 = (int)((long long)nbatch_all * sg / nseg);
             S.batch1 = (int)((long long)nbatch_all * (sg + 1) / nseg);
             const int rays_seg = (S.batch1 - S.batch0) * 64;
@@ -279,27 +270,11 @@ int envgs_trace_forward(const envgs_trace_cfg *cfg, const float *nodes, const fl
             const int seg_wgs = coop_wgs;
             {
                 ProfScope p1(K_TRACE_COLLECT, st);
-#ifndef ENVGS_DIAG
-                // product library: the cooperative collection is the only collection kernel (without a coherence sort its batches are the
-                // rays in the order given: correct, slower)
+                // the cooperative collection is the only collection kernel (without a coherence sort its batches are the rays in the order
+                // given: correct, slower)
                 const dim3 cg(persistent_grid(rays_seg, seg_wgs));
                 const float4 *n4 = S.nodes + (size_t)(cfg->P > 1 ? cfg->P - 1 : 1) * 4;
-                hipLaunchKernelGGL((collect_hits_coop<false, 8>), cg, dim3(256), 0, st, S, S.nodes, n4, S.srec);
-#else
-                const dim3 cg(persistent_grid(rays_seg, seg_wgs));
-                const float4 *n4 = S.nodes + (size_t)(cfg->P > 1 ? cfg->P - 1 : 1) * 4;
-                const bool coop = S.order && !(S.exp & 512) && !(S.exp & 16) && !(S.exp & 2048);
-                if (coop && (S.exp & 4096)) hipLaunchKernelGGL((collect_hits_coop<true, 8>), cg, dim3(256), 0, st, S, S.nodes, n4, S.srec);       // A/B: deferred exact tests
-                else if (coop && (S.exp & 8192)) hipLaunchKernelGGL((collect_hits_coop<true, 6>), cg, dim3(256), 0, st, S, S.nodes, n4, S.srec);
-                else if (coop) hipLaunchKernelGGL((collect_hits_coop<false, 8>), cg, dim3(256), 0, st, S, S.nodes, n4, S.srec);
-                else if (S.order && !(S.exp & 512) && !(S.exp & 16))
-                    hipLaunchKernelGGL(collect_hits_packet4, dim3(persistent_grid(rays_seg, 24)), dim3(64), 0, st, S, S.nodes,
-                                       S.nodes + (size_t)(cfg->P > 1 ? cfg->P - 1 : 1) * 4, S.srec);
-                else if (S.order && !(S.exp & 512))
-                    hipLaunchKernelGGL(collect_hits_packet, dim3(persistent_grid(rays_seg, 24)), dim3(64), 0, st, S, S.nodes, S.srec);
-                else
-                    hipLaunchKernelGGL(collect_hits, dim3(persistent_grid(rays_seg, 24)), dim3(64), 0, st, S);
-#endif
+                hipLaunchKernelGGL(collect_hits_coop, cg, dim3(256), 0, st, S, S.nodes, n4, S.srec);
             }
             ENVGS_CHECK_LAUNCH(dcfg, st);
             if (compact) {
@@ -309,10 +284,6 @@ int envgs_trace_forward(const envgs_trace_cfg *cfg, const float *nodes, const fl
                 unsigned *cntb = L->row_blk;                                       // (batches) row counts, scanned in place per segment
                 // the segment claims its rows from a counter shared by the call's segments (counters[22]); its first row lands in counters[28 + seg]
                 const unsigned long long limit = (unsigned long long)L->compact_rows;
-#ifdef ENVGS_DIAG
-                if (!(S.order && !(S.exp & 512) && !(S.exp & 16) && !(S.exp & 2048)))     // the A/B collection kernels do not write batch counts
-                    hipLaunchKernelGGL(row_count, dim3(nblk), dim3(256), 0, st, S, cntb);
-#endif
                 hipLaunchKernelGGL(row_scan_blocks, dim3(1), dim3(256), 0, st, cntb + S.batch0, nb_seg, counters + 22, counters + 28 + sg);
                 hipLaunchKernelGGL(row_offsets, dim3(nblk), dim3(256), 0, st, S, cntb, L->row_off, (uint2 *)L->batch_rows, (const unsigned *)(counters + 28 + sg), limit);
                 ENVGS_CHECK_LAUNCH(dcfg, st);
@@ -399,9 +370,7 @@ int envgs_trace_backward(const envgs_trace_cfg *cfg, const float *nodes, const f
     A.f_rgb = rgb; A.f_dpt = dpt; A.f_acc = acc; A.f_norm = norm; A.f_aux = aux; A.f_T = final_T;
     A.g_rgb = dL_drgb; A.g_dpt = dL_ddpt; A.g_acc = dL_dacc; A.g_norm = dL_dnorm; A.g_aux = dL_daux;
     A.geo_rec = geo_rec; A.dshs = dshs; A.dcolors = dcolors; A.dothers = dothers; A.dray_o = dray_o; A.dray_d = dray_d;
-#ifndef ENVGS_DIAG
     if (A.exp & (8 | 16 | 512 | 2048 | 4096 | 8192)) return ENVGS_ERR_BAD_ARG;
-#endif
     int rh, rw; ray_layout(cfg, &rh, &rw);
     bool deferred = false, have_records = false;
     int def_dev = 0;
@@ -411,7 +380,7 @@ int envgs_trace_backward(const envgs_trace_cfg *cfg, const float *nodes, const f
         if (lists_usable_bwd(cfg, L)) {                // lists_wanted(): the forward took the list path exactly when it holds
             A.hits = (uint2 *)L->hit_lists; A.hit_cnt = L->hit_cnt; A.n_used = L->n_used; A.cap = L->cap;
             if (L->ray_keys && L->ray_order && L->ray_sort_temp && !(A.exp & 64)) A.order = L->ray_order + cfg->num_rays;
-            if (L->records && L->num_records > 0 && L->surf_cnt && L->surf_off && L->hit_state && L->entries && L->pairs && L->n_entries && !(A.exp & 8)) {
+            if (L->records && L->num_records > 0 && L->surf_cnt && L->surf_off && L->hit_state && L->entries && L->pairs && L->n_entries) {
                 // atomic-free: one record per (batch, surfel) entry, grouped by surfel; then each surfel's records are summed
                 A.surf_cnt = L->surf_cnt; A.surf_off = L->surf_off; A.records = L->records; A.num_records = L->num_records;
                 A.state = (float4 *)L->hit_state; A.entries = (unsigned long long *)L->entries; A.pairs = L->pairs; A.n_entries = L->n_entries;
@@ -442,16 +411,10 @@ int envgs_trace_backward(const envgs_trace_cfg *cfg, const float *nodes, const f
                 if ((dflags & ENVGS_TRACE_DEFER) && aux_objects(&def_dev)) deferred = true;
                 else if (!accumulate) { ProfScope p7(K_TRACE_REDUCE, stream); hipLaunchKernelGGL(reduce_surfel_records, dim3(stride_grid(cfg->P, 16)), dim3(256), 0, stream, A); }
             } else {
-#ifdef ENVGS_DIAG
-                if (!L->hit_lists) return ENVGS_ERR_BAD_ARG;       // the per-ray atomic-flush backward walks the lists themselves
-                ProfScope p5(K_TRACE_LIST_BWD, stream);
-                hipLaunchKernelGGL(composite_lists_bwd, dim3(stride_grid(cfg->num_rays, 64)), dim3(64), 0, stream, A);
-#else
-                // product library: the record backward is the only list backward.  No records = the forward composited nothing on the list
+                // the record backward is the only list backward.  No records = the forward composited nothing on the list
                 // path (num_records is its device-side count) -- anything else is a caller error, not a reason to differentiate nothing silently
                 if (!(L->surf_cnt && L->surf_off && L->hit_state && L->entries && L->pairs && L->n_entries) || (L->records == nullptr && L->num_records > 0))
                     return ENVGS_ERR_BAD_ARG;
-#endif
             }
             A.only_overflow = 1;
         }

@@ -29,7 +29,6 @@ namespace envgs {
 constexpr int KBUF = 16;            // hits buffered per round
 constexpr int STACK = 64;           // LBVH depth bound: 62-bit keys
 constexpr int NCOPY = 8;            // per-surfel hit counters are replicated NCOPY x (by ray index) to spread same-address atomics
-constexpr int LDS_STACK = 24;       // collect_hits keeps this many levels in LDS, the rest in an HBM slab
 constexpr int MAX_ROUNDS = 256;     // safety bound: 4096 hits per ray
 constexpr float UV_MAX = 3.0f;
 constexpr int MID = ENVGS_MID_CHANNELS;
@@ -166,19 +165,16 @@ struct TraceArgs {
     float *records;           // (num_records, 24) per-hit gradient records grouped by surfel
     unsigned long long num_records;
     const unsigned *order;    // (R) ray permutation (coherence sort) or NULL
-    int exp;            // diagnostic switches (envgs_debug_set(ENVGS_DBG_TRACE, ...); 0 in production): 8 = atomic-flush backward instead of records,
-                        // 16 = binary packet traversal instead of the 4-wide one,
-                        // 64 = no coherence sort of the rays, 512 = per-ray collection kernel even when the rays are sorted,
-                        // 1024 = packet stack limited to 2 entries (tests the overflow hand-off)
-    int *stack_spill;   // collect_hits: (grid, STACK, 64) ints of stack overflow space
+    int exp;            // diagnostic switches (envgs_debug_set(ENVGS_DBG_TRACE, ...); 0 in production): 64 = no coherence sort of the rays,
+                        // 1024 = packet stack limited to 2 entries (tests the overflow hand-off), 16384 = forward_prepare on the caller's stream.
+                        // The bits of the deleted A/B kernels (8, 16, 512, 2048, 4096, 8192) are refused with ENVGS_ERR_BAD_ARG
     int only_overflow;  // K-buffer kernels: process only rays whose hit_cnt exceeds cap
     int batch0, batch1; // list-path forward kernels: the range of 64-ray batches this launch owns (segments run on two streams)
     uint4 *sparse;      // (sparse_cap) hits of SPARSE entries (envgs_trace.h: sparse_hits): {sorted ray slot, list position, surfel id, record slot}; counter[64] = how many
     unsigned sparse_cap;
     int sparse_max;     // an entry with at most this many hits is filed per hit instead of becoming an entry of the batch kernel (0 = off)
     int reduce_adds;    // reduce_surfel_records adds its sums to what the buffers hold instead of storing them (the backward's deferred tail: the K-buffer pass ran before it)
-    int seg;            // segment index: selects the batch-fetch counters and the stack-spill slab
-    int spill_stride;   // stack-spill slabs per segment
+    int seg;            // segment index: selects the batch-fetch counters
     unsigned long long *entries;  // (batches, 64*cap) distinct (batch, surfel) entries, see register_hits
     unsigned *pairs;              // (batches, 64*cap) (lane << 16 | k) of every composited hit, grouped by entry
     int *n_entries;               // (batches, 2) table entries, single entries
@@ -611,9 +607,9 @@ __device__ __forceinline__ int ray_of(const TraceArgs &A, int slot) { return slo
 // ---------------------------------------------------------------------------------- list path ---
 // MI355X-first variant of T2/T3 for bounce-free tracing (what EnvGS runs: max_trace_depth = 0).  HBM is plentiful
 // (288 GB), so instead of re-traversing the BVH in rounds of K hits -- and again in the backward -- the ray's hits
-// are collected ONCE, unordered, into a per-ray list in HBM (collect_hits: no K-buffer, few registers, high
-// occupancy), sorted by (t, id) per ray in LDS by the whole wavefront (sort_hit_lists), and then walked front to back
-// by the forward (composite_lists_fwd) and again by the backward (composite_lists_bwd), which never touches the BVH.
+// are collected ONCE, unordered, into a per-ray list in HBM (collect_hits_coop: no K-buffer), sorted by (t, id) per ray and
+// composited front to back by the forward (sort_composite_fwd), which registers every composited hit under its (batch, surfel) entry
+// (register_hits); the backward (batch_surfel_bwd) walks those entries and never touches the BVH.
 // Rays whose list overflows `cap` fall back to the K-buffer kernels above (only_overflow mode).
 
 // XCD-affine batch fetch.  Rays are coherence-sorted, so a contiguous run of 64-ray batches covers one region of direction space;
@@ -662,17 +658,12 @@ __device__ __forceinline__ void batch_region(const TraceArgs &A, const int batch
     else { size = (size_t)64 * A.cap; start = (size_t)batch * size; }
 }
 
-// Conservative termination bound for the unordered collection.  The ray's accepted hits are binned by distance into 16
-// linear bins over its chord through the scene box (16 registers of optical depth -ln(1-alpha)); as soon as the bins up to edge e hold more optical depth than
+// Conservative termination bound for the unordered collection.  The ray's accepted hits are binned by distance into
+// linear bins over its chord through the scene box (optical depth -ln(1-alpha) per bin, in LDS); as soon as the bins up to edge e hold more optical depth than
 // the compositing can survive (T < 1e-4), every hit beyond e is provably after the terminating hit: it is dropped and BVH nodes
 // that start beyond e are pruned.  Exact (never drops a composited hit) and it removes most of the 3x over-collection of a fog.
-constexpr int NBIN = 16;
 constexpr float KILL_OD = 9.2104f * 1.03f + 0.05f;       // -ln(1e-4) with margin for fp32 product vs sum-of-logs
 
-// Wave-uniform stack of the packet kernels, in LDS.  Sized so that it does not overflow: the LBVH is at most 63 levels deep (62-bit unique Morton keys),
-// the binary walk holds one postponed child per level and the 4-wide walk at most three per TWO levels.  Should a child ever not fit, the batch is
-// flagged: its rays are handed to the K-buffer kernels (per-lane stacks) and counters[20] counts the event -- never a silently dropped subtree.
-constexpr int PSTACK = 128;
 constexpr int WIDE_EMPTY = ENVGS_WIDE_EMPTY;   // reference of an unused slot of a 4-wide node (never a surfel: ids are < 2^24 on the list path)
 constexpr int SORT_MAX = 1024;  // longest list the sort / composite pass takes (16 keys per lane)
 constexpr int RH_W = 8;         // register_hits: wavefronts per batch -- wave q takes list positions q, q + RH_W, ... of every ray
@@ -690,23 +681,8 @@ struct ForwardPrepare {
 __global__ void __launch_bounds__(256) forward_prepare(const ForwardPrepare F);
 __global__ void __launch_bounds__(64) trace_fwd(const TraceArgs A, const int ray_h, const int ray_w);
 __global__ void __launch_bounds__(64) trace_bwd(const TraceArgs A, const int ray_h, const int ray_w);
-#ifdef ENVGS_DIAG
-__global__ void __launch_bounds__(64) collect_hits(const TraceArgs A);
-__global__ void __attribute__((amdgpu_waves_per_eu(8, 8))) __launch_bounds__(64)
-collect_hits_packet(const TraceArgs A, const float4 *__restrict__ nodes, const float4 *__restrict__ srec);
-__global__ void __attribute__((amdgpu_waves_per_eu(6, 8))) __launch_bounds__(64)
-collect_hits_packet4(const TraceArgs A, const float4 *__restrict__ nodes, const float4 *__restrict__ nodes4, const float4 *__restrict__ srec);
-__global__ void __launch_bounds__(64) composite_lists_bwd(const TraceArgs A);
-#endif
-template <bool DEFER, int WAVES> __global__ void __launch_bounds__(256, WAVES)
+__global__ void __launch_bounds__(256, 8)
 collect_hits_coop(const TraceArgs A, const float4 *__restrict__ nodes, const float4 *__restrict__ nodes4, const float4 *__restrict__ srec);
-#define ENVGS_COOP_DECL(D, W) extern template __global__ void __launch_bounds__(256, W) \
-    collect_hits_coop<D, W>(const TraceArgs A, const float4 *__restrict__ nodes, const float4 *__restrict__ nodes4, const float4 *__restrict__ srec);
-ENVGS_COOP_DECL(false, 8)
-#ifdef ENVGS_DIAG
-ENVGS_COOP_DECL(true, 8) ENVGS_COOP_DECL(true, 6)
-#endif
-#undef ENVGS_COOP_DECL
 
 template <int EMAX, bool LONG, bool QSH> __global__ void __launch_bounds__(256) sort_composite_fwd(const TraceArgs A);
 extern template __global__ void __launch_bounds__(256) sort_composite_fwd<4, false, false>(const TraceArgs A);
@@ -716,7 +692,6 @@ extern template __global__ void __launch_bounds__(256) sort_composite_fwd<4, fal
 extern template __global__ void __launch_bounds__(256) sort_composite_fwd<8, true, true>(const TraceArgs A);
 extern template __global__ void __launch_bounds__(256) sort_composite_fwd<16, true, true>(const TraceArgs A);
 template <bool CACHED> __global__ void __launch_bounds__(64 * RH_W) register_hits(const TraceArgs A);
-__global__ void __launch_bounds__(256) row_count(const TraceArgs A, unsigned *__restrict__ blk);
 __global__ void __launch_bounds__(256) row_scan_blocks(unsigned *__restrict__ blk, int n, unsigned *rows_used, unsigned *seg_base);
 __global__ void __launch_bounds__(256) row_offsets(const TraceArgs A, const unsigned *__restrict__ blk, unsigned *__restrict__ row_off, uint2 *__restrict__ batch_rows,
                                                    const unsigned *__restrict__ seg_base, unsigned long long limit);      // blk: exclusive scan of the per-BATCH row counts

@@ -678,24 +678,13 @@ template __global__ void register_hits<true>(const TraceArgs A);
 // Row offsets of the compact per-hit buffers (envgs_trace.h: compact_rows).  Runs per forward segment between the collection and the sort:
 // rows of a ray = its hits found (none for a ray whose list overflowed), scanned over the segment's slots in coherence-sorted order.  The
 // cooperative collection writes each batch's row count as it finishes the batch (TraceArgs::batch_cnt), so two small launches remain: one
-// workgroup scanning the segment's batch counts, then one wavefront per batch placing its rays.  (row_count -- per-block sums from the hit
-// counts -- serves the diagnostic collection kernels, which do not write batch counts.)
+// workgroup scanning the segment's batch counts, then one wavefront per batch placing its rays.
 __device__ __forceinline__ unsigned rows_of_slot(const TraceArgs &A, const int slot, const int slot_end)
 {
     if (slot >= slot_end) return 0u;
     const int r = ray_of(A, slot);
     const int n = A.hit_cnt[r];
     return n > A.cap ? 0u : (unsigned)n;
-}
-
-__global__ void __launch_bounds__(256)
-row_count(const TraceArgs A, unsigned *__restrict__ blk)
-{
-    const int slot_end = min(A.R, A.batch1 * 64);
-    const int slot = A.batch0 * 64 + (int)blockIdx.x * 256 + (int)threadIdx.x;
-    if ((slot >> 6) >= A.batch1) return;
-    const float s = wave_sum((float)rows_of_slot(A, slot, slot_end));            // exact: <= 64 * 1024
-    if ((threadIdx.x & 63) == 0) blk[slot >> 6] = (unsigned)s;
 }
 
 __global__ void __launch_bounds__(256)

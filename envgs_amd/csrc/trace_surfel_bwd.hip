@@ -1,50 +1,9 @@
 // trace_surfel_bwd.hip -- list path backward: the surfel-major batch kernel (lane = ray, MFMA reduction), the per-surfel record reduction, the
-// hits of sparse entries one lane each (sparse_hits_bwd), the parameter-gradient finish, and -- diagnostic build only -- the per-ray atomic-flush
-// backward (composite_lists_bwd).  The per-hit gradient itself is trace_common.h's (hit_geometry_grad and its neighbours).
+// hits of sparse entries one lane each (sparse_hits_bwd) and the parameter-gradient finish.  The per-hit gradient itself is trace_common.h's
+// (hit_geometry_grad and its neighbours).
 #include "trace_common.h"
 
 namespace envgs {
-
-#ifdef ENVGS_DIAG   // per-ray atomic-flush backward of the list path: superseded by the record backward, kept for A/B measurements and tests
-__global__ void __launch_bounds__(64)
-composite_lists_bwd(const TraceArgs A)
-{
-    __shared__ float fld[NFLD][65];
-    const int lane = threadIdx.x;
-    const FlushRole role = flush_role(A, lane);
-    const int nb = (A.D + 1) * (A.D + 1);
-    for (int base = blockIdx.x * 64; base < A.R; base += gridDim.x * 64) {
-        const int r = ray_of(A, base + lane);
-        const bool valid = r < A.R && A.hit_cnt[r < A.R ? r : 0] <= A.cap;
-        const int rr = r < A.R ? r : 0;
-        BwdRay B;
-        bwd_load_ray(A, rr, B);
-        BwdAcc acc;
-        bwd_init_acc(acc);
-        float basis[16];
-        sh_basis(A.D, B.ux, B.uy, B.uz, basis);
-        __syncthreads();
-        fld[19][lane] = B.ux; fld[20][lane] = B.uy; fld[21][lane] = B.uz;
-        const int n = valid ? A.n_used[rr] : 0;
-        const uint2 *list = A.hits + (size_t)rr * A.cap;
-        int nmax = n;
-        for (int o = 32; o > 0; o >>= 1) nmax = max(nmax, __shfl_xor(nmax, o));
-        for (int k = 0; k < nmax; k++) {
-            bool has = false;
-            int sid = 0;
-            float dc0 = 0.f, dc1 = 0.f, dc2 = 0.f, gv[15];
-#pragma unroll
-            for (int q = 0; q < 15; q++) gv[q] = 0.f;
-            if (k < n) {
-                sid = (int)list[k].y;
-                has = bwd_hit(A, B, acc, basis, nb, sid, dc0, dc1, dc2, gv);
-            }
-            flush_hits(A, fld, lane, role, has, sid, dc0, dc1, dc2, gv);
-        }
-        if (valid) bwd_store_ray(A, r, B, acc);
-    }
-}
-#endif  // ENVGS_DIAG
 
 // Backward of the list path, SURFEL-MAJOR per batch (the tracer's counterpart of the rasterizer's tile backward): one wavefront owns a
 // batch of 64 coherence-sorted rays, LANE = RAY.  It walks the batch's entries (distinct surfels); the surfel's record and SH block are

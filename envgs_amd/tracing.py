@@ -106,7 +106,6 @@ ROW_CAP = {}                 # tests only: ROW_CAP["force_per_ray"] pins the row
 COMPACT = {"on": True}
 HIT_CAP = {}                 # tests only: HIT_CAP["force"] pins the list capacity of every tracer (e.g. tiny, to exercise the overflow hand-off)
 SORT_RAYS = {"on": True}     # coherence-sort the rays (direction, origin) before tracing
-USE_RECORDS = {"on": True}   # atomic-free backward (one record per (batch, surfel) entry, grouped by surfel); False = cooperative atomic flush
 
 
 class CapState:
@@ -345,7 +344,7 @@ def trace_forward(nodes, ray_o, ray_d, means3D, shs, colors_precomp, others_prec
         nbatch = (R + 63) // 64
         # the small int32 scratch of a call comes out of ONE allocation (a dozen torch.empty calls are ~0.1 ms of host time, and this code runs
         # right behind the rasterizer's one host sync, where the GPU has nothing queued)
-        keep = _carve_i32(dev, dict(hit_cnt=R, n_used=R, spill=lib.envgs_trace_stack_spill_ints(R), surf_acc=2 * P * NCOPY, surf_cnt=P * NCOPY,
+        keep = _carve_i32(dev, dict(hit_cnt=R, n_used=R, surf_acc=2 * P * NCOPY, surf_cnt=P * NCOPY,
                                     surf_off=P * NCOPY, scan_temp=(max(sb, 1) + 3) // 4, ray_keys=2 * R, ray_order=2 * R, ray_sort_temp=(max(rb, 1) + 3) // 4,
                                     n_entries=2 * nbatch, row_off=R, batch_rows=2 * nbatch, row_blk=nbatch + 16))
         keep["n_entries"] = keep["n_entries"].view(nbatch, 2)
@@ -353,7 +352,7 @@ def trace_forward(nodes, ray_o, ray_d, means3D, shs, colors_precomp, others_prec
         srt = SORT_RAYS["on"]
         if shs is not None and shs.shape[1] == 16 and QUAD_SH["on"]:
             keep["sh_perm"] = torch.empty(P, 48, dtype=shs.dtype, device=dev)      # quad-permuted SH copy (envgs_trace.h: sh_perm)
-        if need_grad and USE_RECORDS["on"]:
+        if need_grad:
             # what the record backward needs from the forward: per-hit state, and the (batch, surfel) entries with their (lane, k) pairs.
             # COMPACT: rows follow the hits the rays actually have (a prefix sum of the hit counts, taken on the device between the collection
             # and the sort) instead of rays x capacity -- a ray uses a third of its capacity (42 -> 19 GB for a 1.92 M-ray stage)
@@ -378,7 +377,7 @@ def trace_forward(nodes, ray_o, ray_d, means3D, shs, colors_precomp, others_prec
         if "sparse_hits" in keep:
             sparse_cap = keep["sparse_hits"].shape[0] if SPARSE.get("cap") is None else min(int(SPARSE["cap"]), keep["sparse_hits"].shape[0])
         lists = _lib.TraceLists(keep["hit_lists"].data_ptr(), keep["hit_cnt"].data_ptr(), keep["n_used"].data_ptr(), cap,
-                                keep["spill"].data_ptr(), keep["surf_acc"].data_ptr(), keep["surf_cnt"].data_ptr(), keep["surf_off"].data_ptr(),
+                                keep["surf_acc"].data_ptr(), keep["surf_cnt"].data_ptr(), keep["surf_off"].data_ptr(),
                                 keep["scan_temp"].data_ptr(), sb, keep["ray_keys"].data_ptr() if srt else None,
                                 keep["ray_order"].data_ptr() if srt else None, keep["ray_sort_temp"].data_ptr() if srt else None, rb, None, 0,
                                 *[(keep[k].data_ptr() if k in keep else None) for k in ("hit_state", "entries", "pairs")],
@@ -448,7 +447,7 @@ def trace_backward(saved, g_rgb, g_dpt, g_acc, g_norm, g_aux, chain=None, allow_
     p = _lib.ptr
     s = saved
     lists = s["lists"]
-    defer = bool(allow_defer and lists is not None and USE_RECORDS["on"] and "hit_state" in s["keep"] and s["keep"].get("defer_reduce"))
+    defer = bool(allow_defer and lists is not None and "hit_state" in s["keep"] and s["keep"].get("defer_reduce"))
     chained = defer and chain is not None
     if chain is not None:
         if (not defer and chain[0].acc is not None) or (defer and chain[0].plain):
@@ -478,7 +477,7 @@ def trace_backward(saved, g_rgb, g_dpt, g_acc, g_norm, g_aux, chain=None, allow_
     if lists is not None and s["keep"].get("colour_only") and any(g_ is not None for g_ in (g_dpt, g_acc, g_norm, g_aux)):
         raise RuntimeError("SurfelTracer: set_colour_only_backward(True) promised that only the colour output would be differentiated, but a gradient "
                            "arrived for dpt / acc / norm / aux -- the forward kept the colour's per-hit state only; switch the promise off")
-    if lists is not None and USE_RECORDS["on"] and "hit_state" in s["keep"]:
+    if lists is not None and "hit_state" in s["keep"]:
         # atomic-free backward: one 256 B record per (batch, surfel) entry, grouped by surfel.  The count is known on the device
         # (inclusive scan of the per-surfel entry counts, done at the end of the forward); reading it is the one host sync here.
         s["keep"]["n_rec_event"].synchronize()         # copied at the end of the forward; long since complete

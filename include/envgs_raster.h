@@ -156,7 +156,7 @@ ENVGS_API int envgs_raster_backward(const envgs_raster_cfg *cfg, uint32_t N,
  * reference's counterpart is its `timer.record` sections, easyvolcap/utils/console_utils.py:615-693).
  * kernel_id: 0 project_surfels, 1 scan, 2 bin_tile_pairs (histograms + scans + scatter), 3 sort_tile_lists, 4 (unused),
  *            5 composite_fwd, 6 composite_bwd, 7 project_surfels_bwd, 8 bvh_build, 9 trace_fwd (whole forward), 10 trace_bwd
- *            (whole backward), 11 collect_hits, 12 sort_composite_fwd, 13 (unused), 14 K-buffer forward, 15 batch_surfel_bwd,
+ *            (whole backward), 11 collect_hits_coop, 12 sort_composite_fwd, 13 (unused), 14 K-buffer forward, 15 batch_surfel_bwd,
  *            16 K-buffer backward, 17 reduce_surfel_records, 18 register_hits, 19 fused_adam_multi, 20 l1_ssim_fwd, 21 l1_ssim_bwd.  envgs_prof_kernel_name(id) returns "" past the last id.
  * envgs_prof_read synchronises on the recorded events, returns the summed milliseconds and launch count
  * since the last read, and resets the counter.
@@ -172,12 +172,11 @@ ENVGS_API const char *envgs_prof_kernel_name(int kernel_id);
 /*
  * Diagnostic switches for experiments and tests (scratch/, tests/, bench.py --debug-*): process-global, all 0 in production.
  * The library never reads the environment; whoever sets a switch is responsible for reporting it (bench.py prints them).
- *   ENVGS_DBG_TRACE  bit mask: 8 = atomic-flush tracer backward instead of records, 16 = binary packet traversal instead of the 4-wide one,
- *                    64 = no coherence sort of the rays, 512 = per-ray collection kernel even when the rays are sorted,
+ *   ENVGS_DBG_TRACE  bit mask: 64 = no coherence sort of the rays,
  *                    1024 = packet stack limited to 2 entries (forces the stack-overflow hand-off to the K-buffer path; tests only),
- *                    2048 = one wavefront per 64-ray batch (collect_hits_packet4) instead of the cooperative workgroup (collect_hits_coop),
- *                    4096 / 8192 = cooperative collection with DEFERRED exact tests at 8 / 6 wavefronts per SIMD (round-5 A/B, diagnostic library),
- *                    16384 = forward_prepare on the caller's stream after the coherence sort instead of beside it on the second stream (round-6 A/B)
+ *                    16384 = forward_prepare on the caller's stream after the coherence sort instead of beside it on the second stream (round-6 A/B).
+ *                    8, 16, 512, 2048, 4096 and 8192 selected A/B kernels that have been deleted (profiles/DEAD_ENDS.md): envgs_trace_forward /
+ *                    envgs_trace_backward answer ENVGS_ERR_BAD_ARG to any of them, in both builds
  *   ENVGS_DBG_SEGMENTS  forward batch segments of the tracer (0 = default 2; 1 = single launch)
  */
 #define ENVGS_DBG_TRACE 0

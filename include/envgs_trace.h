@@ -79,7 +79,6 @@ typedef struct envgs_trace_lists {
     int32_t cap;             /* list capacity per ray, <= 1024; 0 disables the list path.  With cap > 0 (and max_trace_depth == 0, P and R below 2^24) BOTH
                                 calls take the list path and every buffer of their direction must be present: a missing one is ENVGS_ERR_BAD_ARG, never
                                 a silent fallback to the K-buffer kernels (the two calls could otherwise disagree about the path) */
-    int32_t *stack_spill;    /* envgs_trace_stack_spill_ints(R) int32 */
     uint64_t *surf_acc;      /* (P,8) packed accumulators of the forward (8 copies per surfel, chosen by ray index, spread same-address
                                 atomics): low 24 bits hit count, high 40 bits fixed-point weight */
     uint32_t *surf_cnt;      /* (P,8) (batch, surfel) entries per (surfel, copy) (list path only); a batch = 64 consecutive rays of the
@@ -207,7 +206,6 @@ ENVGS_API int envgs_bvh_quality(int32_t P, const float *nodes, float *out2, void
  * more than `cap` hits, and all rays when lists == NULL or bounces are requested, use the K-nearest-buffer traversal instead.
  * After the call counters[1] holds the largest hit_cnt (so the caller can size `cap` for the next call).
  */
-ENVGS_API size_t envgs_trace_stack_spill_ints(int32_t num_rays);
 ENVGS_API size_t envgs_trace_ray_sort_temp_bytes(int32_t num_rays);
 /* The coherence order envgs_trace_forward forms its 64-ray batches in, on its own (parity tests; a caller that wants to reuse one order
  * for several traces): pairs (num_rays x uint64, scratch) ends up holding every ray's (key << 32 | ray id), order (num_rays) the ray ids

@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of debug-switch values on ONE library:  bash scratch/ab_switch.sh "0 4096" [extra bench args]
+# A/B of debug-switch values on ONE library:  bash scratch/ab_switch.sh "0 16384" [extra bench args]
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
 VALS="$1"; shift
 for rep in 1 2; do for v in $VALS; do

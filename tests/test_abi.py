@@ -94,16 +94,22 @@ def test_product_path_fails_loudly_without_gpu_or_library(monkeypatch):
 
 
 def test_product_library_is_trimmed_of_the_diagnostic_kernels():
-    """the superseded A/B kernels (three earlier collection kernels, the per-ray atomic-flush list backward) are compiled only with
-    -DENVGS_DIAG into libenvgs_hip_diag.so, which tests and `bench.py --diag` select explicitly; the product library does not contain them
-    (and rejects the debug switches that would ask for them).  Both builds export the whole C-ABI."""
+    """The superseded A/B kernels (three earlier collection kernels, the per-ray atomic-flush list backward, the deferred-exact-test form of the
+    cooperative collection) are deleted: neither library contains them, and both reject the debug switches that asked for them.  What
+    -DENVGS_DIAG still adds to libenvgs_hip_diag.so -- which tests and `bench.py --diag` select explicitly -- is the exact-math instantiations of
+    the raster compositing kernels; the product library does not contain those.  Both builds export the whole C-ABI."""
     from envgs_amd import _lib, build
     prod = open(build.LIB, "rb").read(); diag = open(build.LIB_DIAG, "rb").read()
     for name in (b"collect_hits_packet4", b"collect_hits_packet", b"composite_lists_bwd"):
-        assert name not in prod and name in diag, name
+        assert name not in prod and name not in diag, name
     for name in (b"collect_hits_coop", b"sort_composite_fwd", b"batch_surfel_bwd", b"composite_bwd"):
         assert name in prod and name in diag, name
-    assert b"collect_hits_coopILb1E" not in prod and b"collect_hits_coopILb1E" in diag        # round 5's deferred-exact-test form: measured slower, A/B only
+    assert b"collect_hits_coopILb1E" not in prod and b"collect_hits_coopILb1E" not in diag    # round 5's deferred-exact-test form: measured slower, deleted
+    # EXACT = true (ENVGS_DBG_RASTER_EXACT): composite_fwd<C, AUDIT, EXACT> and composite_bwd<C, EXACT>, for each channel count
+    for name in (b"composite_fwdILi%dELb0ELb1E" % c for c in (3, 5, 7)):
+        assert name not in prod and name in diag, name
+    for name in (b"composite_bwdILi%dELb1E" % c for c in (3, 5, 7)):
+        assert name not in prod and name in diag, name
     old = _lib.select("diag")
     try:
         lib = _lib.load()

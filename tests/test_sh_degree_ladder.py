@@ -8,8 +8,8 @@ would start moving them).  The SH colour and its gradient are evaluated in about
   rasterizer   project_surfels (raster_project.hip), sh_record_bwd_q16 (glue.hip: fp32, M = 16), the one-lane ladder of project_surfels_bwd
                (raster_project_bwd.hip: fp16 storage or M != 16, its k = nb..M zero fill, its culled-surfel branch)
   tracer       quad_sh_color over the permuted copy (trace_lists.hip), surfel_color / load_sh (trace_common.h: M = 16 fp16, M = 16 fp32, generic),
-               the K-buffer kernels (trace_kbuffer.hip), batch_surfel_bwd's staging, sparse_hits_bwd, reduce_store (trace_surfel_bwd.hip), the
-               atomic flush (trace_common.h: sh_lane), bwd_hit
+               the K-buffer kernels (trace_kbuffer.hip: the atomic flush of trace_common.h's sh_lane, bwd_hit), batch_surfel_bwd's staging,
+               sparse_hits_bwd, reduce_store (trace_surfel_bwd.hip)
   fused glue   sh_colors_* (glue.hip; tests/test_fused_glue.py)
 
 Inputs: `ladder_shs` gives every inactive coefficient a value of the order of 1e3 (finite, representable in fp16), so that a leak of one of them misses
@@ -228,7 +228,7 @@ def _check_inactive_gradient(res, deg, M):
     assert (np.abs(got[:, :nb]).reshape(got.shape[0], -1).max(-1) > 0)[hit].all(), "a surfel that was hit has no gradient on its active coefficients"
 
 
-TRACER_FORMS = ("default", "per_lane", "fp16", "sparse", "kbuffer", "flush")
+TRACER_FORMS = ("default", "per_lane", "fp16", "sparse", "kbuffer")
 
 
 def _tracer_case(test, form, deg, M=16):
@@ -245,8 +245,6 @@ def _tracer_case(test, form, deg, M=16):
         kw = dict(hip_ctx=_Switch(sparse="on", sparse_poison=SPARSE_POISON), after_hip=lambda: _check_sparse_list(test))        # (asserts sparse_invalid == 0)
     elif form == "kbuffer":
         kw = dict(hip_ctx=_Switch(force_cap=8), require_lists=False)
-    elif form == "flush":
-        kw = dict(hip_ctx=_Switch(records=False))
     res = _parity(test, g, ro, rd, TRACE_BG, deg, True, False, others=True, **kw)
     assert res["ref"]["nhits"].mean() > 10
     if form == "sparse":
@@ -267,8 +265,7 @@ def test_tracer_ladder(form, deg, request):
     per_lane  load_sh M = 16 fp32 (its nq rounding at nb = 1 and 9)
     fp16      both fp16 loaders and the fp16 staging, against the oracle on the rounded values
     sparse    sparse_hits_bwd (sparse_invalid == 0, entries filed)
-    kbuffer   trace_kbuffer.hip forward and bwd_hit for the rays over an 8-entry list capacity
-    flush     the per-ray atomic flush of the diagnostic library (trace_common.h: sh_lane)"""
+    kbuffer   trace_kbuffer.hip forward, bwd_hit and the atomic flush (trace_common.h: sh_lane) for the rays over an 8-entry list capacity"""
     _tracer_case(request.node.name, form, deg)
 
 

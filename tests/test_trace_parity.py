@@ -293,8 +293,8 @@ class _Switch:
     def __enter__(self):
         from envgs_amd import tracing, _lib
         self.old = {}
-        # the A/B kernels these switches select live in the DIAGNOSTIC build only (libenvgs_hip_diag.so; the product library was trimmed of them)
-        self.lib_kind = _lib.select("diag") if any(k in self.kw for k in ("records", "sort_rays", "debug_trace")) else None
+        # diag=True: the diagnostic build (libenvgs_hip_diag.so: the product kernels plus the exact-math raster kernels and the LDS alignment trap)
+        self.lib_kind = _lib.select("diag") if self.kw.get("diag") else None
         for k, v in self.kw.items():
             if k == "force_cap":
                 self.old[k] = dict(tracing.HIT_CAP)
@@ -303,7 +303,6 @@ class _Switch:
                 self.old[k] = tracing.trace_forward
                 orig = tracing.trace_forward
                 tracing.trace_forward = lambda *a, **kk: orig(*a, **{**kk, "use_lists": False})
-            elif k == "records": self.old[k] = tracing.USE_RECORDS["on"]; tracing.USE_RECORDS["on"] = v
             elif k == "rows_per_ray": self.old[k] = dict(tracing.ROW_CAP); tracing.ROW_CAP["force_per_ray"] = v
             elif k == "compact": self.old[k] = tracing.COMPACT["on"]; tracing.COMPACT["on"] = v
             elif k == "sparse": self.old[k] = tracing.SPARSE["mode"]; tracing.SPARSE["mode"] = v
@@ -319,7 +318,6 @@ class _Switch:
         for k, v in self.old.items():
             if k == "force_cap": tracing.HIT_CAP.clear(); tracing.HIT_CAP.update(v)
             elif k == "no_lists": tracing.trace_forward = v
-            elif k == "records": tracing.USE_RECORDS["on"] = v
             elif k == "rows_per_ray": tracing.ROW_CAP.clear(); tracing.ROW_CAP.update(v)
             elif k == "compact": tracing.COMPACT["on"] = v
             elif k == "sparse": tracing.SPARSE["mode"] = v
@@ -633,13 +631,13 @@ def test_trace_edge_cases():
     assert rgb2.shape == (1, 64, 3) and torch.isfinite(rgb2).all()
 
 
-@pytest.mark.parametrize("force_cap,records", [(12, True), (20, False), (0, True), (512, False)])
-def test_trace_list_path_overflow_handoff(force_cap, records, request):
+@pytest.mark.parametrize("force_cap", [12, 20, 0, 512])
+def test_trace_list_path_overflow_handoff(force_cap, request):
     """Per-ray hit lists with a tiny capacity: rays that overflow must be handed to the K-buffer kernels and give the same
     result as the oracle (forward and backward); force_cap=0 disables the list path entirely."""
     g, ro, rd = trace_scene(P=600, R=512, seed=11, camera=False)
     g["scales"] = g["scales"] * 0.6
-    sw = _Switch(records=records, **({"force_cap": force_cap} if force_cap else {"no_lists": True}))
+    sw = _Switch(**({"force_cap": force_cap} if force_cap else {"no_lists": True}))
     res = _parity(request.node.name, g, ro, rd, torch.tensor([0.1, 0.2, 0.3]), 3, True, False, seed=3, hip_ctx=sw, require_lists=bool(force_cap))
     if force_cap and force_cap < 100:
         assert res["cnt"]["max_list"] > force_cap                 # the overflow path really ran
@@ -735,7 +733,8 @@ def test_fragile_rays_differ_from_the_oracle_by_threshold_hits_only():
 def test_trace_batch_table_overflow_and_unsorted_rays(sort_rays, request):
     """Incoherent rays through a dense set: a 64-ray batch blends far more distinct surfels than its 1024-slot merge table holds, so part
     of the hits become single entries (filed from the top of the batch's region) -- forward weights and every gradient must still match
-    the oracle; with the coherence sort disabled the per-ray collection kernel feeds the same batch kernels."""
+    the oracle; with the coherence sort disabled the cooperative collection takes the rays in the order given (the (R, cap) layouts) and feeds
+    the same batch kernels."""
     from envgs_amd import tracing
     gen = torch.Generator().manual_seed(33)
     P, R = 6000, 1000                                                   # R is not a multiple of 64: a ragged last batch
@@ -1242,10 +1241,9 @@ def test_trace_rebuild_requests_are_served_by_refits_while_the_tree_is_young():
         assert trace(t, m0)[1] == "build"
 
 
-@pytest.mark.parametrize("switch", [2048, 16, 512])
-def test_trace_diagnostic_collection_kernels(switch, request):
-    """The collection kernels kept for A/B measurements behind envgs_debug_set (2048: one wavefront per batch over the 4-wide nodes, 16: over the
-    binary nodes, 512: per-ray traversal) must keep producing the contract's results."""
+def test_trace_diagnostic_collection_kernels(request):
+    """The diagnostic library's collection kernel -- the product's cooperative kernel plus the trap on a misaligned LDS bin table -- must keep
+    producing the contract's results (the trap would abort the run)."""
     P, R = 2500, 1536
     e = synth.env_gaussians(P, seed=13)
     gen = torch.Generator().manual_seed(14)
@@ -1253,9 +1251,38 @@ def test_trace_diagnostic_collection_kernels(switch, request):
     rd = torch.randn(R, 3, generator=gen); rd = rd / rd.norm(dim=-1, keepdim=True)
     g = dict(means3D=e["means3D"] * 0.06, scales=e["scales"] * 0.3, rotations=e["rotations"], opacities=e["opacities"], shs=e["shs"],
              others=torch.rand(P, 2, generator=gen), colors_precomp=torch.rand(P, 3, generator=gen))
-    res = _parity(request.node.name, g, ro, rd, torch.tensor([0.3, 0.2, 0.1]), 3, True, False, seed=15, hip_ctx=_Switch(debug_trace=switch),
+    res = _parity(request.node.name, g, ro, rd, torch.tensor([0.3, 0.2, 0.1]), 3, True, False, seed=15, hip_ctx=_Switch(diag=True),
                   which=("dmeans3D", "dopacities", "dcolor", "dray_o", "dray_d"))
     assert res["cnt"]["hits"] > 20 * res["R"]
+
+
+def test_trace_removed_debug_switches_are_refused():
+    """The ENVGS_DBG_TRACE bits of the deleted A/B kernels (8, 16, 512, 2048, 4096): a traced forward answers "bad argument" in the product AND in
+    the diagnostic library, never a silent run of the default kernels under a switch that names another one."""
+    import diff_surfel_tracing as mod
+    from envgs_amd import _lib
+    dev = torch.device("cuda:0")
+    g, ro, rd = trace_scene(P=50, R=64, seed=2, camera=False)
+    gd = {k: g[k].to(dev) for k in ("means3D", "scales", "rotations", "opacities", "shs")}
+    v, f = synth.get_disks(gd["means3D"], gd["scales"], gd["rotations"])
+    tracer = mod.SurfelTracer()
+    tracer.build_acceleration_structure(v, f, rebuild=True)
+    kw = dict(means3D=gd["means3D"], grads3D=None, shs=gd["shs"], colors_precomp=None, others_precomp=None, opacities=gd["opacities"], scales=gd["scales"],
+              rotations=gd["rotations"], cov3D_precomp=None, tracer_settings=_settings(mod, torch.zeros(3), 1, dev), start_from_first=False)
+    for kind in ("product", "diag"):
+        old = _lib.select(kind)
+        try:
+            before = _lib.load().envgs_debug_get(0)
+            for bit in (8, 16, 512, 2048, 4096):
+                with _Switch(debug_trace=before | bit):
+                    with pytest.raises(RuntimeError, match="bad argument"):
+                        tracer(ro.to(dev), rd.to(dev), v, **kw)
+                assert _lib.load().envgs_debug_get(0) == before, (kind, bit)    # the switch is restored ...
+            rgb, *_ = tracer(ro.to(dev), rd.to(dev), v, **kw)                   # ... and the same call is accepted again
+            torch.cuda.synchronize()
+            assert rgb.shape == (64, 3) and torch.isfinite(rgb).all(), kind
+        finally:
+            _lib.select(old)
 
 
 @pytest.mark.parametrize("P,R", [(50, 0), (0, 64), (0, 0), (1, 64)])
@@ -1714,7 +1741,7 @@ def test_trace_c_abi_refuses_a_lists_struct_with_a_missing_buffer():
     if full.hit_lists is not None:
         assert fwd(full) == 0                                                   # the complete struct is accepted
         torch.cuda.synchronize()
-    for field in ("hit_lists", "stack_spill", "surf_acc", "scan_temp", "hit_cnt"):
+    for field in ("hit_lists", "surf_acc", "scan_temp", "hit_cnt"):
         bad = clone(full); setattr(bad, field, None)
         assert fwd(bad) == -1, field                                            # ... and with any forward buffer missing it is refused, not re-routed
     gup = torch.zeros(R, 3, **f32)
