@@ -1,10 +1,12 @@
-"""CPU: the mesh oracle's own acceptance test on analytic level sets, the mesh PLY round trip, and the argument checks of the mesh C-ABI that need
-no GPU.  (The HIP kernels are compared against this oracle in tests/test_mesh_gpu.py.)"""
+"""CPU: the mesh oracle's own acceptance test on analytic level sets, the case table of tests/mesh_cases.py on the oracle alone (every
+configuration is one the GPU comparison can judge), the mesh PLY round trip, and the argument checks of the mesh C-ABI that need no GPU.
+(The HIP kernels are compared against this oracle in tests/test_mesh_gpu.py and tests/test_mesh_shapes_gpu.py.)"""
 import ctypes
 
 import numpy as np
 import pytest
 
+from tests import mesh_cases as mc
 from tests import mesh_oracle as mo
 
 DIMS = (14, 12, 10)
@@ -80,6 +82,86 @@ def test_oracle_integration_float32_and_float64_agree_off_the_fragile_voxels():
         d, w, c = mo.integrate_voxel(ijk, (1.0, 0.0, (0.0, 0.0, 0.0)), origin, voxel, [view, view], 64.0, 0.3, [(0, 0, False)] * 2)
         at = (ijk[2], ijk[1], ijk[0])
         assert d == D32[at] and w == W32[at] and all(c[q] == C32[(q,) + at] for q in range(3))
+
+
+@pytest.mark.parametrize("name", list(mc.INTEGRATION))
+def test_integration_case_table_meets_the_conditions_of_check_fused(name):
+    """Every integration configuration of tests/mesh_cases.py, on the oracle alone: what test_mesh_gpu.check_fused asserts before it compares
+    anything.  The 1 % cap on the fragile share is a condition, not a measurement: a row that breaks it gets another origin, off the cameras'
+    symmetry planes."""
+    c = mc.oracle_conditions(name)
+    print("%s: fragile %d of %d voxels (%.2f %%), observed %d, unobserved %d, f32/f64 weight disagreements off the fragile voxels %d"
+          % (name, c.fragile, c.n, 100 * c.share, c.observed, c.unobserved, c.disagree))
+    assert c.share <= 0.01
+    assert c.observed > 0.02 * c.n
+    assert c.unobserved >= 1
+    assert c.disagree == 0
+    assert c.finite                                             # NaN / inf depth pixels are skipped or give val = 1, never a NaN in the volume
+    dims = mc.INTEGRATION[name][0]
+    if max(dims) > 4:                                           # beyond the tiny rows: the surface itself is seen, by overlapping views
+        assert c.max_weight >= 2.0 and c.min_tsdf < -0.4
+
+
+def test_integration_case_table_reaches_the_paths_it_names():
+    n = {k: int(np.prod(v[0])) for k, v in mc.INTEGRATION.items()}
+    assert [n[k] % 4 for k in ("37x35x33", "41x37x33", "5x3x2", "7x5x3", "40x36x32")] == [3, 1, 2, 1, 0]
+    assert n["2x3x171"] == 1026 and n["40x36x32"] % 1024 == 0 and mc.INTEGRATION["1027x2x2"][0][0] > 1024
+    dims, voxel, lo, _ = mc.INTEGRATION["ragged e2e"]            # the dimensions TSDFVolume(lo, hi, voxel) rounds to: odd on every axis
+    assert tuple(int(np.ceil((h - l) / voxel - 1e-9)) + 1 for l, h in zip(lo, mc.E2E_HI)) == dims and all(d % 2 == 1 and d <= 45 for d in dims)
+    kinds = {v[3] for v in mc.INTEGRATION.values()}
+    assert kinds == {"orbit", "inside", "mixed", "e2e"}
+    inside = mc.view_set("inside")
+    assert len(inside) == 5
+    X, Y, Z = mo.voxel_positions((37, 35, 33), mc.INTEGRATION["inside"][2], 0.05, np.float64)
+    for v in inside:                                            # the camera stands inside the sphere: voxels on both sides of its image plane
+        centre = -v.R.astype(np.float64).T @ v.T
+        assert np.linalg.norm(centre - np.array(mc.base.SPHERE_C)) < mc.base.SPHERE_R
+        zc = v.R[2, 0] * X + v.R[2, 1] * Y + v.R[2, 2] * Z + v.T[2]
+        assert (zc > 0).mean() > 0.1 and (zc <= 0).mean() > 0.1
+        assert np.isnan(v.depth).sum() > 20 and np.isposinf(v.depth).sum() > 20 and (v.depth < 0).sum() > 20
+    mixed = mc.view_set("mixed")
+    assert len({v.depth.shape for v in mixed}) == 2 and len({float(v.trunc) for v in mixed}) > 2 and len({float(v.depth_max) for v in mixed}) > 2
+    assert {v.rgb is None for v in mixed} == {True, False}
+    for v in mixed:                                             # depth_max cuts a part of every view it is set on, never all of it
+        if np.isfinite(v.depth_max):
+            assert ((v.depth > 0) & (v.depth <= v.depth_max)).any() and (v.depth > v.depth_max).any()
+
+
+@pytest.mark.parametrize("name", mc.EXTRACTION)
+def test_extraction_case_table_gives_the_meshes_it_names(name):
+    e = mc.extraction(name)
+    nz, ny, nx = e.tsdf.shape
+    weight = np.ones_like(e.tsdf) if e.weight is None else e.weight
+    ref = mo.marching_tetrahedra(e.tsdf, weight, None, e.origin, e.voxel, level=e.level, min_weight=e.min_weight)
+    V, F = ref.vertices.shape[0], ref.faces.shape[0]
+    top = mo.mesh_topology(ref.faces, V)
+    print("%s: V %d F %d, closed %s, euler %d" % (name, V, F, top.closed_oriented, top.euler))
+    assert V > 0 and F > 0 and top.all_referenced and np.isfinite(ref.vertices).all()
+    assert top.closed_oriented == (e.euler is not None) and (e.euler is None or top.euler == e.euler)
+    if name == "thin 2x2x2":
+        assert (V, F) == (7, 6)                                 # one corner inside: its 7 edges, the 6 tetrahedra around it
+    if name in ("thin 2x2x300", "thin 300x2x2", "thin 2x300x2", "thin 257x2x2"):
+        assert (V, F) == (18, 16)
+    if name == "big":
+        assert (V, F) == (20100, 40196) and (nx * ny * nz + 255) // 256 > 1024
+    if "level" in name or "sample" in name:                     # samples exactly on the level: not inside, t == 0 on the edges they own
+        flat, d = e.tsdf.reshape(-1), np.array(mo.SLOT_DIRS)[ref.vertex_slot]
+        t0 = flat[ref.vertex_owner] == np.float32(e.level)
+        t1 = flat[ref.vertex_owner + d[:, 0] + d[:, 1] * nx + d[:, 2] * nx * ny] == np.float32(e.level)
+        print("%s: %d samples equal the level, %d vertices with t == 0, %d with t == 1" % (name, (e.tsdf == np.float32(e.level)).sum(), t0.sum(), t1.sum()))
+        assert {"plane on the level": t0.sum() >= 3, "plane under the level": t1.sum() >= 3, "torus on a sample": t0.sum() + t1.sum() >= 1}[name]
+    if name.startswith("last corner"):
+        assert nx * ny * nz % 4 == 3 and ref.face_cell.max() == ((nz - 2) * ny + ny - 2) * nx + nx - 2
+    if name.startswith("min_weight"):
+        assert sorted(np.unique(weight)) == [0.0, 0.5, 1.0, 3.0]
+        ones = mo.marching_tetrahedra(e.tsdf, weight, None, e.origin, e.voxel, min_weight=1.0)
+        full = mo.marching_tetrahedra(e.tsdf, np.ones_like(weight), None, e.origin, e.voxel)
+        # the threshold is what decides: 0.75 separates the weights as 1 does, 0.5 lets the 0.5 voxels in
+        assert F < full.faces.shape[0] and (F == ones.faces.shape[0] if e.min_weight == 0.75 else F > ones.faces.shape[0])
+        ck, r = np.divmod(ref.face_cell, nx * ny)
+        cj, ci = np.divmod(r, nx)
+        corner = np.stack([weight[ck + ((c >> 2) & 1), cj + ((c >> 1) & 1), ci + (c & 1)] for c in range(8)])
+        assert (corner >= e.min_weight).all() and (corner == 0.5).any() == (e.min_weight == 0.5)
 
 
 def test_mesh_ply_round_trip(tmp_path, sphere):
