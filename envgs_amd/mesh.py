@@ -1,4 +1,5 @@
-"""Mesh extraction (include/envgs_mesh.h, csrc/mesh.hip): TSDF fusion of rendered depth into a dense volume, marching tetrahedra over it.
+"""Mesh extraction (include/envgs_mesh.h, csrc/mesh.hip, csrc/mesh_clean.hip): TSDF fusion of rendered depth into a dense volume, marching
+tetrahedra over it, and the clean-up of the mesh: connected components, order-preserving face selection, removal of small components.
 
 PARITY UNPINNED: the reference ships a fuser (easyvolcap/utils/tsdf_utils.py, fusion_utils.py, runners/visualizers/geometry_visualizer.py) that
 cannot run as it stands and leaves the marching step to libraries outside it, so the semantics are this project's ("Mesh extraction");
@@ -6,7 +7,7 @@ tests/mesh_oracle.py restates them independently.  There is no CPU path: CPU ten
 
     vol = TSDFVolume((-1, -1, -1), (1, 1, 1), voxel_size=0.01)
     fuse_surfels(vol, cameras, base, sh_degree=3)
-    mesh = vol.extract()
+    mesh = clean(vol.extract())                 # csrc/mesh_clean.hip: components(), select_faces() and the 2DGS rule built on them
     ckpt.save_mesh_ply("scene.ply", mesh.vertices, mesh.faces, mesh.colors)
 """
 import math
@@ -155,6 +156,92 @@ class TSDFVolume:
         colors = torch.empty(V, 3, dtype=torch.float32, device=dev) if self.rgb is not None else None
         _lib.check(lib.envgs_mesh_extract(vol, float(level), p(temp), tb, V, F, p(vertices), p(colors), p(faces), _stream(dev)), "envgs_mesh_extract")
         return Mesh(vertices=vertices, faces=faces, colors=colors)
+
+
+# ---- clean-up (csrc/mesh_clean.hip) ---------------------------------------------------------------------------------------------------------------
+def _mesh_tensors(mesh, what):
+    """-> (vertices, faces, colors) of a Mesh-like namespace, checked: contiguous device tensors of the documented dtypes and shapes."""
+    v, f, c = mesh.vertices, mesh.faces, getattr(mesh, "colors", None)
+    _need_gpu(v, what)
+    _need_gpu(f, what)
+    if v.dtype != torch.float32 or v.dim() != 2 or v.shape[1] != 3 or not v.is_contiguous():
+        raise ValueError("%s: vertices must be a contiguous (V,3) float32 tensor" % what)
+    if f.dtype != torch.int32 or f.dim() != 2 or f.shape[1] != 3 or not f.is_contiguous():
+        raise ValueError("%s: faces must be a contiguous (F,3) int32 tensor" % what)
+    if c is not None:
+        _need_gpu(c, what)
+        if c.dtype != torch.float32 or tuple(c.shape) != tuple(v.shape) or not c.is_contiguous():
+            raise ValueError("%s: colors must be a contiguous (V,3) float32 tensor" % what)
+    if f.device != v.device or (c is not None and c.device != v.device):
+        raise ValueError("%s: vertices, faces and colors must be on one device" % what)
+    if v.shape[0] >= 2 ** 31 or f.shape[0] >= 2 ** 31:
+        raise ValueError("%s: %d vertices / %d faces do not fit int32 indices" % (what, v.shape[0], f.shape[0]))
+    return v, f, c
+
+
+def components(mesh):
+    """Connected components of the mesh: faces are connected iff they share a vertex index (include/envgs_mesh.h).  Components are numbered by
+    ascending smallest vertex index; a face with an index outside [0, V) is ignored (label -1), as is an unreferenced vertex.
+    -> namespace(count: int, vertex_label (V,) i32, face_label (F,) i32, faces (C,) i32, vertices (C,) i32: per-component counts), device
+    tensors.  One host sync: the read-back of the count."""
+    v, f, _ = _mesh_tensors(mesh, "components")
+    lib = _lib.load()
+    dev = v.device
+    V, F = v.shape[0], f.shape[0]
+    tb = lib.envgs_mesh_components_temp_bytes(V, F)
+    temp = torch.empty(tb, dtype=torch.uint8, device=dev)
+    vertex_label = torch.empty(V, dtype=torch.int32, device=dev)
+    face_label = torch.empty(F, dtype=torch.int32, device=dev)
+    comp_faces = torch.empty(min(V, F), dtype=torch.int32, device=dev)
+    comp_vertices = torch.empty(min(V, F), dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    p = _lib.ptr
+    _lib.check(lib.envgs_mesh_components(V, F, p(f), p(temp), tb, p(vertex_label), p(face_label), p(comp_faces), p(comp_vertices), p(count), _stream(dev)),
+               "envgs_mesh_components")
+    C = int(count.item())
+    return SimpleNamespace(count=C, vertex_label=vertex_label, face_label=face_label, faces=comp_faces[:C], vertices=comp_vertices[:C])
+
+
+def select_faces(mesh, keep, return_index=False):
+    """The mesh of the faces with keep != 0 (`keep`: (F,) bool or uint8 device tensor) and of the vertices they name, both in their old relative
+    order, faces re-indexed, vertices and colours copied bit for bit.  Faces with an index outside [0, V) are never selected.
+    -> Mesh, or (Mesh, vertex_index (V',) i32: the old index of each new vertex) with return_index.  One host sync: the read-back of (V', F')."""
+    v, f, c = _mesh_tensors(mesh, "select_faces")
+    _need_gpu(keep, "select_faces")
+    if keep.dtype == torch.bool and keep.is_contiguous():
+        keep = keep.view(torch.uint8)                           # a bool tensor stores 0 / 1 bytes
+    if keep.dtype != torch.uint8 or keep.dim() != 1 or keep.shape[0] != f.shape[0] or not keep.is_contiguous() or keep.device != v.device:
+        raise ValueError("select_faces: keep must be a contiguous (F,) bool or uint8 tensor on the mesh's device")
+    lib = _lib.load()
+    dev = v.device
+    V, F = v.shape[0], f.shape[0]
+    tb = lib.envgs_mesh_select_temp_bytes(V, F)
+    temp = torch.empty(tb, dtype=torch.uint8, device=dev)
+    totals = torch.empty(2, dtype=torch.int32, device=dev)
+    p = _lib.ptr
+    _lib.check(lib.envgs_mesh_select_count(V, F, p(f), p(keep), p(temp), tb, p(totals), _stream(dev)), "envgs_mesh_select_count")
+    Vo, Fo = [int(x) for x in totals.tolist()]
+    vertices = torch.empty(Vo, 3, dtype=torch.float32, device=dev)
+    faces = torch.empty(Fo, 3, dtype=torch.int32, device=dev)
+    colors = torch.empty(Vo, 3, dtype=torch.float32, device=dev) if c is not None else None
+    index = torch.empty(Vo, dtype=torch.int32, device=dev) if return_index else None
+    _lib.check(lib.envgs_mesh_select_emit(V, F, p(v), p(c), p(f), p(keep), p(temp), tb, Vo, Fo, p(vertices), p(colors), p(faces), p(index), _stream(dev)),
+               "envgs_mesh_select_emit")
+    out = Mesh(vertices=vertices, faces=faces, colors=colors)
+    return (out, index) if return_index else out
+
+
+def clean(mesh, keep_largest=50, min_faces=50):
+    """Drops the debris of a fused mesh, by the rule of the 2DGS mesh post-processing (adopted here as this project's choice): a component is
+    kept iff its face count >= max(min_faces, face count of the keep_largest-th largest component); the second term is 0 when keep_largest is
+    None, 0 or at least the number of components.  Ties at the threshold are all kept.  The choice is made on the (C,) tables on the device;
+    two host syncs in all: the one of components() and the one of select_faces()."""
+    comp = components(mesh)
+    threshold = torch.full((), int(min_faces), dtype=torch.int32, device=comp.faces.device)
+    if keep_largest is not None and 0 < int(keep_largest) < comp.count:
+        threshold = torch.maximum(threshold, torch.sort(comp.faces, descending=True).values[int(keep_largest) - 1])
+    kept = torch.cat([comp.faces >= threshold, torch.zeros(1, dtype=torch.bool, device=comp.faces.device)])      # row -1: the ignored faces
+    return select_faces(mesh, kept[comp.face_label.long()])
 
 
 def surface_depth(allmap, depth_ratio=0.0):

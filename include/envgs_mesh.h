@@ -1,9 +1,10 @@
 /*
- * envgs_mesh.h -- C-ABI of mesh extraction: TSDF fusion of depth maps into a dense volume, and marching tetrahedra over it.
+ * envgs_mesh.h -- C-ABI of mesh extraction: TSDF fusion of depth maps into a dense volume, marching tetrahedra over it, and the clean-up of
+ * the extracted (or any other indexed) triangle mesh: connected components and order-preserving face selection.
  *
  * PARITY UNPINNED: the reference's fuser (easyvolcap/utils/tsdf_utils.py) cannot run as shipped and hands the marching step to libraries that
- * are not part of it, so nothing of it is recorded as a golden fixture.  The semantics below are this project's; tests/mesh_oracle.py restates
- * them independently in NumPy ("Mesh extraction").
+ * are not part of it, so nothing of it is recorded as a golden fixture.  The semantics below are this project's; tests/mesh_oracle.py and
+ * tests/mesh_clean_oracle.py restate them independently in NumPy ("Mesh extraction").
  *
  * The library never allocates: the caller owns every buffer.  Bad arguments return ENVGS_ERR_BAD_ARG before any GPU work.
  */
@@ -78,6 +79,47 @@ ENVGS_API int envgs_mesh_count(const envgs_tsdf_volume *vol, float level, float 
  * No atomics: two runs give identical bytes.  Nothing at or beyond row V / F is written. */
 ENVGS_API int envgs_mesh_extract(const envgs_tsdf_volume *vol, float level, const void *temp, size_t temp_bytes, uint32_t V, uint32_t F,
                                  float *vertices, float *colors, int32_t *faces, void *stream);
+
+/* ---- clean-up of an indexed triangle mesh (csrc/mesh_clean.hip) ----------------------------------------------------------------------------
+ * The mesh may come from anywhere (a loaded PLY, not only envgs_mesh_extract): V vertices, faces (F,3) int32, V and F below 2^31.
+ * A face with any index outside [0, V) is IGNORED throughout: never dereferenced, joined to nothing, labelled -1, never selected.
+ * V = 0 or F = 0 are valid.  Pointers to arrays of zero rows may be NULL; every other NULL, a count at or above 2^31 and a `temp` that is not
+ * 16-byte aligned return ENVGS_ERR_BAD_ARG before any GPU work, a short `temp` ENVGS_ERR_TEMP_TOO_SMALL.  Integer work only (vertices and
+ * colours are copied bit for bit): two runs give identical bytes. */
+
+/* Scratch bytes of envgs_mesh_components: 16 B per vertex plus the per-workgroup totals (0 if a count is out of range). */
+ENVGS_API size_t envgs_mesh_components_temp_bytes(uint32_t V, uint32_t F);
+
+/* Connected components.  Two faces are connected iff they share a vertex INDEX: the components are those of the graph on the vertices whose
+ * edges are the triangle sides.  That is a superset of adjacency across a shared edge; on the output of envgs_mesh_extract the two differ only
+ * at pinch vertices (sheets that touch in one vertex without sharing an edge are one component here).  Vertices at equal positions under
+ * different indices are different vertices.  A degenerate face (a,a,b) is an ordinary face that joins a and b; (a,a,a) is a component of one
+ * vertex and one face.  A vertex no (valid) face names belongs to no component.
+ * Components are numbered 0 .. C-1 by ascending smallest vertex index, so every output is independent of scheduling and of the order of the faces.
+ *   vertex_label (V)  component of the vertex, -1 if unreferenced          face_label (F)  component of the face, -1 if ignored
+ *   comp_faces, comp_vertices (min(V,F))  faces / vertices per component: rows 0 .. C-1 are written, C <= min(V, F)
+ *   count             C, left on the device for the caller's one read-back */
+ENVGS_API int envgs_mesh_components(uint32_t V, uint32_t F, const int32_t *faces, void *temp, size_t temp_bytes, int32_t *vertex_label,
+                                    int32_t *face_label, int32_t *comp_faces, int32_t *comp_vertices, uint32_t *count, void *stream);
+
+/* Scratch bytes of envgs_mesh_select_count / envgs_mesh_select_emit: 2 B per vertex plus the per-workgroup totals (0 if out of range). */
+ENVGS_API size_t envgs_mesh_select_temp_bytes(uint32_t V, uint32_t F);
+
+/* Order-preserving selection.  A face survives iff keep[f] != 0 and its three indices are in range; a vertex survives iff a surviving face names
+ * it.  Survivors keep their relative order (on the output of envgs_mesh_extract: vertices ascending by (owner voxel, slot), faces grouped by
+ * ascending cell), the faces are re-indexed.
+ * envgs_mesh_select_count marks and scans, and leaves totals[0] = V', totals[1] = F' on the device; the caller reads them back (the one host
+ * sync) and sizes the outputs.  `temp` carries the plan to envgs_mesh_select_emit and must not be touched in between; faces and keep must be
+ * the same there. */
+ENVGS_API int envgs_mesh_select_count(uint32_t V, uint32_t F, const int32_t *faces, const uint8_t *keep, void *temp, size_t temp_bytes,
+                                      uint32_t *totals, void *stream);
+
+/* out_vertices (V',3) and out_colors (V',3; NULL: none, else `colors` must be given) are the surviving rows of vertices / colors, bit for bit;
+ * out_faces (F',3) the surviving faces in the new numbering; vertex_index (V') the old index of each new vertex (NULL: not wanted).
+ * Vout <= V and Fout <= F are the totals read back; nothing at or beyond row Vout / Fout is written. */
+ENVGS_API int envgs_mesh_select_emit(uint32_t V, uint32_t F, const float *vertices, const float *colors, const int32_t *faces, const uint8_t *keep,
+                                     const void *temp, size_t temp_bytes, uint32_t Vout, uint32_t Fout, float *out_vertices, float *out_colors,
+                                     int32_t *out_faces, int32_t *vertex_index, void *stream);
 
 #ifdef __cplusplus
 }

@@ -4,6 +4,8 @@ Per volume size N^3 (bounds [-1,1]^3, colour on):
   integrate   one launch fusing 8 views of 800x800 (analytic sphere depth + a colour map): median of `reps` launches, HIP events
   torch       the same arithmetic written in torch on the device, one view at a time (the baseline the speed-up is quoted against)
   extract     envgs_mesh_count + the read-back + envgs_mesh_extract of the fused volume
+  components  envgs_mesh_components of that mesh + the read-back of C;  select: envgs_mesh_select_count + read-back + envgs_mesh_select_emit of its largest
+              component;  clean: mesh.clean with its defaults (components, the rule in torch, select)
 The byte model of integrate: every voxel's tsdf, weight and rgb read once (20 B), and written back (20 B) in the 16 B granules where a voxel changed;
 of extract: 8 B read + 1 B written (classify), 1 B read + 3 B written (count), 4 B read (emit) per voxel, plus 24 B per vertex and 12 B per face
 written.  Fractions are of 6.3 TB/s (the achievable HBM rate, not the 8 TB/s peak).  Nothing is asserted; the table goes to DESIGN.md."""
@@ -110,7 +112,22 @@ def main():
         t_ext = median_ms(lambda: vol.extract(), args.reps)
         by = n * 17.0 + V * 24.0 + F * 12.0
         print("%-6d %-10s %10.3f %12.1f %9.1f%%   V %d F %d; includes the (V, F) read-back and the output allocation" % (N, "extract", t_ext, by / 1e6, 100 * by / (t_ext * 1e-3) / ACHIEVABLE, V, F))
-        del vol, m
+        # the clean-up of that mesh (csrc/mesh_clean.hip); the models count the streaming reads and writes of the passes, not the union-find's chases
+        comp = mesh.components(m)
+        t_cc = median_ms(lambda: mesh.components(m), args.reps)
+        by = V * 36.0 + F * 48.0
+        print("%-6d %-10s %10.3f %12.1f %9.1f%%   %d components, the largest %d faces; includes the read-back of C and the output allocation"
+              % (N, "components", t_cc, by / 1e6, 100 * by / (t_cc * 1e-3) / ACHIEVABLE, comp.count, int(comp.faces.max()) if comp.count else 0))
+        keep = comp.face_label == int(comp.faces.argmax()) if comp.count else torch.zeros(F, dtype=torch.bool, device=dev)
+        s = mesh.select_faces(m, keep)
+        t_sel = median_ms(lambda: mesh.select_faces(m, keep), args.reps)
+        by = F * 26.0 + V * 4.0 + s.vertices.shape[0] * 48.0 + s.faces.shape[0] * 15.0
+        print("%-6d %-10s %10.3f %12.1f %9.1f%%   the largest component: V' %d F' %d; includes the (V', F') read-back and the output allocation"
+              % (N, "select", t_sel, by / 1e6, 100 * by / (t_sel * 1e-3) / ACHIEVABLE, s.vertices.shape[0], s.faces.shape[0]))
+        t_clean = median_ms(lambda: mesh.clean(m), args.reps)
+        print("%-6d %-10s %10.3f %12s %10s   components + the rule in torch (sort of C counts, gather of F labels) + select: %.2fx the extraction"
+              % (N, "clean", t_clean, "-", "-", t_clean / t_ext))
+        del vol, m, comp, s
         torch.cuda.empty_cache()
 
 
