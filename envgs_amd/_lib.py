@@ -67,7 +67,7 @@ class TraceLists(ctypes.Structure):
                 ("n_entries", ctypes.c_void_p), ("compact_rows", ctypes.c_uint64), ("row_off", ctypes.c_void_p), ("batch_rows", ctypes.c_void_p),
                 ("row_blk", ctypes.c_void_p), ("sh_perm", ctypes.c_void_p), ("state_planes", ctypes.c_int32),
                 ("sparse_hits", ctypes.c_void_p), ("sparse_cap", ctypes.c_uint64),
-                ("defer_reduce", ctypes.c_uint32), ("reserved0", ctypes.c_uint32)]
+                ("defer_reduce", ctypes.c_uint32), ("reserved0", ctypes.c_uint32), ("bwd_order", ctypes.c_void_p)]
 
 
 class TraceCfg(ctypes.Structure):

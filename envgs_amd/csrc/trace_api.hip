@@ -112,6 +112,13 @@ static TraceArgs base_args(const envgs_trace_cfg *cfg, const float *nodes, const
     return A;
 }
 
+// classes of the record backward's longest-first batch order (envgs_trace.h: bwd_order); ENVGS_DBG_BALANCE >> 8 overrides (the K sweep)
+static int bwd_order_classes()
+{
+    const int k = debug_switch(ENVGS_DBG_BALANCE) >> 8;
+    return k > 0 ? k : ENVGS_BWD_ORDER_CLASSES;
+}
+
 static unsigned sparse_capacity(const envgs_trace_lists *L)       // (the kernels count the filed hits in a 32-bit word)
 {
     return (unsigned)(L->sparse_cap > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : L->sparse_cap);
@@ -311,8 +318,11 @@ int envgs_trace_forward(const envgs_trace_cfg *cfg, const float *nodes, const fl
         }
         for (int i = 1; i < nseg; i++)
             if (hipEventRecord(ev_join[i], aux[i]) != hipSuccess || hipStreamWaitEvent(stream, ev_join[i], 0) != hipSuccess) return ENVGS_ERR_BAD_ARG;
-        hipLaunchKernelGGL(unpack_surfel_acc, dim3((cfg->P + 255) / 256), dim3(256), 0, stream, cfg->P, A.wfrac, A.surf_acc, L->surf_cnt, wet,
-                           counters);                                          // (also clears the ray-fetch counter of the overflow pass)
+        // (also clears the ray-fetch counter of the overflow pass, and -- one more workgroup, no launch of its own -- sorts the batches for the
+        //  record backward, longest first: envgs_trace.h: bwd_order)
+        unsigned *bwd_order = (L->bwd_order && L->n_entries && L->entries && L->pairs && L->hit_state) ? L->bwd_order : nullptr;
+        hipLaunchKernelGGL(unpack_surfel_acc, dim3((cfg->P + 255) / 256 + (bwd_order ? 1 : 0)), dim3(256), 0, stream, cfg->P, A.wfrac, A.surf_acc, L->surf_cnt, wet,
+                           counters, (const int *)L->n_entries, nbatch_all, bwd_order, bwd_order_classes());
         ENVGS_CHECK_LAUNCH(dcfg, stream);
         {   // records of the backward are addressed through the inclusive scan of the per-surfel hit counts
             const int rc = launch_scan(L->surf_cnt, L->surf_off, cfg->P * NCOPY, L->scan_temp, L->scan_temp_bytes, stream);
@@ -394,7 +404,11 @@ int envgs_trace_backward(const envgs_trace_cfg *cfg, const float *nodes, const f
                     // the colour is the only output the loss uses (the EnvGS step): the specialisation that drops the other outputs' terms and state planes
                     const bool rgb_only = dL_drgb && !dL_ddpt && !dL_dacc && !dL_dnorm && !dL_daux;
                     if (L->state_planes == 1 && !rgb_only) return ENVGS_ERR_BAD_ARG;      // the forward was told to keep the colour's plane only
-                    const dim3 g(stride_grid((cfg->num_rays + 63) / 64, 1));
+                    // one workgroup per batch in the forward's longest-first order: a slot that frees takes the longest batch not yet started
+                    // (ENVGS_DBG_BALANCE bit 1: coherence order, grid-stride over at most 8192 workgroups -- the dispatch until round 7)
+                    const bool by_cost = L->bwd_order && !(debug_switch(ENVGS_DBG_BALANCE) & 1);
+                    A.bwd_order = by_cost ? L->bwd_order : nullptr;
+                    const dim3 g(by_cost ? (cfg->num_rays + 63) / 64 : stride_grid((cfg->num_rays + 63) / 64, 1));
                     if (rgb_only) hipLaunchKernelGGL((batch_surfel_bwd<true, false>), g, dim3(64), 0, stream, A);
                     else if (cfg->has_others) hipLaunchKernelGGL((batch_surfel_bwd<false, true>), g, dim3(64), 0, stream, A);
                     else hipLaunchKernelGGL((batch_surfel_bwd<false, false>), g, dim3(64), 0, stream, A);

@@ -190,6 +190,7 @@ struct TraceArgs {
     const unsigned *row_off;      // (R) by sorted slot: the ray's first row of hit_state
     const uint2 *batch_rows;      // (batches) {first row, rows} of the batch in entries / pairs
     const void *shp;    // (P, 48) quad-permuted copy of the SH blocks (permute_sh), same storage type as shs; nullptr = per-lane gathers from shs
+    const unsigned *bwd_order;    // (batches) batch_surfel_bwd: slot i of the dispatch takes batch bwd_order[i] (longest first, envgs_trace.h: bwd_order); nullptr = batch i
 };
 
 // K-nearest buffer ordered by (t, id); insertion is a fully unrolled compare-exchange chain (registers only).
@@ -696,7 +697,8 @@ __global__ void __launch_bounds__(256) row_scan_blocks(unsigned *__restrict__ bl
 __global__ void __launch_bounds__(256) row_offsets(const TraceArgs A, const unsigned *__restrict__ blk, unsigned *__restrict__ row_off, uint2 *__restrict__ batch_rows,
                                                    const unsigned *__restrict__ seg_base, unsigned long long limit);      // blk: exclusive scan of the per-BATCH row counts
 __global__ void __launch_bounds__(256) unpack_surfel_acc(int P, int wfrac, const unsigned long long *__restrict__ acc, unsigned *__restrict__ cnt,
-                                                         float *__restrict__ wet, unsigned *ray_counter);
+                                                         float *__restrict__ wet, unsigned *ray_counter, const int *__restrict__ n_entries, int nbatch,
+                                                         unsigned *__restrict__ bwd_order, int order_classes);
 __global__ void __launch_bounds__(256) sparse_hits_bwd(const TraceArgs A, const int rgbo);
 template <bool RGBO, bool OTH> __global__ void __attribute__((amdgpu_waves_per_eu(ENVGS_BSB_WAVES, ENVGS_BSB_WAVES))) __launch_bounds__(64) batch_surfel_bwd(const TraceArgs A);
 extern template __global__ void __attribute__((amdgpu_waves_per_eu(ENVGS_BSB_WAVES, ENVGS_BSB_WAVES))) __launch_bounds__(64) batch_surfel_bwd<false, false>(const TraceArgs A);

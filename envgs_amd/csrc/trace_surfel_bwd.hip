@@ -48,7 +48,10 @@ batch_surfel_bwd(const TraceArgs A)
     const int lane = threadIdx.x;
     const int nb = (A.D + 1) * (A.D + 1);
     const int nbatch = (A.R + 63) >> 6;
-    for (int batch = blockIdx.x; batch < nbatch; batch += gridDim.x) {
+    // which batch a dispatch slot takes: the forward's longest-first order (one workgroup per batch: the loop runs once), or the slot itself
+    for (int slot = blockIdx.x; slot < nbatch; slot += gridDim.x) {
+        const int batch = A.bwd_order ? (int)A.bwd_order[slot] : slot;
+        if ((unsigned)batch >= (unsigned)nbatch) continue;          // (never: the order is a permutation)
         const int base = batch << 6;
         const int copy = batch & (NCOPY - 1);
         const int r = ray_of(A, base + lane);

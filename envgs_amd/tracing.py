@@ -220,6 +220,14 @@ def _carve_i32(dev, sizes):
 SPARSE = {"mode": "auto", "below": 6.0, "cap": None, "poison": None}
 QUAD_SH = {"on": True}       # list path: four lanes share the fetch of a surfel's SH block (tests switch it off to cover the per-lane gathers)
 KEEP_LISTS = {"on": False}   # tests: keep the last forward's per-ray hit lists reachable through last_hit_lists()
+BWD_ORDER = {"on": True}     # record backward: batches handed out longest first (envgs_trace.h: bwd_order); off = coherence order
+BWD_ORDER_CLASSES = 32       # ENVGS_BWD_ORDER_CLASSES
+
+
+def bwd_order_class(counts, classes=BWD_ORDER_CLASSES):
+    """The class of each batch in the record backward's longest-first order (envgs_trace.h: bwd_order): counts = a batch's entries
+    (n_entries.sum(1)), as an integer tensor or array; class c * K // (max + 1), 0 = shortest.  The order is a stable sort by descending class."""
+    return (counts * int(classes)) // (int(counts.max()) + 1)
 
 
 _DEFERRED = {"pending": False, "keep": None, "dev": None}
@@ -346,7 +354,7 @@ def trace_forward(nodes, ray_o, ray_d, means3D, shs, colors_precomp, others_prec
         # right behind the rasterizer's one host sync, where the GPU has nothing queued)
         keep = _carve_i32(dev, dict(hit_cnt=R, n_used=R, surf_acc=2 * P * NCOPY, surf_cnt=P * NCOPY,
                                     surf_off=P * NCOPY, scan_temp=(max(sb, 1) + 3) // 4, ray_keys=2 * R, ray_order=2 * R, ray_sort_temp=(max(rb, 1) + 3) // 4,
-                                    n_entries=2 * nbatch, row_off=R, batch_rows=2 * nbatch, row_blk=nbatch + 16))
+                                    n_entries=2 * nbatch, row_off=R, batch_rows=2 * nbatch, row_blk=nbatch + 16, bwd_order=nbatch))
         keep["n_entries"] = keep["n_entries"].view(nbatch, 2)
         keep["hit_lists"] = _scratch((R, cap, 2), torch.int32, dev)
         srt = SORT_RAYS["on"]
@@ -385,6 +393,8 @@ def trace_forward(nodes, ray_o, ray_d, means3D, shs, colors_precomp, others_prec
                                 *[(keep[k].data_ptr() if (k in keep and rows) else None) for k in ("row_off", "batch_rows", "row_blk")],
                                 keep["sh_perm"].data_ptr() if "sh_perm" in keep else None, 0,
                                 keep["sparse_hits"].data_ptr() if "sparse_hits" in keep else None, sparse_cap)
+        if "hit_state" in keep and BWD_ORDER["on"]:
+            lists.bwd_order = keep["bwd_order"].data_ptr()   # the record backward's batches, longest first (envgs_trace.h: bwd_order)
         if "hit_state" in keep and getattr(caps, "colour_only", False):
             lists.state_planes = 1
             keep["colour_only"] = True
@@ -398,7 +408,8 @@ def trace_forward(nodes, ray_o, ray_d, means3D, shs, colors_precomp, others_prec
                       lists=((keep["hit_lists"], keep["n_used"], keep["hit_cnt"]) if (cap and KEEP_LISTS["on"]) else None),
                       records=(dict(sparse_hits=keep.get("sparse_hits"), sparse_cap=sparse_cap, entries=keep["entries"], pairs=keep["pairs"],
                                     n_entries=keep["n_entries"], batch_rows=(keep["batch_rows"].view(-1, 2) if rows else None),
-                                    ray_order=(keep["ray_order"][R:] if SORT_RAYS["on"] else None), surf_cnt=keep["surf_cnt"], surf_off=keep["surf_off"])
+                                    ray_order=(keep["ray_order"][R:] if SORT_RAYS["on"] else None), surf_cnt=keep["surf_cnt"], surf_off=keep["surf_off"],
+                                    bwd_order=(keep["bwd_order"] if BWD_ORDER["on"] else None))
                                if (cap and KEEP_LISTS["on"] and "hit_state" in keep) else None))
     if cap:
         if "hit_state" in keep and not KEEP_LISTS["on"]:

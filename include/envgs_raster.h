@@ -185,7 +185,8 @@ ENVGS_API const char *envgs_prof_kernel_name(int kernel_id);
 #define ENVGS_DBG_RASTER_EXACT 3     /* libenvgs_hip_diag.so only: R6 / R7 with IEEE divisions and the library expf instead of v_rcp_f32 (+ Newton) / v_exp_f32 -- the attribution run of the parity tests; no effect in the product library */
 #define ENVGS_DBG_RAYKEY 4           /* ray coherence key (csrc/ray_key.h): value - 1 = direction-only rounds in front of the interleaved (direction, origin) rounds; 0 = default */
 #define ENVGS_DBG_SPARSE 5           /* sparse entries of the tracer's record backward (envgs_trace.h: sparse_hits): value - 1 = the largest hit count an entry may have to be filed per hit; 0 = default (4), 1 = off */
-#define ENVGS_DBG_COUNT 6
+#define ENVGS_DBG_BALANCE 6          /* how coarse work is handed out (round 7).  Bit 1: the tracer's record backward takes its batches in coherence order, grid-stride over at most 8192 workgroups (the order until round 7) instead of longest batch first, one workgroup per batch.  Bit 2: reserved (selected the fixed tile bands against round 7's tile queues of R6 / R7, which lost and were taken out: profiles/DEAD_ENDS.md); no effect.  Bits 8..: value >> 8 = classes K of the longest-first order (0 = default; 1 = coherence order through the new dispatch) -- the K sweep of profiles/r07_ab_balance.txt */
+#define ENVGS_DBG_COUNT 7
 ENVGS_API void envgs_debug_set(int32_t which, int32_t value);
 ENVGS_API int32_t envgs_debug_get(int32_t which);
 

@@ -148,7 +148,16 @@ typedef struct envgs_trace_lists {
                                 passes NO_FINISH (geo_rec stays unconverted; dmeans3D .. dopacities may be NULL).  The conversion is linear in geo_rec, so
                                 converting the sum once equals the sum of the conversions */
     uint32_t reserved0;
+    uint32_t *bwd_order;     /* optional (round 7), (ceil(R/64)): the batches in the order envgs_trace_backward's record kernel takes them -- LONGEST FIRST.  A
+                                batch costs that kernel one pass per entry and the counts differ severalfold across a view; taken in coherence order the
+                                last wavefronts to start may hold the longest batches and the chip idles behind them.  Written by envgs_trace_forward (in
+                                its unpack launch, after the segments have joined) as a stable counting sort of the batches by descending
+                                n_entries[b][0] + n_entries[b][1] into ENVGS_BWD_ORDER_CLASSES classes, class of a count c = c * K / (max count + 1);
+                                coherence order is kept inside a class.  A deterministic function of n_entries.  The kernel then runs one workgroup per
+                                batch, workgroup i = batch bwd_order[i]: the hardware hands a freed slot the longest batch not yet started.
+                                NULL = coherence order */
 } envgs_trace_lists;
+#define ENVGS_BWD_ORDER_CLASSES 32
 #define ENVGS_TRACE_DEFER 1u
 #define ENVGS_TRACE_ACCUMULATE 2u
 #define ENVGS_TRACE_NO_FINISH 4u
