@@ -79,6 +79,19 @@ class TraceCfg(ctypes.Structure):
                 ("scale_modifier", ctypes.c_float), ("specular_threshold", ctypes.c_float), ("feature_f16", ctypes.c_int32)]
 
 
+# The counter block of a traced call (include/envgs_trace.h) and the ENVGS_DBG_TRACE bits (include/envgs_raster.h): the headers' names without
+# their ENVGS_ prefix.  tests/test_abi.py compares every one of them with the header.
+TRACE_COUNTER_WORDS, TRACE_COUNTER_MIRROR, TRACE_MAX_SEG = 96, 72, 4
+CTR_RAY_FETCH, CTR_MAX_LIST, CTR_TOTALS = 0, 1, 2
+(TOT_HITS, TOT_NODE_VISITS, TOT_ROUNDS, TOT_FOUND, TOT_PACKET_NODES, TOT_PACKET_LEAVES, TOT_COOP_EXPAND, TOT_COOP_WALK, TOT_COOP_WAIT,
+ TOT_COUNT) = range(10)
+CTR_STACK_OVERFLOWS, CTR_RAYS_WITHOUT_ROWS, CTR_ROW_CLAIM, CTR_LONG_QUEUE, CTR_SEG_FIRST_ROW = 20, 21, 22, 24, 28
+CTR_BATCH_FETCH, CTR_BATCH_FETCH_STRIDE = 32, 8
+CTR_SPARSE_FILED, CTR_BATCH_ENTRIES, CTR_SPARSE_SKIPPED = 64, 65, 66
+DBG_TRACE, DBG_TRACE_NO_SORT, DBG_TRACE_SMALL_STACK, DBG_TRACE_PREPARE_INLINE = 0, 64, 1024, 16384
+DBG_TRACE_RETIRED = 8 | 16 | 512 | 2048 | 4096 | 8192
+
+
 class SupervisorArgs(ctypes.Structure):
     """struct envgs_supervisor_args (include/envgs_supervisor.h)."""
     _fields_ = ([("N", ctypes.c_int64), ("P", ctypes.c_int64), ("flags", ctypes.c_uint32), ("reserved0", ctypes.c_uint32),

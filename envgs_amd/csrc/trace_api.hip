@@ -4,10 +4,9 @@
 
 #include <mutex>
 
-
 namespace envgs {
 
-constexpr int MAX_SEG = 4;      // forward batch segments that may run concurrently (own stream and fetch counters each)
+constexpr int MAX_SEG = ENVGS_TRACE_MAX_SEG;      // forward batch segments that may run concurrently (own stream and fetch counters each)
 
 static int persistent_grid(int R, int per_cu = 8)
 {
@@ -49,7 +48,11 @@ static bool lists_usable_bwd(const envgs_trace_cfg *cfg, const envgs_trace_lists
 {
     return lists_wanted(cfg, L) && L->hit_cnt && L->n_used && L->surf_cnt && L->surf_off;
 }
-
+// A record backward was prepared: the forward keeps (the backward reads) the per-hit state, the entries / pairs and the per-surfel offsets
+static bool records_prepared(const envgs_trace_lists *L)
+{
+    return L->surf_cnt && L->surf_off && L->hit_state && L->entries && L->pairs && L->n_entries;
+}
 
 }  // namespace envgs
 
@@ -124,6 +127,55 @@ static unsigned sparse_capacity(const envgs_trace_lists *L)       // (the kernel
     return (unsigned)(L->sparse_cap > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : L->sparse_cap);
 }
 
+// One forward segment (S.seg, batches [S.batch0, S.batch1)) on its stream: collect -> row scan (compact layouts) -> sort + composite -> register
+static int forward_segment(const envgs_trace_cfg *cfg, const envgs_raster_cfg *dcfg, const envgs_trace_lists *L, const TraceArgs &S, hipStream_t st,
+                           int seg_wgs, bool compact)
+{
+    const int rays_seg = (S.batch1 - S.batch0) * 64;
+    {
+        ProfScope p1(K_TRACE_COLLECT, st);
+        // the cooperative collection is the only collection kernel (without a coherence sort its batches are the rays in the order
+        // given: correct, slower)
+        const dim3 cg(persistent_grid(rays_seg, seg_wgs));
+        const float4 *n4 = S.nodes + (size_t)(cfg->P > 1 ? cfg->P - 1 : 1) * 4;
+        hipLaunchKernelGGL(collect_hits_coop, cg, dim3(256), 0, st, S, S.nodes, n4, S.srec);
+    }
+    ENVGS_CHECK_LAUNCH(dcfg, st);
+    if (compact) {
+        // row offsets of the compact per-hit buffers: scan of this segment's hit counts in sorted order; the segment owns the share of
+        // the rows that corresponds to its share of the batches
+        const int nb_seg = S.batch1 - S.batch0, nblk = (rays_seg + 255) / 256;
+        unsigned *cntb = L->row_blk;                                       // (batches) row counts, scanned in place per segment
+        // the segment claims its rows from a counter shared by the call's segments (ENVGS_CTR_ROW_CLAIM); its first row lands in ENVGS_CTR_SEG_FIRST_ROW + seg
+        const unsigned long long limit = (unsigned long long)L->compact_rows;
+        unsigned *first_row = S.counter + ENVGS_CTR_SEG_FIRST_ROW + S.seg;
+        hipLaunchKernelGGL(row_scan_blocks, dim3(1), dim3(256), 0, st, cntb + S.batch0, nb_seg, S.counter + ENVGS_CTR_ROW_CLAIM, first_row);
+        hipLaunchKernelGGL(row_offsets, dim3(nblk), dim3(256), 0, st, S, cntb, L->row_off, (uint2 *)L->batch_rows, (const unsigned *)first_row, limit);
+        ENVGS_CHECK_LAUNCH(dcfg, st);
+    }
+    {
+        ProfScope p2(K_TRACE_SORT, st);
+        const dim3 g(stride_grid(rays_seg, 4)), b(256);
+        if (S.shp) hipLaunchKernelGGL((sort_composite_fwd<4, false, true>), g, b, 0, st, S);
+        else hipLaunchKernelGGL((sort_composite_fwd<4, false, false>), g, b, 0, st, S);
+        if (S.cap > 256) {
+            const dim3 gl(min(stride_grid(rays_seg, 256), 512));
+            if (S.cap <= 512) { if (S.shp) hipLaunchKernelGGL((sort_composite_fwd<8, true, true>), gl, b, 0, st, S); else hipLaunchKernelGGL((sort_composite_fwd<8, true, false>), gl, b, 0, st, S); }
+            else { if (S.shp) hipLaunchKernelGGL((sort_composite_fwd<16, true, true>), gl, b, 0, st, S); else hipLaunchKernelGGL((sort_composite_fwd<16, true, false>), gl, b, 0, st, S); }
+        }
+    }
+    ENVGS_CHECK_LAUNCH(dcfg, st);
+    {
+        ProfScope p8(K_TRACE_REGISTER, st);
+        const dim3 gr(stride_grid(rays_seg, 64)), br(64 * RH_W);
+        // (lists of at most 256 hits: each hit's table slot and rank stay in registers between the kernel's phases)
+        if (S.pairs && S.cap <= 256) hipLaunchKernelGGL(register_hits<true>, gr, br, 0, st, S);
+        else hipLaunchKernelGGL(register_hits<false>, gr, br, 0, st, S);
+    }
+    ENVGS_CHECK_LAUNCH(dcfg, st);
+    return 0;
+}
+
 extern "C" {
 
 size_t envgs_trace_ray_sort_temp_bytes(int32_t num_rays) { return ray_sort_temp_bytes(num_rays); }
@@ -152,14 +204,12 @@ int envgs_trace_forward(const envgs_trace_cfg *cfg, const float *nodes, const fl
     if (cfg->has_others && cfg->P > 0 && !others_precomp) return ENVGS_ERR_BAD_ARG;
     hipStream_t stream = (hipStream_t)stream_;
     if (join_deferred(stream)) return ENVGS_ERR_BAD_ARG;
-    envgs_raster_cfg dbg; dbg.debug = cfg->debug;
-    const envgs_raster_cfg *dcfg = &dbg;
-    hipError_t e;
+    envgs_raster_cfg dbg; dbg.debug = cfg->debug; const envgs_raster_cfg *dcfg = &dbg;
     ForwardPrepare FP;                      // queued as ONE launch further down, once the list path has said whether it wants permuted SH blocks
     std::memset(&FP, 0, sizeof(FP));
     {   // counters, wet, mid and (list path) the per-surfel accumulators
         ZeroBatch &zb = FP.zero; zb.count = 0;
-        zb.ptr[zb.count] = reinterpret_cast<float *>(counters); zb.n[zb.count++] = 96;
+        zb.ptr[zb.count] = reinterpret_cast<float *>(counters); zb.n[zb.count++] = ENVGS_TRACE_COUNTER_WORDS;
         if (cfg->P > 0) { zb.ptr[zb.count] = wet; zb.n[zb.count++] = (unsigned long long)cfg->P; }
         zb.ptr[zb.count] = mid; zb.n[zb.count++] = (unsigned long long)cfg->num_rays * MID * (cfg->max_trace_depth + 1);
         if (lists_usable(cfg, L)) { zb.ptr[zb.count] = reinterpret_cast<float *>(L->surf_acc); zb.n[zb.count++] = (unsigned long long)cfg->P * NCOPY * 2; }
@@ -174,9 +224,9 @@ int envgs_trace_forward(const envgs_trace_cfg *cfg, const float *nodes, const fl
         return (int)hipGetLastError();
     };
     TraceArgs A = base_args(cfg, nodes, srec, shs, colors_precomp, others_precomp, bg, ray_o, ray_d, counters);
-    A.ND = cfg->max_trace_depth + 1; A.stats = (unsigned long long *)(counters + 2);
+    A.ND = cfg->max_trace_depth + 1; A.stats = (unsigned long long *)(counters + ENVGS_CTR_TOTALS);
     A.rgb = rgb; A.dpt = dpt; A.acc = acc; A.norm = norm; A.dist = dist; A.aux = aux; A.mid = mid; A.wet = wet; A.final_T = final_T;
-    if (A.exp & (8 | 16 | 512 | 2048 | 4096 | 8192)) return ENVGS_ERR_BAD_ARG;      // switches of deleted A/B kernels: refused, never silently ignored
+    if (A.exp & ENVGS_DBG_TRACE_RETIRED) return ENVGS_ERR_BAD_ARG;      // switches of deleted A/B kernels: refused, never silently ignored
     int rh, rw; ray_layout(cfg, &rh, &rw);
     const bool lists = lists_usable(cfg, L);
     if (lists_wanted(cfg, L) && !lists) return ENVGS_ERR_BAD_ARG;      // (see lists_usable_bwd: no silent fallback to the K-buffer path)
@@ -186,7 +236,7 @@ int envgs_trace_forward(const envgs_trace_cfg *cfg, const float *nodes, const fl
         if (L->scan_temp_bytes < scan_temp_bytes(cfg->P * NCOPY)) return ENVGS_ERR_TEMP_TOO_SMALL;
         A.hits = (uint2 *)L->hit_lists; A.hit_cnt = L->hit_cnt; A.n_used = L->n_used; A.cap = L->cap;
         A.surf_cnt = L->surf_cnt; A.surf_off = L->surf_off; A.surf_acc = (unsigned long long *)L->surf_acc;
-        const bool will_sort = L->ray_keys && L->ray_order && L->ray_sort_temp && !(A.exp & 64);
+        const bool will_sort = L->ray_keys && L->ray_order && L->ray_sort_temp && !(A.exp & ENVGS_DBG_TRACE_NO_SORT);
         {   // 40-bit fixed-point weight: enough integer bits that even a surfel seen with w = 1 by every ray cannot overflow
             int ib = 1;
             while ((1ll << ib) <= (long long)cfg->num_rays) ib++;
@@ -198,7 +248,7 @@ int envgs_trace_forward(const envgs_trace_cfg *cfg, const float *nodes, const fl
         A.state_plane = compact ? (size_t)L->compact_rows : (size_t)cfg->num_rays * (size_t)L->cap;
         A.colour_state = L->state_planes == 1 ? 1 : 0;
         if (compact) { A.row_off = L->row_off; A.batch_rows = (const uint2 *)L->batch_rows; A.batch_cnt = L->row_blk; }
-        if (L->sparse_hits && L->sparse_cap > 0 && L->entries && L->pairs && L->hit_state) {
+        if (L->sparse_hits && L->sparse_cap > 0 && L->entries && L->pairs && L->hit_state) {      // (not records_prepared(): n_entries has never been asked for here)
             // sparse entries (envgs_trace.h: sparse_hits): entries of at most 4 hits are filed per hit (ENVGS_DBG_SPARSE: value - 1 overrides, 1 = off)
             const int sw = debug_switch(ENVGS_DBG_SPARSE);
             A.sparse = (uint4 *)L->sparse_hits;
@@ -217,22 +267,20 @@ int envgs_trace_forward(const envgs_trace_cfg *cfg, const float *nodes, const fl
         const int nbatch_all = (cfg->num_rays + 63) / 64;
         int nseg = 2;                                         // measured (round 1): 1 -> 18.3 ms / step, 2 -> 17.5, 4 -> 19.4 (each collection launch lasts at least one batch)
         if (debug_switch(ENVGS_DBG_SEGMENTS) > 0) nseg = debug_switch(ENVGS_DBG_SEGMENTS);
-        if (nseg > MAX_SEG) nseg = MAX_SEG;                   // (fetch counters: 8 words per segment from counters[32])
+        if (nseg > MAX_SEG) nseg = MAX_SEG;                   // (fetch counters: ENVGS_CTR_BATCH_FETCH_STRIDE words per segment from ENVGS_CTR_BATCH_FETCH)
         while (nseg > 1 && nbatch_all / nseg < 256) nseg--;
         if (nseg < 1) nseg = 1;
         hipStream_t aux[MAX_SEG] = {};
         hipEvent_t ev_fork = nullptr, ev_join[MAX_SEG] = {};
+        int dev = 0;
+        if (nseg > 1 && !aux_objects(&dev)) nseg = 1;
         if (nseg > 1) {
-            int dev = 0;
-            if (!aux_objects(&dev)) nseg = 1;
-            if (nseg > 1) {
-                ev_fork = s_fork[dev];
-                for (int i = 1; i < nseg; i++) { aux[i] = s_aux[dev][i]; ev_join[i] = s_join[dev][i]; }
-            }
+            ev_fork = s_fork[dev];
+            for (int i = 1; i < nseg; i++) { aux[i] = s_aux[dev][i]; ev_join[i] = s_join[dev][i]; }
         }
         // forward_prepare (zero fills, surfel records, permuted SH blocks) reads nothing of the rays: with a second stream at hand it runs
         // there, beside the coherence sort's seven small launches, instead of after them
-        const bool prepare_aside = nseg > 1 && will_sort && !(A.exp & 16384);
+        const bool prepare_aside = nseg > 1 && will_sort && !(A.exp & ENVGS_DBG_TRACE_PREPARE_INLINE);
         if (prepare_aside) {
             if (hipEventRecord(ev_fork, stream) != hipSuccess || hipStreamWaitEvent(aux[1], ev_fork, 0) != hipSuccess) return ENVGS_ERR_BAD_ARG;
             const int rcp = launch_prepare(aux[1]); if (rcp) return rcp;
@@ -265,73 +313,28 @@ int envgs_trace_forward(const envgs_trace_cfg *cfg, const float *nodes, const fl
         const int coop_wgs = (debug_switch(ENVGS_DBG_COLLECT_WGS) > 0 && debug_switch(ENVGS_DBG_COLLECT_WGS) <= 8) ? debug_switch(ENVGS_DBG_COLLECT_WGS)
                                                                                                                   : (nseg > 1 ? 4 : 8);
         for (int sg = 0; sg < nseg; sg++) {                   // segment 0 on the caller's stream, the others on auxiliary streams
-            hipStream_t st = sg ? aux[sg] : stream;
             TraceArgs S = A;
             S.seg = sg;
             S.batch0 = (int)((long long)nbatch_all * sg / nseg);
             S.batch1 = (int)((long long)nbatch_all * (sg + 1) / nseg);
-            const int rays_seg = (S.batch1 - S.batch0) * 64;
             // (round 3 gave the later segment's collection one more workgroup per CU -- 4+4 / 4+5 / 4+6 / 3+5 / 5+4 workgroups: 9.54 / 9.48 / 9.57 / 9.62 /
             //  9.59 ms per step then.  Round 6, with the collection 15 % faster than the sort pass it runs beside: 4+4 wins, three alternating pairs
             //  7.91 / 7.93 / 7.92 ms against 7.94 / 7.94 / 7.97, configs[4] 50.7 / 50.8 against 50.9 / 51.2 -- the sort pass gets the slots)
-            const int seg_wgs = coop_wgs;
-            {
-                ProfScope p1(K_TRACE_COLLECT, st);
-                // the cooperative collection is the only collection kernel (without a coherence sort its batches are the rays in the order
-                // given: correct, slower)
-                const dim3 cg(persistent_grid(rays_seg, seg_wgs));
-                const float4 *n4 = S.nodes + (size_t)(cfg->P > 1 ? cfg->P - 1 : 1) * 4;
-                hipLaunchKernelGGL(collect_hits_coop, cg, dim3(256), 0, st, S, S.nodes, n4, S.srec);
-            }
-            ENVGS_CHECK_LAUNCH(dcfg, st);
-            if (compact) {
-                // row offsets of the compact per-hit buffers: scan of this segment's hit counts in sorted order; the segment owns the share of
-                // the rows that corresponds to its share of the batches
-                const int nb_seg = S.batch1 - S.batch0, nblk = (rays_seg + 255) / 256;
-                unsigned *cntb = L->row_blk;                                       // (batches) row counts, scanned in place per segment
-                // the segment claims its rows from a counter shared by the call's segments (counters[22]); its first row lands in counters[28 + seg]
-                const unsigned long long limit = (unsigned long long)L->compact_rows;
-                hipLaunchKernelGGL(row_scan_blocks, dim3(1), dim3(256), 0, st, cntb + S.batch0, nb_seg, counters + 22, counters + 28 + sg);
-                hipLaunchKernelGGL(row_offsets, dim3(nblk), dim3(256), 0, st, S, cntb, L->row_off, (uint2 *)L->batch_rows, (const unsigned *)(counters + 28 + sg), limit);
-                ENVGS_CHECK_LAUNCH(dcfg, st);
-            }
-            {
-                ProfScope p2(K_TRACE_SORT, st);
-                const dim3 g(stride_grid(rays_seg, 4)), b(256);
-                if (S.shp) hipLaunchKernelGGL((sort_composite_fwd<4, false, true>), g, b, 0, st, S);
-                else hipLaunchKernelGGL((sort_composite_fwd<4, false, false>), g, b, 0, st, S);
-                if (S.cap > 256) {
-                    const dim3 gl(min(stride_grid(rays_seg, 256), 512));
-                    if (S.cap <= 512) { if (S.shp) hipLaunchKernelGGL((sort_composite_fwd<8, true, true>), gl, b, 0, st, S); else hipLaunchKernelGGL((sort_composite_fwd<8, true, false>), gl, b, 0, st, S); }
-                    else { if (S.shp) hipLaunchKernelGGL((sort_composite_fwd<16, true, true>), gl, b, 0, st, S); else hipLaunchKernelGGL((sort_composite_fwd<16, true, false>), gl, b, 0, st, S); }
-                }
-            }
-            ENVGS_CHECK_LAUNCH(dcfg, st);
-            {
-                ProfScope p8(K_TRACE_REGISTER, st);
-                const dim3 gr(stride_grid(rays_seg, 64)), br(64 * RH_W);
-                // (lists of at most 256 hits: each hit's table slot and rank stay in registers between the kernel's phases)
-                if (S.pairs && S.cap <= 256) hipLaunchKernelGGL(register_hits<true>, gr, br, 0, st, S);
-                else hipLaunchKernelGGL(register_hits<false>, gr, br, 0, st, S);
-            }
-            ENVGS_CHECK_LAUNCH(dcfg, st);
+            const int rcs = forward_segment(cfg, dcfg, L, S, sg ? aux[sg] : stream, coop_wgs, compact); if (rcs) return rcs;
         }
         for (int i = 1; i < nseg; i++)
             if (hipEventRecord(ev_join[i], aux[i]) != hipSuccess || hipStreamWaitEvent(stream, ev_join[i], 0) != hipSuccess) return ENVGS_ERR_BAD_ARG;
         // (also clears the ray-fetch counter of the overflow pass, and -- one more workgroup, no launch of its own -- sorts the batches for the
         //  record backward, longest first: envgs_trace.h: bwd_order)
-        unsigned *bwd_order = (L->bwd_order && L->n_entries && L->entries && L->pairs && L->hit_state) ? L->bwd_order : nullptr;
+        unsigned *bwd_order = (L->bwd_order && records_prepared(L)) ? L->bwd_order : nullptr;      // (surf_cnt / surf_off: lists_usable() above)
         hipLaunchKernelGGL(unpack_surfel_acc, dim3((cfg->P + 255) / 256 + (bwd_order ? 1 : 0)), dim3(256), 0, stream, cfg->P, A.wfrac, A.surf_acc, L->surf_cnt, wet,
-                           counters, (const int *)L->n_entries, nbatch_all, bwd_order, bwd_order_classes());
+                           counters + ENVGS_CTR_RAY_FETCH, (const int *)L->n_entries, nbatch_all, bwd_order, bwd_order_classes());
         ENVGS_CHECK_LAUNCH(dcfg, stream);
-        {   // records of the backward are addressed through the inclusive scan of the per-surfel hit counts
-            const int rc = launch_scan(L->surf_cnt, L->surf_off, cfg->P * NCOPY, L->scan_temp, L->scan_temp_bytes, stream);
-            if (rc) return rc;
-        }
+        // records of the backward are addressed through the inclusive scan of the per-surfel hit counts
+        const int rc = launch_scan(L->surf_cnt, L->surf_off, cfg->P * NCOPY, L->scan_temp, L->scan_temp_bytes, stream); if (rc) return rc;
         A.only_overflow = 1;
     } else {
-        const int rcp = launch_prepare(stream);
-        if (rcp) return rcp;
+        const int rcp = launch_prepare(stream); if (rcp) return rcp;
         ENVGS_CHECK_LAUNCH(dcfg, stream);
     }
     { ProfScope p4(K_TRACE_KBUF_FWD, stream); hipLaunchKernelGGL(trace_fwd, dim3(persistent_grid(cfg->num_rays)), dim3(64), 0, stream, A, rh, rw); }
@@ -355,18 +358,16 @@ int envgs_trace_backward(const envgs_trace_cfg *cfg, const float *nodes, const f
     const bool accumulate = (dflags & ENVGS_TRACE_ACCUMULATE) != 0, no_finish = (dflags & ENVGS_TRACE_NO_FINISH) != 0;
     // (a call that continues a chain leaves the previous tail running under its own record kernels and waits for it before its K-buffer pass)
     if (!accumulate && join_deferred(stream)) return ENVGS_ERR_BAD_ARG;
-    envgs_raster_cfg dbg; dbg.debug = cfg->debug;
-    const envgs_raster_cfg *dcfg = &dbg;
+    envgs_raster_cfg dbg; dbg.debug = cfg->debug; const envgs_raster_cfg *dcfg = &dbg;
     const size_t P = (size_t)cfg->P, R = (size_t)cfg->num_rays;
-    hipError_t e;
     {
         ZeroBatch zb; zb.count = 0;
 #define ZERO(buf_, nn) do { if ((buf_) && (nn) > 0) { zb.ptr[zb.count] = (buf_); zb.n[zb.count] = (unsigned long long)(nn); zb.count++; } } while (0)
         if (!accumulate) { ZERO(geo_rec, P * ENVGS_GEOREC_STRIDE); if (cfg->sh_coeffs > 0) ZERO(dshs, P * cfg->sh_coeffs * 3); else ZERO(dcolors, P * 3); }
         if (!no_finish) { ZERO(dmeans3D, P * 3); ZERO(dgrads3D, P * 3); ZERO(dscales, P * 2); ZERO(drots, P * 4); ZERO(dopacities, P); }
         ZERO(dothers, P * 2); ZERO(dray_o, R * 3); ZERO(dray_d, R * 3);
-        if (counters && cfg->num_rays > 0 && cfg->P > 0) ZERO(reinterpret_cast<float *>(counters), 1);      // only the ray-fetch counter: [1] (largest list) and the stats stay readable
-        if (counters && cfg->num_rays > 0 && cfg->P > 0) ZERO(reinterpret_cast<float *>(counters + 66), 1); // and this backward's count of invalid sparse-list entries
+        if (counters && cfg->num_rays > 0 && cfg->P > 0) ZERO(reinterpret_cast<float *>(counters + ENVGS_CTR_RAY_FETCH), 1);      // only the ray-fetch counter: the largest list and the totals stay readable
+        if (counters && cfg->num_rays > 0 && cfg->P > 0) ZERO(reinterpret_cast<float *>(counters + ENVGS_CTR_SPARSE_SKIPPED), 1); // and this backward's count of invalid sparse-list entries
 #undef ZERO
         const int rcz = launch_zero_many(zb, stream);              // one launch instead of eleven fills
         if (rcz) return rcz;
@@ -380,7 +381,7 @@ int envgs_trace_backward(const envgs_trace_cfg *cfg, const float *nodes, const f
     A.f_rgb = rgb; A.f_dpt = dpt; A.f_acc = acc; A.f_norm = norm; A.f_aux = aux; A.f_T = final_T;
     A.g_rgb = dL_drgb; A.g_dpt = dL_ddpt; A.g_acc = dL_dacc; A.g_norm = dL_dnorm; A.g_aux = dL_daux;
     A.geo_rec = geo_rec; A.dshs = dshs; A.dcolors = dcolors; A.dothers = dothers; A.dray_o = dray_o; A.dray_d = dray_d;
-    if (A.exp & (8 | 16 | 512 | 2048 | 4096 | 8192)) return ENVGS_ERR_BAD_ARG;
+    if (A.exp & ENVGS_DBG_TRACE_RETIRED) return ENVGS_ERR_BAD_ARG;
     int rh, rw; ray_layout(cfg, &rh, &rw);
     bool deferred = false, have_records = false;
     int def_dev = 0;
@@ -389,8 +390,8 @@ int envgs_trace_backward(const envgs_trace_cfg *cfg, const float *nodes, const f
         if (lists_wanted(cfg, L) && !lists_usable_bwd(cfg, L)) return ENVGS_ERR_BAD_ARG;
         if (lists_usable_bwd(cfg, L)) {                // lists_wanted(): the forward took the list path exactly when it holds
             A.hits = (uint2 *)L->hit_lists; A.hit_cnt = L->hit_cnt; A.n_used = L->n_used; A.cap = L->cap;
-            if (L->ray_keys && L->ray_order && L->ray_sort_temp && !(A.exp & 64)) A.order = L->ray_order + cfg->num_rays;
-            if (L->records && L->num_records > 0 && L->surf_cnt && L->surf_off && L->hit_state && L->entries && L->pairs && L->n_entries) {
+            if (L->ray_keys && L->ray_order && L->ray_sort_temp && !(A.exp & ENVGS_DBG_TRACE_NO_SORT)) A.order = L->ray_order + cfg->num_rays;
+            if (L->records && L->num_records > 0 && records_prepared(L)) {
                 // atomic-free: one record per (batch, surfel) entry, grouped by surfel; then each surfel's records are summed
                 A.surf_cnt = L->surf_cnt; A.surf_off = L->surf_off; A.records = L->records; A.num_records = L->num_records;
                 A.state = (float4 *)L->hit_state; A.entries = (unsigned long long *)L->entries; A.pairs = L->pairs; A.n_entries = L->n_entries;
@@ -427,8 +428,7 @@ int envgs_trace_backward(const envgs_trace_cfg *cfg, const float *nodes, const f
             } else {
                 // the record backward is the only list backward.  No records = the forward composited nothing on the list
                 // path (num_records is its device-side count) -- anything else is a caller error, not a reason to differentiate nothing silently
-                if (!(L->surf_cnt && L->surf_off && L->hit_state && L->entries && L->pairs && L->n_entries) || (L->records == nullptr && L->num_records > 0))
-                    return ENVGS_ERR_BAD_ARG;
+                if (!records_prepared(L) || (L->records == nullptr && L->num_records > 0)) return ENVGS_ERR_BAD_ARG;
             }
             A.only_overflow = 1;
         }

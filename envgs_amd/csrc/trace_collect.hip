@@ -27,7 +27,7 @@ constexpr int COOP_ODROW = 36;            // floats per ray of the bin table: 32
 constexpr int COOP_NBIN = 32;             // distance bins of the termination bound (LDS: the update is one ds_add_f32 whatever their number)
 // Wave-uniform private stacks, in LDS.  Sized so that they do not overflow: the LBVH is at most 63 levels deep (62-bit unique Morton keys) and the
 // 4-wide walk holds at most three postponed children per TWO levels.  Should a child ever not fit, the batch is flagged: its rays are handed to
-// the K-buffer kernels (per-lane stacks) and counters[20] counts the event -- never a silently dropped subtree.
+// the K-buffer kernels (per-lane stacks) and ENVGS_CTR_STACK_OVERFLOWS counts the event -- never a silently dropped subtree.
 constexpr int COOP_STK = 96;
 constexpr int COOP_FRONT = 64;            // stop expanding once a level has this many entered subtrees (the next level holds at most 4x that).  Measured
                                           // (bench scene): 16 -> 93.8 M hits found, collect 2.70 ms; 32 -> 83.3 M, 1.97 ms; 64 -> 79.1 M, 1.87 ms (one wavefront
@@ -65,9 +65,9 @@ collect_hits_coop(const TraceArgs A, const float4 *__restrict__ nodes, const flo
     if ((reinterpret_cast<size_t>(&L.od[0][0]) & 15) != 0) __builtin_trap();
 #endif
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int slimit = (A.exp & 1024) ? 2 : COOP_STK;     // (test switch: forces the overflow hand-off)
+    const int slimit = (A.exp & ENVGS_DBG_TRACE_SMALL_STACK) ? 2 : COOP_STK;     // (test switch: forces the overflow hand-off)
     unsigned found_tot = 0, psteps = 0, pleaves = 0;
-    unsigned long long cyc_expand = 0, cyc_walk = 0, cyc_wait = 0;      // where the wavefront's time goes (diagnostics, stats[6..8])
+    unsigned long long cyc_expand = 0, cyc_walk = 0, cyc_wait = 0;      // where the wavefront's time goes (diagnostics, ENVGS_TOT_COOP_*)
     float rlx, rly, rlz, rhx, rhy, rhz;                   // the scene box = union of the root's two child boxes
     {
         const float4 n0 = nodes[0], n1 = nodes[1], n2 = nodes[2];
@@ -82,7 +82,7 @@ collect_hits_coop(const TraceArgs A, const float4 *__restrict__ nodes, const flo
     int *stk = L.stk[wave];
     while (true) {
         if (wave == 0) {
-            const int b = fetch_batch(A.counter + 32 + 8 * A.seg, nbatch, home, lane);
+            const int b = fetch_batch(A.counter + ENVGS_CTR_BATCH_FETCH + ENVGS_CTR_BATCH_FETCH_STRIDE * A.seg, nbatch, home, lane);
             if (lane == 0) { L.batch = b; L.nitems[0] = 1; L.nitems[1] = 0; L.items[0][0] = 0ull; L.next = 0; L.ovf = 0; }
         }
 #pragma unroll
@@ -183,7 +183,7 @@ collect_hits_coop(const TraceArgs A, const float4 *__restrict__ nodes, const flo
             const float4 *nd = nodes4 + (size_t)cur * 8;
             psteps++;
             float4 qa[4], qb[4];
-#if defined(ENVGS_COOP_TIMING) && ENVGS_COOP_TIMING == 2      // scratch/ measurement build: stats[6] = node loads, stats[8] = the four slots (slab tests, ballots, leaf tests)
+#if defined(ENVGS_COOP_TIMING) && ENVGS_COOP_TIMING == 2      // scratch/ measurement build: ENVGS_TOT_COOP_EXPAND = node loads, ENVGS_TOT_COOP_WAIT = the four slots (slab tests, ballots, leaf tests)
             const unsigned long long ta = __builtin_readcyclecounter();
             {
                 typedef float f8_ __attribute__((ext_vector_type(8)));
@@ -226,14 +226,14 @@ collect_hits_coop(const TraceArgs A, const float4 *__restrict__ nodes, const flo
                 }
                 const bool hit = tn <= tf;                        // (tmin <= tkill always, so this is the three-way test of the other kernels)
                 const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
-#if defined(ENVGS_COOP_TIMING) && ENVGS_COOP_TIMING == 3      // scratch/ measurement build: stats[6] = leaf slots slab-tested, stats[8] = lanes that passed a leaf slot's slab test
+#if defined(ENVGS_COOP_TIMING) && ENVGS_COOP_TIMING == 3      // scratch/ measurement build: ENVGS_TOT_COOP_EXPAND = leaf slots slab-tested, ENVGS_TOT_COOP_WAIT = lanes that passed a leaf slot's slab test
                 if (ch < 0) { cyc_expand += 1ull; cyc_wait += (unsigned long long)__builtin_popcountll(m); }
 #endif
                 if (m != 0ull) {
                     if (ch < 0) {
                         const int sid = ~ch;
                         pleaves++;
-#if defined(ENVGS_COOP_TIMING) && ENVGS_COOP_TIMING == 1      // scratch/ measurement build: where the immediate form's leaf test spends its cycles (stats[6] = whole leaf tests, stats[8] = their record loads)
+#if defined(ENVGS_COOP_TIMING) && ENVGS_COOP_TIMING == 1      // scratch/ measurement build: where the immediate form's leaf test spends its cycles (ENVGS_TOT_COOP_EXPAND = whole leaf tests, ENVGS_TOT_COOP_WAIT = their record loads)
                         const unsigned long long ta = __builtin_readcyclecounter();
                         typedef float f8_ __attribute__((ext_vector_type(8)));
                         f8_ r0, r1;
@@ -365,14 +365,14 @@ collect_hits_coop(const TraceArgs A, const float4 *__restrict__ nodes, const flo
             int n = L.cnt[lane];
             if (L.ovf) {
                 // a postponed child was dropped: this batch's lists are incomplete.  Mark every ray as overflowed (hit_cnt > cap) so that it is
-                // traced by the K-buffer kernels instead (per-lane stacks), and count the event (counters[20]).
+                // traced by the K-buffer kernels instead (per-lane stacks), and count the event (ENVGS_CTR_STACK_OVERFLOWS).
                 n = A.cap + 1;
-                if (lane == 0) atomicAdd(A.counter + 20, 1u);
+                if (lane == 0) atomicAdd(A.counter + ENVGS_CTR_STACK_OVERFLOWS, 1u);
             }
             if (valid) { A.hit_cnt[r] = n; found_tot += (unsigned)n; }
             int mx = n;
             for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_xor(mx, o));
-            if (lane == 0) atomicMax((int *)(A.counter + 1), mx);
+            if (lane == 0) atomicMax((int *)(A.counter + ENVGS_CTR_MAX_LIST), mx);
             if (A.batch_cnt) {                         // rows of the compact per-hit buffers this batch needs (envgs_trace.h: compact_rows)
                 const float rows = wave_sum((valid && n <= A.cap) ? (float)n : 0.f);
                 if (lane == 0) A.batch_cnt[A.batch0 + fb] = (unsigned)rows;
@@ -383,9 +383,9 @@ collect_hits_coop(const TraceArgs A, const float4 *__restrict__ nodes, const flo
     if (A.stats) {
         const float ff = wave_sum((float)found_tot);
         if (lane == 0) {
-            if (wave == 0) atomicAdd(A.stats + 3, (unsigned long long)ff);
-            atomicAdd(A.stats + 4, (unsigned long long)psteps); atomicAdd(A.stats + 5, (unsigned long long)pleaves);
-            atomicAdd(A.stats + 6, cyc_expand); atomicAdd(A.stats + 7, cyc_walk); atomicAdd(A.stats + 8, cyc_wait);
+            if (wave == 0) atomicAdd(A.stats + ENVGS_TOT_FOUND, (unsigned long long)ff);
+            atomicAdd(A.stats + ENVGS_TOT_PACKET_NODES, (unsigned long long)psteps); atomicAdd(A.stats + ENVGS_TOT_PACKET_LEAVES, (unsigned long long)pleaves);
+            atomicAdd(A.stats + ENVGS_TOT_COOP_EXPAND, cyc_expand); atomicAdd(A.stats + ENVGS_TOT_COOP_WALK, cyc_walk); atomicAdd(A.stats + ENVGS_TOT_COOP_WAIT, cyc_wait);
         }
     }
 #undef ENVGS_LDS_READ

@@ -145,7 +145,7 @@ struct TraceArgs {
     const float *shs, *colors, *others, *bg;
     const float *ray_o, *ray_d;
     unsigned *counter;
-    unsigned long long *stats;      // [hits, per-ray node visits, rounds, hits found, wide nodes fetched per packet, surfel records fetched per packet]
+    unsigned long long *stats;      // counter + ENVGS_CTR_TOTALS as uint64, indexed by ENVGS_TOT_* (forward only)
     // forward outputs
     float *rgb, *dpt, *acc, *norm, *dist, *aux, *mid, *wet, *final_T;
     // backward inputs / outputs
@@ -165,12 +165,11 @@ struct TraceArgs {
     float *records;           // (num_records, 24) per-hit gradient records grouped by surfel
     unsigned long long num_records;
     const unsigned *order;    // (R) ray permutation (coherence sort) or NULL
-    int exp;            // diagnostic switches (envgs_debug_set(ENVGS_DBG_TRACE, ...); 0 in production): 64 = no coherence sort of the rays,
-                        // 1024 = packet stack limited to 2 entries (tests the overflow hand-off), 16384 = forward_prepare on the caller's stream.
-                        // The bits of the deleted A/B kernels (8, 16, 512, 2048, 4096, 8192) are refused with ENVGS_ERR_BAD_ARG
+    int exp;            // diagnostic switches (envgs_debug_set(ENVGS_DBG_TRACE, ...); 0 in production): the ENVGS_DBG_TRACE_* bits of envgs_raster.h.
+                        // ENVGS_DBG_TRACE_RETIRED (the deleted A/B kernels) is refused with ENVGS_ERR_BAD_ARG
     int only_overflow;  // K-buffer kernels: process only rays whose hit_cnt exceeds cap
     int batch0, batch1; // list-path forward kernels: the range of 64-ray batches this launch owns (segments run on two streams)
-    uint4 *sparse;      // (sparse_cap) hits of SPARSE entries (envgs_trace.h: sparse_hits): {sorted ray slot, list position, surfel id, record slot}; counter[64] = how many
+    uint4 *sparse;      // (sparse_cap) hits of SPARSE entries (envgs_trace.h: sparse_hits): {sorted ray slot, list position, surfel id, record slot}; counter[ENVGS_CTR_SPARSE_FILED] = how many
     unsigned sparse_cap;
     int sparse_max;     // an entry with at most this many hits is filed per hit instead of becoming an entry of the batch kernel (0 = off)
     int reduce_adds;    // reduce_surfel_records adds its sums to what the buffers hold instead of storing them (the backward's deferred tail: the K-buffer pass ran before it)
@@ -178,7 +177,7 @@ struct TraceArgs {
     unsigned long long *entries;  // (batches, 64*cap) distinct (batch, surfel) entries, see register_hits
     unsigned *pairs;              // (batches, 64*cap) (lane << 16 | k) of every composited hit, grouped by entry
     int *n_entries;               // (batches, 2) table entries, single entries
-    unsigned *long_list; // (R) scratch: slots of the rays whose lists exceed 256 hits, appended by the main sort pass (counter[24 + seg] = how many)
+    unsigned *long_list; // (R) scratch: slots of the rays whose lists exceed 256 hits, appended by the main sort pass (counter[ENVGS_CTR_LONG_QUEUE + seg] = how many)
     float4 *state;      // per composited hit, for the backward, as two PLANES: plane 0 (16 B rows, row i at state[i]) = (transmittance before the hit, rgb
                         // prefix sums after it); plane 1 (behind the state_plane rows of plane 0; state_row1) = (depth, normal prefix sums) in 16 B rows, or
                         // -- with `others` -- (depth, normal, the two aux sums) in 24 B rows (round 6: the aux sums used to be a third plane of 8 B rows, a
@@ -626,7 +625,7 @@ __device__ __forceinline__ int xcc_id()
     return (int)(v & 7u);
 }
 
-__device__ __forceinline__ int fetch_batch(unsigned *ctr /*8 counters*/, int nbatch, int home, int lane)
+__device__ __forceinline__ int fetch_batch(unsigned *ctr /*one per XCD: ENVGS_CTR_BATCH_FETCH_STRIDE words*/, int nbatch, int home, int lane)
 {
     const int per = (nbatch + 7) >> 3;
     int b = -1;

@@ -10,13 +10,13 @@ trace_fwd(const TraceArgs A, const int ray_h, const int ray_w)
 {
     __shared__ int stk[STACK][64];
     const int lane = threadIdx.x;
-    // overflow pass after the list path: counter[1] holds the longest list of this call, counter[21] the rays that found no room in the compact
+    // overflow pass after the list path: ENVGS_CTR_MAX_LIST holds the longest list of this call, ENVGS_CTR_RAYS_WITHOUT_ROWS the rays that found no room in the compact
     // per-hit buffers -- nothing overflowed, nothing to do
-    if (A.only_overflow && (int)__hip_atomic_load(A.counter + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= A.cap &&
-        __hip_atomic_load(A.counter + 21, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) return;      // ([21]: rays the compact row scan handed over)
+    if (A.only_overflow && (int)__hip_atomic_load(A.counter + ENVGS_CTR_MAX_LIST, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= A.cap &&
+        __hip_atomic_load(A.counter + ENVGS_CTR_RAYS_WITHOUT_ROWS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) return;      // (rays the compact row scan handed over)
     while (true) {
         int base = 0;
-        if (lane == 0) base = (int)atomicAdd(A.counter, 64u);
+        if (lane == 0) base = (int)atomicAdd(A.counter + ENVGS_CTR_RAY_FETCH, 64u);
         base = __builtin_amdgcn_readfirstlane(base);
         if (base >= A.R) break;
         const int slot = base + lane;
@@ -123,9 +123,9 @@ trace_fwd(const TraceArgs A, const int ray_h, const int ray_w)
             // per-wavefront totals -> 3 atomics per 64 rays
             const float fh = wave_sum((float)st_hits), fv = wave_sum((float)st_visits), fr = wave_sum((float)st_rounds);
             if (lane == 0) {
-                atomicAdd(A.stats + 0, (unsigned long long)fh);
-                atomicAdd(A.stats + 1, (unsigned long long)fv);
-                atomicAdd(A.stats + 2, (unsigned long long)fr);
+                atomicAdd(A.stats + ENVGS_TOT_HITS, (unsigned long long)fh);
+                atomicAdd(A.stats + ENVGS_TOT_NODE_VISITS, (unsigned long long)fv);
+                atomicAdd(A.stats + ENVGS_TOT_ROUNDS, (unsigned long long)fr);
             }
         }
     }
@@ -138,13 +138,13 @@ trace_bwd(const TraceArgs A, const int ray_h, const int ray_w)
     __shared__ int stk[STACK][64];
     __shared__ float fld[NFLD][65];                 // row stride 65: lanes 48..62 read 15 different rows of one column conflict-free
     const int lane = threadIdx.x;
-    if (A.only_overflow && (int)__hip_atomic_load(A.counter + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= A.cap &&
-        __hip_atomic_load(A.counter + 21, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) return;      // ([21]: rays the compact row scan handed over)
+    if (A.only_overflow && (int)__hip_atomic_load(A.counter + ENVGS_CTR_MAX_LIST, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= A.cap &&
+        __hip_atomic_load(A.counter + ENVGS_CTR_RAYS_WITHOUT_ROWS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) return;      // (rays the compact row scan handed over)
     const FlushRole role = flush_role(A, lane);
     const int nb = (A.D + 1) * (A.D + 1);
     while (true) {
         int base = 0;
-        if (lane == 0) base = (int)atomicAdd(A.counter, 64u);
+        if (lane == 0) base = (int)atomicAdd(A.counter + ENVGS_CTR_RAY_FETCH, 64u);
         base = __builtin_amdgcn_readfirstlane(base);
         if (base >= A.R) break;
         const int slot = base + lane;

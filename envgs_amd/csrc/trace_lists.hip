@@ -337,7 +337,7 @@ sort_composite_fwd(const TraceArgs A)
             const int n = A.hit_cnt[r];
             if (n > A.cap) continue;                            // overflow: the K-buffer kernel owns this ray
             if (n > 256) {                                      // long: the LONG pass sorts it -- queued here, so that pass is one ray per wavefront step
-                if (A.long_list && lane == 0) A.long_list[A.batch0 * 64 + atomicAdd(A.counter + 24 + A.seg, 1u)] = (unsigned)slot;
+                if (A.long_list && lane == 0) A.long_list[A.batch0 * 64 + atomicAdd(A.counter + ENVGS_CTR_LONG_QUEUE + A.seg, 1u)] = (unsigned)slot;
                 continue;
             }
             if (n <= 64) sort_composite_ray<1, QSH>(A, slot, r, n, lane, st_hits);
@@ -347,18 +347,18 @@ sort_composite_fwd(const TraceArgs A)
         }
     } else {
         // the longest list so far (this segment's collection has finished, so its own maximum is in): nothing to do in the usual case
-        if ((int)__hip_atomic_load(A.counter + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= 256) return;
+        if ((int)__hip_atomic_load(A.counter + ENVGS_CTR_MAX_LIST,__ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= 256) return;
         if (A.long_list) {
             // the main pass queued the long rays of this segment: one ray per wavefront step, spread over the whole grid (neighbouring rays have
             // similar hit counts, so a wavefront that scanned its own 64-ray window used to sort a dozen long rays one after the other)
-            const int nl = (int)__hip_atomic_load(A.counter + 24 + A.seg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const int nl = (int)__hip_atomic_load(A.counter + ENVGS_CTR_LONG_QUEUE + A.seg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < nl; i += gridDim.x * 4) {
                 const int slot = (int)A.long_list[A.batch0 * 64 + i];
                 const int rr = ray_of(A, slot), nn = A.hit_cnt[rr];
                 if (EMAX == 8 || nn <= 512) sort_composite_ray<8, QSH>(A, slot, rr, nn, lane, st_hits);
                 else if constexpr (EMAX >= 16) sort_composite_ray<16, QSH>(A, slot, rr, nn, lane, st_hits);
             }
-            if (A.stats && lane == 0 && st_hits) atomicAdd(A.stats + 0, (unsigned long long)st_hits);
+            if (A.stats && lane == 0 && st_hits) atomicAdd(A.stats + ENVGS_TOT_HITS,(unsigned long long)st_hits);
             return;
         }
         for (int base = A.batch0 * 64 + (blockIdx.x * 4 + (threadIdx.x >> 6)) * 64; base < slot_end; base += gridDim.x * 256) {
@@ -375,7 +375,7 @@ sort_composite_fwd(const TraceArgs A)
             }
         }
     }
-    if (A.stats && lane == 0 && st_hits) atomicAdd(A.stats + 0, (unsigned long long)st_hits);
+    if (A.stats && lane == 0 && st_hits) atomicAdd(A.stats + ENVGS_TOT_HITS,(unsigned long long)st_hits);
 }
 
 // Register every composited hit with its surfel, per BATCH of 64 coherence-sorted rays.  The rays of a batch mostly composite the SAME
@@ -387,15 +387,15 @@ sort_composite_fwd(const TraceArgs A)
 //   entries[b][e]  e < D: the distinct surfels of the table, packed  sid | (hits-1) << 24 | slot << 32 ; singles that found no room in
 //                  the table are filed from the TOP of the region downwards (n_entries[2b] = D, n_entries[2b+1] = singles)
 //   pairs[b][...]  (lane << 16 | k) of every hit, grouped by entry in entry order (singles again from the top)
-// Claims n consecutive slots of the sparse-hit list (counters[64] = slots handed out so far): the first slot, or 0xFFFFFFFF when they do
-// not fit.  The counter only grows and only by claims that fit (compare-and-swap), so [0, counters[64]) is exactly the slots written, each
+// Claims n consecutive slots of the sparse-hit list (ENVGS_CTR_SPARSE_FILED = slots handed out so far): the first slot, or 0xFFFFFFFF when they do
+// not fit.  The counter only grows and only by claims that fit (compare-and-swap), so [0, ENVGS_CTR_SPARSE_FILED) is exactly the slots written, each
 // by the one claim that counted it, and a smaller later claim can still fit after a larger one failed.
 __device__ __forceinline__ unsigned sparse_claim(const TraceArgs &A, const unsigned n)
 {
-    unsigned cur = __hip_atomic_load(A.counter + 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    unsigned cur = __hip_atomic_load(A.counter + ENVGS_CTR_SPARSE_FILED,__ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     for (;;) {
         if (cur > A.sparse_cap || n > A.sparse_cap - cur) return 0xFFFFFFFFu;      // (sparse_cap <= 0xFFFFFFF0: a first slot never reads as the sentinel)
-        const unsigned prev = atomicCAS(A.counter + 64, cur, cur + n);
+        const unsigned prev = atomicCAS(A.counter + ENVGS_CTR_SPARSE_FILED,cur, cur + n);
         if (prev == cur) return cur;
         cur = prev;                                                             // another claim fitted first: the counter grew, try behind it
     }
@@ -535,7 +535,7 @@ register_hits(const TraceArgs A)
         // entry -- batch_surfel_bwd pays one 64-lane pass per entry however few of its lanes are live, and a fifth of the entries of the benchmark
         // view carry 1.4 % of its hits.  Its hits are filed in a global list instead (one lane of sparse_hits_bwd and one gradient record PER HIT:
         // the surfel's record count grows by its hit count).  List space is claimed per 64-surfel chunk by a compare-and-swap that adds only
-        // when the claim fits (sparse_claim); a chunk that does not fit files ordinary entries.  Space is never given back, so counters[64] is
+        // when the claim fits (sparse_claim); a chunk that does not fit files ordinary entries.  Space is never given back, so ENVGS_CTR_SPARSE_FILED is
         // exactly the number of hits filed and every slot below it is written by the chunk that counted it (an add-then-give-back claim left
         // holes and overlaps whenever two failed claims were in flight at once).
         const bool sparse_on = A.sparse != nullptr && A.sparse_max > 0 && ent != nullptr && prs != nullptr;
@@ -582,7 +582,7 @@ register_hits(const TraceArgs A)
                 carry_d += (unsigned)wave_bcast(dincl, 63);
             }
             if (A.n_entries && lane == 0) { A.n_entries[2 * batch] = (int)carry_d; A.n_entries[2 * batch + 1] = (int)nfail; }
-            if (ent && lane == 0) atomicAdd(A.counter + 65, carry_d + nfail);      // entries of the call (with counters[2..3], the composited hits: how coherent its batches are)
+            if (ent && lane == 0) atomicAdd(A.counter + ENVGS_CTR_BATCH_ENTRIES,carry_d + nfail);      // entries of the call (with ENVGS_TOT_HITS, the composited hits: how coherent its batches are)
             if (lane == 0) ptotal = carry_off;
         }
         __syncthreads();
@@ -665,7 +665,7 @@ register_hits(const TraceArgs A)
                         const unsigned pv = prs[region - 1 - f];
                         A.sparse[fbase + f] = make_uint4((unsigned)base + (pv >> 16), pv & 0xFFFFu, (unsigned)(ev & 0xFFFFFFull), (unsigned)(ev >> 32));
                     }
-                    if (threadIdx.x == 0) { if (A.n_entries) A.n_entries[2 * batch + 1] = 0; atomicSub(A.counter + 65, nfail); }
+                    if (threadIdx.x == 0) { if (A.n_entries) A.n_entries[2 * batch + 1] = 0; atomicSub(A.counter + ENVGS_CTR_BATCH_ENTRIES,nfail); }
                 }
             }
         }
@@ -761,7 +761,7 @@ row_offsets(const TraceArgs A, const unsigned *__restrict__ blk, unsigned *__res
         row_off[slot] = (unsigned)(fits ? row : 0ull);
         if (!fits && cnt > 0u) {                                     // the segment's share of the rows is used up: this ray (and every later one
             A.hit_cnt[ray_of(A, slot)] = A.cap + 1;                 // of the segment) takes the K-buffer kernels, like a ray whose list overflowed
-            atomicAdd(A.counter + 21, 1u);
+            atomicAdd(A.counter + ENVGS_CTR_RAYS_WITHOUT_ROWS, 1u);
         }
     }
     const unsigned tot = (unsigned)wave_bcast(incl, 63);

@@ -427,13 +427,13 @@ template __global__ void __attribute__((amdgpu_waves_per_eu(ENVGS_BSB_WAVES, ENV
 __global__ void __launch_bounds__(256)
 sparse_hits_bwd(const TraceArgs A, const int rgbo)
 {
-    const unsigned filed = __hip_atomic_load(A.counter + 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned filed = __hip_atomic_load(A.counter + ENVGS_CTR_SPARSE_FILED,__ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const unsigned n = filed < A.sparse_cap ? filed : A.sparse_cap;
     const int nb = (A.D + 1) * (A.D + 1);
     for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
         const uint4 e = A.sparse[i];
         // every entry is checked before it is used as an index: a ray slot of the call, a composited position of that ray's list, a surfel, a
-        // gradient record of the call.  One that fails is skipped and counted in counters[66] (zeroed by every backward; envgs_trace.h: sparse_hits)
+        // gradient record of the call.  One that fails is skipped and counted in ENVGS_CTR_SPARSE_SKIPPED (zeroed by every backward; envgs_trace.h: sparse_hits)
         // -- the claim in register_hits makes the list exact, so the count is 0 and a nonzero one is a bug to report, not an address to follow
         bool ok = e.x < (unsigned)A.R && e.z < (unsigned)A.P;
         int r = A.R;
@@ -445,7 +445,7 @@ sparse_hits_bwd(const TraceArgs A, const int rgbo)
             const size_t ci0 = (size_t)e.z * NCOPY + (((int)e.x >> 6) & (NCOPY - 1));
             ok = (unsigned long long)(A.surf_off[ci0] - A.surf_cnt[ci0]) + (unsigned long long)e.w < A.num_records;
         }
-        if (!ok) { atomicAdd(A.counter + 66, 1u); continue; }
+        if (!ok) { atomicAdd(A.counter + ENVGS_CTR_SPARSE_SKIPPED, 1u); continue; }
         const int slot = (int)e.x, k = (int)e.y, sid = (int)e.z;
         BwdRay B;
         bwd_load_ray(A, r, B);

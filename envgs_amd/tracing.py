@@ -60,16 +60,20 @@ def _stream(dev):
     return _lib.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
+def _check_vertices(v):
+    if v.dim() != 2 or v.shape[1] != 3 or v.shape[0] % 4 != 0:
+        raise RuntimeError("vertices must be (4P,3) in the get_disks layout, got %s" % (tuple(v.shape),))
+    if v.device.type != "cuda":
+        raise RuntimeError("envgs_amd tracer needs tensors on the GPU (got %s); there is no CPU path" % v.device)
+
+
 def build_bvh(vertices, opacities=None, debug=False, refit=None):
     """LBVH over the (4P,3) quad vertices (leaf boxes tightened by `opacities` when given).  Returns (nodes: envgs_bvh_node_floats(P) floats, P).
     refit: the `nodes` tensor of an earlier build over the same number of surfels -- its topology is kept and only the boxes are recomputed, in
     place (envgs_bvh_refit; OptiX's "update")."""
     lib = _lib.load()
     v = _f32c(vertices.detach())
-    if v.device.type != "cuda":
-        raise RuntimeError("envgs_amd tracer needs tensors on the GPU (got %s); there is no CPU path" % v.device)
-    if v.dim() != 2 or v.shape[1] != 3 or v.shape[0] % 4 != 0:
-        raise RuntimeError("vertices must be (4P,3) in the get_disks layout, got %s" % (tuple(v.shape),))
+    _check_vertices(v)
     P = v.shape[0] // 4
     dev = v.device
     nf = lib.envgs_bvh_node_floats(P)
@@ -108,6 +112,23 @@ HIT_CAP = {}                 # tests only: HIT_CAP["force"] pins the list capaci
 SORT_RAYS = {"on": True}     # coherence-sort the rays (direction, origin) before tracing
 
 
+def decode_counters(words, rays):
+    """What the mirrored head of a call's counter block (_lib.TRACE_COUNTER_MIRROR words, indexed by _lib.CTR_* / TOT_*) says to the next call of the
+    same tracer state, `rays` = the rays of the call that wrote it.  Pure: no GPU.  Returns (list capacity: 20 % above the longest list plus 8, up to a
+    multiple of 64 entries (512 B), within [64, 1024]; hits found per ray; composited hits per (batch, surfel) entry, None without entries)."""
+    u32 = lambda i: int(words[i]) & 0xFFFFFFFF
+    u64 = lambda t: u32(_lib.CTR_TOTALS + 2 * t) | (u32(_lib.CTR_TOTALS + 2 * t + 1) << 32)
+    mx = int(words[_lib.CTR_MAX_LIST])
+    want = ((int(mx * 1.2) + 8 + 63) // 64) * 64
+    if want > 256 and int(mx * 1.1) + 8 <= 256:
+        # 256 is a class boundary: a capacity above it adds the long-list launch to every forward segment (~0.04 ms per step even when it finds
+        # nothing to do: 512 workgroups scheduled onto a busy chip) -- not crossed for less than 10 % of headroom.  A ray that then finds more
+        # than 256 hits takes the K-buffer kernels, as with any capacity
+        want = 256
+    ent = u32(_lib.CTR_SPARSE_FILED) + u32(_lib.CTR_BATCH_ENTRIES)                # hits filed per hit + entries of the batch kernel
+    return max(64, min(want, 1024)), u64(_lib.TOT_FOUND) / max(1, rays), (u64(_lib.TOT_HITS) / ent if ent > 0 else None)
+
+
 class CapState:
     """Adaptive capacity of the per-ray hit lists, per TRACER INSTANCE (and device): 20 % above the longest list of that tracer's previous
     call, read through a pinned host mirror that was copied asynchronously at the end of that call -- no host sync on the hot path.  Two
@@ -121,11 +142,12 @@ class CapState:
         self.colour_only = False    # SurfelTracer.set_colour_only_backward: the backward will see the colour's gradient only -> store plane 0 alone
         self.defer_reduce = False   # SurfelTracer.set_deferred_surfel_gradients: the backward finishes the surfel gradients off the caller's stream
         self._mirrors = {}          # device -> dict(host, event, valid)
+        self._ring = [None, 0, [None] * 32]      # pinned_word: [pinned int32 x 32 (made on first use), last slot handed out, the slots' tokens]
 
     def mirror(self, dev):
         m = self._mirrors.get(dev)
         if m is None:
-            m = self._mirrors[dev] = dict(host=torch.zeros(72, dtype=torch.int32).pin_memory(), event=torch.cuda.Event(), valid=False, rays=1)
+            m = self._mirrors[dev] = dict(host=torch.zeros(_lib.TRACE_COUNTER_MIRROR, dtype=torch.int32).pin_memory(), event=torch.cuda.Event(), valid=False, rays=1)
         return m
 
     def next_cap(self, dev):
@@ -133,20 +155,8 @@ class CapState:
             return int(HIT_CAP["force"])
         m = self.mirror(dev)
         if m["valid"] and m["event"].query():
-            mx = int(m["host"][1])
-            want = ((int(mx * 1.2) + 8 + 63) // 64) * 64          # 20 % headroom, multiple of 64 entries (512 B)
-            if want > 256 and int(mx * 1.1) + 8 <= 256:
-                # 256 is a class boundary: a capacity above it adds the long-list launch to every forward segment (~0.04 ms per step even when it finds
-                # nothing to do: 512 workgroups scheduled onto a busy chip) -- not crossed for less than 10 % of headroom.  A ray that then finds more
-                # than 256 hits takes the K-buffer kernels, as with any capacity
-                want = 256
-            self.cap = max(64, min(want, 1024))
-            found = (int(m["host"][8]) & 0xFFFFFFFF) | ((int(m["host"][9]) & 0xFFFFFFFF) << 32)
-            self.found_per_ray = found / max(1, m["rays"])
-            hits = (int(m["host"][2]) & 0xFFFFFFFF) | ((int(m["host"][3]) & 0xFFFFFFFF) << 32)
-            ent = (int(m["host"][64]) & 0xFFFFFFFF) + (int(m["host"][65]) & 0xFFFFFFFF)       # hits filed per hit + entries of the batch kernel
-            if ent > 0:
-                self.hits_per_entry = hits / ent
+            self.cap, self.found_per_ray, hpe = decode_counters(m["host"], m["rays"])
+            self.hits_per_entry = self.hits_per_entry if hpe is None else hpe
         return self.cap
 
     def pinned_word(self):
@@ -154,7 +164,7 @@ class CapState:
         plus a TOKEN that identifies the claim: a forward whose slot was handed out again before its backward ran (more than 32 grad-enabled
         traced calls in between: eval renders without no_grad, many-view accumulation with retained graphs) finds a different token in the
         slot and reads its count from the device instead (trace_backward)."""
-        ring = self.__dict__.setdefault("_ring", [None, 0, [None] * 32])
+        ring = self._ring
         if ring[0] is None:
             ring[0] = torch.zeros(32, dtype=torch.int32).pin_memory()
         ring[1] = (ring[1] + 1) % 32
@@ -173,9 +183,9 @@ class CapState:
         return int(min(R * cap, max(int(per * R) + 4096, 4096)))
 
     def publish(self, counters, dev, rays=1):
-        """Queue the asynchronous read-back of this call's longest list (counters[1]) and of its total of hits found (counters[8:10])."""
+        """Queue the asynchronous read-back of the head of this call's counter block (decode_counters reads it)."""
         m = self.mirror(dev)
-        m["host"].copy_(counters[0:72], non_blocking=True)                 # (one copy of the head of the counter block: words 1, 2..3, 8..9, 64..65 are read)
+        m["host"].copy_(counters[0:_lib.TRACE_COUNTER_MIRROR], non_blocking=True)
         m["event"].record(torch.cuda.current_stream(dev)); m["valid"] = True; m["rays"] = int(rays)
 
 
@@ -208,9 +218,41 @@ def _carve_i32(dev, sizes):
         offs[k] = total
         total += ((int(n) + 63) // 64) * 64
     buf = torch.empty(max(total, 64), dtype=torch.int32, device=dev)
-    out = {k: buf[o:o + int(sizes[k])] for k, o in offs.items()}
-    out["_i32_block"] = buf
-    return out
+    return {k: buf[o:o + int(sizes[k])] for k, o in offs.items()}
+
+
+class _ListScratch:
+    """The list-path scratch of ONE traced call.  BUFFERS: the device buffers of struct envgs_trace_lists under its names (None = not passed).  records: a
+    record backward was prepared; rows: compact_rows; colour_only / defer_reduce: the tracer's promises; n_rec_*: the read-back of the record count."""
+    BUFFERS = ("hit_lists", "hit_cnt", "n_used", "surf_acc", "surf_cnt", "surf_off", "scan_temp", "ray_keys", "ray_order", "ray_sort_temp",
+               "hit_state", "entries", "pairs", "n_entries", "row_off", "batch_rows", "row_blk", "sh_perm", "sparse_hits", "bwd_order")
+    __slots__ = BUFFERS + ("cap", "scan_bytes", "sort_bytes", "rows", "sparse_cap", "records", "colour_only", "defer_reduce", "n_rec_host", "n_rec_claim", "n_rec_event")
+
+    def __init__(self, cap, scan_bytes, sort_bytes, **buffers):
+        for name in self.__slots__:
+            setattr(self, name, buffers.get(name))
+        self.cap, self.scan_bytes, self.sort_bytes, self.rows, self.sparse_cap = cap, scan_bytes, sort_bytes, 0, 0
+        self.records = self.colour_only = self.defer_reduce = False
+
+
+class _Saved:
+    """What trace_backward needs from trace_forward; `lists`: the _lib.TraceLists both calls pass (None = K-buffer path), `keep`: its _ListScratch."""
+    __slots__ = ("cfg", "nodes", "ro", "rd", "means3D", "scales", "rotations", "opacities", "shs", "colors_precomp", "others", "bg", "srec",
+                 "counters", "rgb", "dpt", "acc", "norm", "aux", "final_T", "lead", "lists", "keep", "cap")
+
+    def __init__(self, **fields):
+        for name in self.__slots__:
+            setattr(self, name, fields[name])
+
+
+def _trace_lists(k):
+    """struct envgs_trace_lists of a call from its scratch, field by field; a buffer the call does not have stays NULL."""
+    L = _lib.TraceLists(cap=k.cap, scan_temp_bytes=k.scan_bytes, ray_sort_temp_bytes=k.sort_bytes, compact_rows=k.rows, sparse_cap=k.sparse_cap,
+                        state_planes=1 if k.colour_only else 0)
+    for name in k.BUFFERS:
+        if getattr(k, name) is not None:
+            setattr(L, name, getattr(k, name).data_ptr())
+    return L
 
 
 # record backward: entries with few hits filed per hit (envgs_trace.h: sparse_hits).  "auto": when this tracer state's previous call averaged fewer than
@@ -238,25 +280,34 @@ def join_deferred_gradients():
     with set_deferred_surfel_gradients(True), the gradients of the SURFEL parameters are still being finished on a stream of the library's own;
     this makes the current stream wait for them.  No-op when nothing is pending.  envgs_amd.optim.FusedAdam.step, GradExchange and every later
     traced call do it themselves; any other consumer of those gradients (a torch optimizer, a hook, .grad arithmetic) must call it first."""
+    _wait_for_deferred(release=True)
+
+
+def _wait_for_deferred(release):
+    """The current stream waits for the pending deferred tail.  release=False: WITHOUT releasing it -- the buffers it writes stay held and a join
+    still has them to release, so the state a caller observes -- pending until someone joins -- is that of a backward without barriers."""
     if not _DEFERRED["pending"]:
         return
     dev = _DEFERRED["dev"]
     with torch.cuda.device(dev):
         _lib.check(_lib.load().envgs_trace_backward_join(_stream(dev)), "envgs_trace_backward_join")
-    _DEFERRED.update(pending=False, keep=None, dev=None)
+    if release:
+        _DEFERRED.update(pending=False, keep=None, dev=None)
 
 
-class _DeferBarrier(torch.autograd.Function):
-    """Identity in the forward; its backward joins the deferred surfel gradients before handing them on."""
+class _Barrier(torch.autograd.Function):
+    """Identity in the forward; its backward orders the current stream after the deferred tail before it hands the gradients on.  release
+    (defer_barrier): the tail is joined; without (leaf_barrier: a LEAF, where autograd may add to another consumer's gradient at once) it stays pending."""
 
     @staticmethod
-    def forward(ctx, *ts):
+    def forward(ctx, release, *ts):
+        ctx.release = release
         return tuple(t.view_as(t) for t in ts)
 
     @staticmethod
     def backward(ctx, *gs):
-        join_deferred_gradients()
-        return gs
+        join_deferred_gradients() if ctx.release else _wait_for_deferred(release=False)      # (the public name: callers may wrap it)
+        return (None,) + gs
 
 
 def defer_barrier(*tensors):
@@ -274,32 +325,8 @@ def defer_barrier(*tensors):
     same ordering for leaves, without the release).  Required: the returned tensors feed the tracer and nothing else (a second consumer of an OUTPUT
     gets its gradient added before the join; the inputs may have any number of consumers), and each parameter receives its tracer gradient from
     one traced call or bounce chain per barrier."""
-    outs = _DeferBarrier.apply(*tensors)
+    outs = _Barrier.apply(True, *tensors)
     return outs if len(tensors) != 1 else outs[0]
-
-
-def _order_after_deferred():
-    """Make the current stream wait for the pending deferred tail WITHOUT releasing it: the buffers it writes stay held, and join_deferred_gradients()
-    still has work to do (release them), so the state a caller observes -- pending until someone joins -- is that of a backward without barriers."""
-    if not _DEFERRED["pending"]:
-        return
-    dev = _DEFERRED["dev"]
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().envgs_trace_backward_join(_stream(dev)), "envgs_trace_backward_join")
-
-
-class _LeafBarrier(torch.autograd.Function):
-    """Identity in the forward; its backward orders the current stream after the deferred tail before it hands the gradients on to a LEAF, where
-    autograd may add them to another consumer's gradient at once (leaf_barrier)."""
-
-    @staticmethod
-    def forward(ctx, *ts):
-        return tuple(t.view_as(t) for t in ts)
-
-    @staticmethod
-    def backward(ctx, *gs):
-        _order_after_deferred()
-        return gs
 
 
 def leaf_barrier(*tensors):
@@ -310,13 +337,13 @@ def leaf_barrier(*tensors):
     pending (its buffers held) until join_deferred_gradients(), which FusedAdam.step, GradExchange and the next traced call do.  SurfelTracer.forward
     creates one at the call for every bare leaf surfel input; envgs_step.envgs_forward creates one before the base pass (where autograd reaches it
     after the base pass's backward has been queued: the overlap is kept).  The returned tensors must feed the tracer and nothing else."""
-    outs = _LeafBarrier.apply(*tensors)
+    outs = _Barrier.apply(False, *tensors)
     return outs if len(tensors) != 1 else outs[0]
 
 
 def _behind_barrier(t):
     fn = t.grad_fn
-    return fn is not None and type(fn).__name__ in ("_DeferBarrierBackward", "_LeafBarrierBackward") and not getattr(t, "_backward_hooks", None)
+    return fn is not None and type(fn).__name__ == "_BarrierBackward" and not getattr(t, "_backward_hooks", None)
 
 
 def trace_forward(nodes, ray_o, ray_d, means3D, shs, colors_precomp, others_precomp, opacities, scales, rotations, settings,
@@ -337,97 +364,76 @@ def trace_forward(nodes, ray_o, ray_d, means3D, shs, colors_precomp, others_prec
     ND = cfg.max_trace_depth + 1
     f32 = dict(dtype=torch.float32, device=dev)
     srec = torch.empty(max(P, 1), 16, **f32)
-    counters = torch.empty(96, dtype=torch.int32, device=dev)
+    counters = torch.empty(_lib.TRACE_COUNTER_WORDS, dtype=torch.int32, device=dev)
     rgb = torch.empty(R, 3, **f32); dpt = torch.empty(R, 1, **f32); acc = torch.empty(R, 1, **f32)
     norm = torch.empty(R, 3, **f32); dist = torch.empty(R, 1, **f32); aux = torch.empty(R, 2, **f32)
     mid = torch.empty(R, 16 * ND, **f32); wet = torch.empty(P, 1, **f32); final_T = torch.empty(R, **f32)
     cap = caps.next_cap(dev) if (use_lists and ND == 1 and P > 0 and R > 0) else 0
-    rows = 0
-    lists = None
-    keep = {}
+    rows, lists, k = 0, None, None
     if cap:
-        i32 = dict(dtype=torch.int32, device=dev)
-        sb = lib.envgs_raster_scan_temp_bytes(NCOPY * P)
-        rb = lib.envgs_trace_ray_sort_temp_bytes(R)
-        nbatch = (R + 63) // 64
+        sb, rb, nbatch = lib.envgs_raster_scan_temp_bytes(NCOPY * P), lib.envgs_trace_ray_sort_temp_bytes(R), (R + 63) // 64
         # the small int32 scratch of a call comes out of ONE allocation (a dozen torch.empty calls are ~0.1 ms of host time, and this code runs
         # right behind the rasterizer's one host sync, where the GPU has nothing queued)
-        keep = _carve_i32(dev, dict(hit_cnt=R, n_used=R, surf_acc=2 * P * NCOPY, surf_cnt=P * NCOPY,
+        k = _ListScratch(cap, sb, rb, **_carve_i32(dev, dict(hit_cnt=R, n_used=R, surf_acc=2 * P * NCOPY, surf_cnt=P * NCOPY,
                                     surf_off=P * NCOPY, scan_temp=(max(sb, 1) + 3) // 4, ray_keys=2 * R, ray_order=2 * R, ray_sort_temp=(max(rb, 1) + 3) // 4,
-                                    n_entries=2 * nbatch, row_off=R, batch_rows=2 * nbatch, row_blk=nbatch + 16, bwd_order=nbatch))
-        keep["n_entries"] = keep["n_entries"].view(nbatch, 2)
-        keep["hit_lists"] = _scratch((R, cap, 2), torch.int32, dev)
+                                    n_entries=2 * nbatch, row_off=R, batch_rows=2 * nbatch, row_blk=nbatch + 16, bwd_order=nbatch)))
+        k.hit_lists = _scratch((R, cap, 2), torch.int32, dev)
         srt = SORT_RAYS["on"]
         if shs is not None and shs.shape[1] == 16 and QUAD_SH["on"]:
-            keep["sh_perm"] = torch.empty(P, 48, dtype=shs.dtype, device=dev)      # quad-permuted SH copy (envgs_trace.h: sh_perm)
+            k.sh_perm = torch.empty(P, 48, dtype=shs.dtype, device=dev)      # quad-permuted SH copy (envgs_trace.h: sh_perm)
         if need_grad:
             # what the record backward needs from the forward: per-hit state, and the (batch, surfel) entries with their (lane, k) pairs.
             # COMPACT: rows follow the hits the rays actually have (a prefix sum of the hit counts, taken on the device between the collection
             # and the sort) instead of rays x capacity -- a ray uses a third of its capacity (42 -> 19 GB for a 1.92 M-ray stage)
-            colour_only = bool(getattr(caps, "colour_only", False))
-            sw = 4 if colour_only else (10 if others_precomp is not None else 8)     # floats per row: two 16 B planes (+ one 8 B plane with `others`); colour only: plane 0
-            if COMPACT["on"] and srt:
-                rows = caps.next_rows(R, cap)
-                keep.update(hit_state=_scratch((rows, sw), torch.float32, dev), entries=_scratch((rows,), torch.int64, dev), pairs=_scratch((rows,), torch.int32, dev))
-            else:
-                keep.update(hit_state=_scratch((R, cap, sw), torch.float32, dev), entries=_scratch((nbatch, 64 * cap), torch.int64, dev),
-                            pairs=_scratch((nbatch, 64 * cap), torch.int32, dev))
+            k.records, k.colour_only, k.defer_reduce = True, bool(caps.colour_only), bool(caps.defer_reduce)
+            sw = 4 if k.colour_only else (10 if others_precomp is not None else 8)     # floats per row: two 16 B planes (+ one 8 B plane with `others`); colour only: plane 0
+            compact = COMPACT["on"] and srt
+            k.rows = rows = caps.next_rows(R, cap) if compact else 0
+            ent = (rows,) if compact else (nbatch, 64 * cap)
+            k.hit_state = _scratch((rows, sw) if compact else (R, cap, sw), torch.float32, dev)
+            k.entries, k.pairs = _scratch(ent, torch.int64, dev), _scratch(ent, torch.int32, dev)
+        k.n_entries = k.n_entries.view(nbatch, 2) if k.records else None      # (None: a view of the carved block that this call does not pass)
+        if not (k.records and BWD_ORDER["on"]): k.bwd_order = None      # (else: the record backward's batches, longest first -- envgs_trace.h: bwd_order)
+        if not srt: k.ray_keys = k.ray_order = k.ray_sort_temp = None
+        if not rows: k.row_off = k.batch_rows = k.row_blk = None
         sparse = SPARSE["mode"] == "on" or (SPARSE["mode"] == "auto" and caps.hits_per_entry is not None and caps.hits_per_entry < SPARSE["below"])
-        if "hit_state" in keep and sparse:
+        if k.records and sparse:
             # sparse entries (envgs_trace.h: sparse_hits): the previous call of this tracer state was INCOHERENT (few hits per (batch, surfel) entry:
             # bounce rays off rough geometry) -- entries of at most four hits are filed per hit; room for every row (most hits of such a call are
             # filed; what finds no room takes the batch kernel -- slower, never wrong)
-            n_rows = rows if rows else R * cap
-            keep["sparse_hits"] = _scratch((max(4096, n_rows), 4), torch.int32, dev)
+            k.sparse_hits = _scratch((max(4096, rows if rows else R * cap), 4), torch.int32, dev)
             if SPARSE.get("poison") is not None:
-                keep["sparse_hits"].fill_(int(SPARSE["poison"]))
-        sparse_cap = 0
-        if "sparse_hits" in keep:
-            sparse_cap = keep["sparse_hits"].shape[0] if SPARSE.get("cap") is None else min(int(SPARSE["cap"]), keep["sparse_hits"].shape[0])
-        lists = _lib.TraceLists(keep["hit_lists"].data_ptr(), keep["hit_cnt"].data_ptr(), keep["n_used"].data_ptr(), cap,
-                                keep["surf_acc"].data_ptr(), keep["surf_cnt"].data_ptr(), keep["surf_off"].data_ptr(),
-                                keep["scan_temp"].data_ptr(), sb, keep["ray_keys"].data_ptr() if srt else None,
-                                keep["ray_order"].data_ptr() if srt else None, keep["ray_sort_temp"].data_ptr() if srt else None, rb, None, 0,
-                                *[(keep[k].data_ptr() if k in keep else None) for k in ("hit_state", "entries", "pairs")],
-                                keep["n_entries"].data_ptr() if "hit_state" in keep else None, rows,
-                                *[(keep[k].data_ptr() if (k in keep and rows) else None) for k in ("row_off", "batch_rows", "row_blk")],
-                                keep["sh_perm"].data_ptr() if "sh_perm" in keep else None, 0,
-                                keep["sparse_hits"].data_ptr() if "sparse_hits" in keep else None, sparse_cap)
-        if "hit_state" in keep and BWD_ORDER["on"]:
-            lists.bwd_order = keep["bwd_order"].data_ptr()   # the record backward's batches, longest first (envgs_trace.h: bwd_order)
-        if "hit_state" in keep and getattr(caps, "colour_only", False):
-            lists.state_planes = 1
-            keep["colour_only"] = True
-        if "hit_state" in keep and getattr(caps, "defer_reduce", False):
-            keep["defer_reduce"] = True
+                k.sparse_hits.fill_(int(SPARSE["poison"]))
+            k.sparse_cap = k.sparse_hits.shape[0] if SPARSE.get("cap") is None else min(int(SPARSE["cap"]), k.sparse_hits.shape[0])
+        lists = _trace_lists(k)
     p = _lib.ptr
     _lib.check(lib.envgs_trace_forward(cfg, p(nodes), p(ro), p(rd), p(means3D), p(scales), p(rotations), p(opacities), p(shs),
                                        p(colors_precomp), p(others_precomp), p(bg), p(srec), p(counters), p(rgb), p(dpt), p(acc),
                                        p(norm), p(dist), p(aux), p(mid), p(wet), p(final_T), lists, _stream(dev)), "envgs_trace_forward")
-    LAST_STATS.update(P=P, R=R, caps=caps, rows=rows, counters=counters, n_entries=(keep.get("n_entries") if "hit_state" in keep else None), cap=cap,
-                      lists=((keep["hit_lists"], keep["n_used"], keep["hit_cnt"]) if (cap and KEEP_LISTS["on"]) else None),
-                      records=(dict(sparse_hits=keep.get("sparse_hits"), sparse_cap=sparse_cap, entries=keep["entries"], pairs=keep["pairs"],
-                                    n_entries=keep["n_entries"], batch_rows=(keep["batch_rows"].view(-1, 2) if rows else None),
-                                    ray_order=(keep["ray_order"][R:] if SORT_RAYS["on"] else None), surf_cnt=keep["surf_cnt"], surf_off=keep["surf_off"],
-                                    bwd_order=(keep["bwd_order"] if BWD_ORDER["on"] else None))
-                               if (cap and KEEP_LISTS["on"] and "hit_state" in keep) else None))
+    records = k is not None and k.records
+    LAST_STATS.update(P=P, R=R, caps=caps, rows=rows, counters=counters, n_entries=(k.n_entries if records else None), cap=cap,
+                      lists=((k.hit_lists, k.n_used, k.hit_cnt) if (cap and KEEP_LISTS["on"]) else None),
+                      records=(dict(sparse_hits=k.sparse_hits, sparse_cap=k.sparse_cap, entries=k.entries, pairs=k.pairs,
+                                    n_entries=k.n_entries, batch_rows=(k.batch_rows.view(-1, 2) if rows else None),
+                                    ray_order=(k.ray_order[R:] if k.ray_order is not None else None), surf_cnt=k.surf_cnt, surf_off=k.surf_off,
+                                    bwd_order=k.bwd_order)
+                               if (records and KEEP_LISTS["on"]) else None))
     if cap:
-        if "hit_state" in keep and not KEEP_LISTS["on"]:
+        if records and not KEEP_LISTS["on"]:
             # the record backward reads the hit counts, the per-hit state and the entries / pairs -- not the lists themselves (rays x capacity
             # x 8 B: the largest buffer of the call, 4.9 GB per stage of the 1200x1600 two-bounce configuration): released here, so that the
             # next stage / the next call re-uses the block instead of three stages holding one each until their backward
-            keep.pop("hit_lists")
-            lists.hit_lists = None
+            k.hit_lists = lists.hit_lists = None
         # asynchronous read-backs for later: the longest list (sizes the next call's cap) and the number of gradient records
         caps.publish(counters, dev, rays=R)
-        if "hit_state" in keep:                                   # (a pinned word from the tracer's ring: pinning host memory per call is ~0.1 ms)
-            keep["n_rec_host"], keep["n_rec_claim"] = caps.pinned_word()
-            keep["n_rec_host"].copy_(keep["surf_off"].view(-1)[NCOPY * P - 1:NCOPY * P], non_blocking=True)
-            keep["n_rec_event"] = torch.cuda.Event(); keep["n_rec_event"].record(torch.cuda.current_stream(dev))
-    saved = dict(cfg=cfg, nodes=nodes, ro=ro, rd=rd, means3D=means3D, scales=scales, rotations=rotations, opacities=opacities,
-                 shs=shs, colors_precomp=colors_precomp, others=others_precomp, bg=bg, srec=srec, counters=counters,
-                 rgb=(rgb if ND == 1 else mid[:, 13:16].contiguous()),      # (C-ABI in-kernel bounces, forward use only: stage 0's own colour)
-                 dpt=dpt, acc=acc, norm=norm, aux=aux, final_T=final_T, lead=lead, lists=lists, keep=keep, cap=cap)
+        if records:                                               # (a pinned word from the tracer's ring: pinning host memory per call is ~0.1 ms)
+            k.n_rec_host, k.n_rec_claim = caps.pinned_word()
+            k.n_rec_host.copy_(k.surf_off.view(-1)[NCOPY * P - 1:NCOPY * P], non_blocking=True)
+            k.n_rec_event = torch.cuda.Event(); k.n_rec_event.record(torch.cuda.current_stream(dev))
+    saved = _Saved(cfg=cfg, nodes=nodes, ro=ro, rd=rd, means3D=means3D, scales=scales, rotations=rotations, opacities=opacities,
+                   shs=shs, colors_precomp=colors_precomp, others=others_precomp, bg=bg, srec=srec, counters=counters,
+                   rgb=(rgb if ND == 1 else mid[:, 13:16].contiguous()),      # (C-ABI in-kernel bounces, forward use only: stage 0's own colour)
+                   dpt=dpt, acc=acc, norm=norm, aux=aux, final_T=final_T, lead=lead, lists=lists, keep=k, cap=cap)
     outs = (rgb.reshape(lead + (3,)), dpt.reshape(lead + (1,)), acc.reshape(lead + (1,)), norm.reshape(lead + (3,)),
             dist.reshape(lead + (1,)), aux.reshape(lead + (2,)), mid.reshape(lead + (16 * ND,)), wet)
     return outs, saved
@@ -448,17 +454,15 @@ def trace_backward(saved, g_rgb, g_dpt, g_acc, g_norm, g_aux, chain=None, allow_
     """chain = (a _BounceChain, this call's stage index) for the stages of a multi-bounce forward whose tracer defers its surfel gradients;
     allow_defer = False: the autograd node found a surfel input that is not a plain leaf without a gradient and without hooks -- stream-ordered then."""
     lib = _lib.load()
-    cfg = saved["cfg"]
+    s, k, cfg, lists = saved, saved.keep, saved.cfg, saved.lists
     P, R = cfg.P, cfg.num_rays
-    dev = saved["ro"].device
+    dev = s.ro.device
     f32 = dict(dtype=torch.float32, device=dev)
     z = lambda g, c: None if g is None else _f32c(g).reshape(R, c)          # an output the loss does not use: NULL = zero upstream gradient
     g_rgb, g_dpt, g_acc, g_norm, g_aux = z(g_rgb, 3), z(g_dpt, 1), z(g_acc, 1), z(g_norm, 3), z(g_aux, 2)
-    shs, others = saved["shs"], saved["others"]
+    shs, others = s.shs, s.others
     p = _lib.ptr
-    s = saved
-    lists = s["lists"]
-    defer = bool(allow_defer and lists is not None and "hit_state" in s["keep"] and s["keep"].get("defer_reduce"))
+    defer = bool(allow_defer and lists is not None and k.records and k.defer_reduce)
     chained = defer and chain is not None
     if chain is not None:
         if (not defer and chain[0].acc is not None) or (defer and chain[0].plain):
@@ -485,27 +489,27 @@ def trace_backward(saved, g_rgb, g_dpt, g_acc, g_norm, g_aux, chain=None, allow_
     dothers = torch.empty(P, 2, **f32) if others is not None else None
     dro = torch.empty(R, 3, **f32); drd = torch.empty(R, 3, **f32)
     records = None
-    if lists is not None and s["keep"].get("colour_only") and any(g_ is not None for g_ in (g_dpt, g_acc, g_norm, g_aux)):
+    if lists is not None and k.colour_only and any(g_ is not None for g_ in (g_dpt, g_acc, g_norm, g_aux)):
         raise RuntimeError("SurfelTracer: set_colour_only_backward(True) promised that only the colour output would be differentiated, but a gradient "
                            "arrived for dpt / acc / norm / aux -- the forward kept the colour's per-hit state only; switch the promise off")
-    if lists is not None and "hit_state" in s["keep"]:
+    if lists is not None and k.records:
         # atomic-free backward: one 256 B record per (batch, surfel) entry, grouped by surfel.  The count is known on the device
         # (inclusive scan of the per-surfel entry counts, done at the end of the forward); reading it is the one host sync here.
-        s["keep"]["n_rec_event"].synchronize()         # copied at the end of the forward; long since complete
-        slots, slot, token = s["keep"]["n_rec_claim"]
+        k.n_rec_event.synchronize()                     # copied at the end of the forward; long since complete
+        slots, slot, token = k.n_rec_claim
         if slots[slot] is token:
-            n_rec = int(s["keep"]["n_rec_host"][0]) & 0xFFFFFFFF if P > 0 else 0
+            n_rec = int(k.n_rec_host[0]) & 0xFFFFFFFF if P > 0 else 0
         else:                                           # the pinned slot was re-used by a later forward: synchronous read of this forward's own scan
-            n_rec = int(s["keep"]["surf_off"].view(-1)[NCOPY * P - 1].item()) & 0xFFFFFFFF if P > 0 else 0
+            n_rec = int(k.surf_off.view(-1)[NCOPY * P - 1].item()) & 0xFFFFFFFF if P > 0 else 0
         if n_rec > 0:
             records = _scratch((n_rec, 64), torch.float32, dev)
             lists.records = records.data_ptr()
             lists.num_records = n_rec
     if lists is not None:
         lists.defer_reduce = (1 if defer else 0) | (0 if first else 2) | (0 if last else 4)
-    _lib.check(lib.envgs_trace_backward(cfg, p(s["nodes"]), p(s["ro"]), p(s["rd"]), p(s["means3D"]), p(s["scales"]), p(s["rotations"]),
-                                        p(s["opacities"]), p(shs), p(s["colors_precomp"]), p(others), p(s["bg"]), p(s["srec"]),
-                                        p(s["counters"]), p(s["rgb"]), p(s["dpt"]), p(s["acc"]), p(s["norm"]), p(s["aux"]), p(s["final_T"]),
+    _lib.check(lib.envgs_trace_backward(cfg, p(s.nodes), p(s.ro), p(s.rd), p(s.means3D), p(s.scales), p(s.rotations),
+                                        p(s.opacities), p(shs), p(s.colors_precomp), p(others), p(s.bg), p(s.srec),
+                                        p(s.counters), p(s.rgb), p(s.dpt), p(s.acc), p(s.norm), p(s.aux), p(s.final_T),
                                         p(g_rgb), p(g_dpt), p(g_acc), p(g_norm), p(g_aux), p(geo_rec), p(dmeans), p(dgrads3D), p(dscales),
                                         p(drots), p(dopac), p(dshs), p(dcolors), p(dothers), p(dro), p(drd), lists, _stream(dev)),
                "envgs_trace_backward")
@@ -515,7 +519,7 @@ def trace_backward(saved, g_rgb, g_dpt, g_acc, g_norm, g_aux, chain=None, allow_
         # STORAGES, so that autograd still sees the returned tensors as unshared and moves them into .grad instead of copying them
         held = [saved] + [t.untyped_storage() for t in (geo_rec, records, dmeans, dgrads3D, dscales, drots, dopac, dshs, dcolors) if t is not None]
         _DEFERRED.update(pending=True, dev=dev, keep=(_DEFERRED["keep"] or []) + held)
-    lead = s["lead"]
+    lead = s.lead
     if not last:
         dshs = dcolors = None                            # (the accumulators: stage 0 returns them)
     return dict(ray_o=dro.reshape(lead + (3,)), ray_d=drd.reshape(lead + (3,)), means3D=dmeans, grads3D=dgrads3D, shs=dshs,
@@ -573,7 +577,6 @@ def invalidate_all_structures():
     _SCENE_EPOCH[0] += 1
 
 
-
 def _build_stream(dev):
     s = _BUILD_STREAMS.get(dev)
     if s is None:
@@ -590,8 +593,7 @@ class _TraceSurfels(torch.autograd.Function):
         from .raster import _store                       # fp16 feature storage selected (envgs_amd.set_feature_storage): half copies made HERE, fp32 gradients
         outs, saved = trace_forward(nodes, ray_o, ray_d, means3D, _store(none(shs)), _store(none(colors_precomp)), none(others_precomp), opacities,
                                     scales, rotations, tracer_settings, start_from_first, need_grad=any(ctx.needs_input_grad), caps=caps)
-        ctx.saved = saved
-        ctx.chain = chain
+        ctx.saved, ctx.chain = saved, chain
         # deferred surfel gradients (set_deferred_surfel_gradients) are only safe when autograd does nothing with them but MOVE them into .grad: every
         # differentiated surfel input must be a leaf (a non-leaf's gradient is fed to the next backward node on the current stream at once); whether
         # it has a .grad to add into, or hooks that would read it, is looked at when the backward runs
@@ -632,6 +634,9 @@ class SurfelTracer(nn.Module):
         self._policy = dict(mode="adaptive", max_age=16, max_growth=1.25)
         self._age = 0                     # structures derived from the last full build by refits
         self._q = None                    # quality read-backs: dict(host=pinned (2,2) floats, build=(event, row), last=(event, row))
+        self._build_event = None          # prepare() built the structure on the side stream: recorded there, waited for by its first consumer
+        self._epoch = 0                   # _SCENE_EPOCH at this tracer's last invalidate_structure()
+        self._bounce_caps = {}            # bounce stage -> CapState (bounce_caps)
 
     def set_structure_policy(self, mode=None, max_age=None, max_growth=None):
         """OPTIONAL, not part of the reference interface.  How a `rebuild=True` request is served when the surfel count is unchanged:
@@ -654,10 +659,8 @@ class SurfelTracer(nn.Module):
         set was re-indexed or moved wholesale without changing its size (prune + densify, opacity reset).  envgs_amd.densify.SurfelSet says so
         for every tracer of the process through `invalidate_all_structures()`; the unchanged EasyVolcap GaussianModel does not, and pays ONE
         badly fitted refit before the quality guard rebuilds."""
-        self._keep = None
-        self.nodes = None
-        self._age = 0
-        self._epoch = _SCENE_EPOCH[0]
+        self._keep = self.nodes = None
+        self._age, self._epoch = 0, _SCENE_EPOCH[0]
 
     def _refit_allowed(self):
         pol = self._policy
@@ -697,17 +700,14 @@ class SurfelTracer(nn.Module):
         the region where it can still contribute (tighter boxes, identical results)."""
         if faces is not None and faces.shape[0] * 2 != vertices.shape[0]:
             raise RuntimeError("faces (%d,3) do not match vertices (%d,3): expected 2 triangles per 4 vertices" % (faces.shape[0], vertices.shape[0]))
-        if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.shape[0] % 4 != 0:
-            raise RuntimeError("vertices must be (4P,3) in the get_disks layout, got %s" % (tuple(vertices.shape),))
-        if vertices.device.type != "cuda":
-            raise RuntimeError("envgs_amd tracer needs tensors on the GPU (got %s); there is no CPU path" % vertices.device)
+        _check_vertices(vertices)
         # rebuild=False is OptiX's "update": the topology of the existing structure is kept and its boxes are refitted to the new vertices
         # (envgs_bvh_refit) -- exact, the hit sets are those of a fresh build.  Nothing to update (first call, or P changed): a full build.
         # The reference itself only ever passes rebuild=True (optix_utils.py:78), which rebuilds, like its OptiX GAS.
-        ev = self.__dict__.pop("_build_event", None)
+        ev, self._build_event = self._build_event, None
         if ev is not None and self.nodes is not None:
             torch.cuda.current_stream(self.nodes.device).wait_event(ev)       # (a build started by prepare() that no trace has consumed)
-        if self.__dict__.get("_epoch", 0) != _SCENE_EPOCH[0]:      # invalidate_all_structures() since this tracer's last build: topology is stale
+        if self._epoch != _SCENE_EPOCH[0]:      # invalidate_all_structures() since this tracer's last build: topology is stale
             self.invalidate_structure()
         have = self.nodes if self.nodes is not None else self._keep
         same = have is not None and vertices.shape[0] // 4 == self.num_surfels
@@ -787,9 +787,8 @@ class SurfelTracer(nn.Module):
                 raise RuntimeError("SurfelTracer: acceleration structure was requested for %d surfels, call has %d" % (self._pending.shape[0] // 4, means3D.shape[0]))
             self.nodes, self.num_surfels = build_bvh(self._pending, opacities, refit=self._keep)
             self._built(LAST_STATS["bvh"] == "refit")
-            self._pending = None
-            self._keep = None
-        ev = self.__dict__.pop("_build_event", None)
+            self._pending = self._keep = None
+        ev, self._build_event = self._build_event, None
         if ev is not None:                                             # built ahead on the side stream (prepare()): order this stream behind it
             cur = torch.cuda.current_stream(self.nodes.device)
             cur.wait_event(ev)
@@ -820,10 +819,9 @@ class SurfelTracer(nn.Module):
 
     def bounce_caps(self, k):
         """Bounce stage k traces a different ray population (fewer, less coherent rays) than stage 0: its own capacity state."""
-        st = self.__dict__.setdefault("_bounce_caps", {})
-        if k not in st:
-            st[k] = CapState(self.caps.cap)
-        return st[k]
+        if k not in self._bounce_caps:
+            self._bounce_caps[k] = CapState(self.caps.cap)
+        return self._bounce_caps[k]
 
     def _forward_bounces(self, ray_o, ray_d, args, settings, start_from_first, barred=()):
         """max_trace_depth > 0 (gaussian2d_sampler.py:413-426, optix_utils.py:117-118): every stage is one bounce-free traced call
@@ -931,7 +929,9 @@ def last_trace_counts():
     c = LAST_STATS.get("counters")
     if c is None:
         return None
-    w = c.cpu()
-    v = w[2:20].view(torch.int64)
-    return dict(coop_cycles=dict(expand=int(v[6]), walk=int(v[7]), wait=int(v[8])), hits=int(v[0]), node_visits=int(v[1]), rounds=int(v[2]), found=int(v[3]), packet_nodes=int(v[4]), packet_leaves=int(v[5]),
-                max_list=int(w[1]), sparse_hits=int(w[64]), sparse_invalid=int(w[66]), cap=LAST_STATS["caps"].cap, compact_rows=LAST_STATS.get("rows", 0), rays_without_rows=int(w[21]), rays=LAST_STATS["R"], stack_overflows=int(w[20]))
+    w, C = c.cpu(), _lib
+    v = w[C.CTR_TOTALS:C.CTR_TOTALS + 2 * C.TOT_COUNT].view(torch.int64)
+    return dict(coop_cycles=dict(expand=int(v[C.TOT_COOP_EXPAND]), walk=int(v[C.TOT_COOP_WALK]), wait=int(v[C.TOT_COOP_WAIT])), hits=int(v[C.TOT_HITS]), node_visits=int(v[C.TOT_NODE_VISITS]),
+                rounds=int(v[C.TOT_ROUNDS]), found=int(v[C.TOT_FOUND]), packet_nodes=int(v[C.TOT_PACKET_NODES]), packet_leaves=int(v[C.TOT_PACKET_LEAVES]), max_list=int(w[C.CTR_MAX_LIST]),
+                sparse_hits=int(w[C.CTR_SPARSE_FILED]), sparse_invalid=int(w[C.CTR_SPARSE_SKIPPED]), cap=LAST_STATS["caps"].cap, compact_rows=LAST_STATS.get("rows", 0),
+                rays_without_rows=int(w[C.CTR_RAYS_WITHOUT_ROWS]), rays=LAST_STATS["R"], stack_overflows=int(w[C.CTR_STACK_OVERFLOWS]))

@@ -172,14 +172,15 @@ ENVGS_API const char *envgs_prof_kernel_name(int kernel_id);
 /*
  * Diagnostic switches for experiments and tests (scratch/, tests/, bench.py --debug-*): process-global, all 0 in production.
  * The library never reads the environment; whoever sets a switch is responsible for reporting it (bench.py prints them).
- *   ENVGS_DBG_TRACE  bit mask: 64 = no coherence sort of the rays,
- *                    1024 = packet stack limited to 2 entries (forces the stack-overflow hand-off to the K-buffer path; tests only),
- *                    16384 = forward_prepare on the caller's stream after the coherence sort instead of beside it on the second stream (round-6 A/B).
- *                    8, 16, 512, 2048, 4096 and 8192 selected A/B kernels that have been deleted (profiles/DEAD_ENDS.md): envgs_trace_forward /
- *                    envgs_trace_backward answer ENVGS_ERR_BAD_ARG to any of them, in both builds
+ *   ENVGS_DBG_TRACE  bit mask of the ENVGS_DBG_TRACE_* bits below
  *   ENVGS_DBG_SEGMENTS  forward batch segments of the tracer (0 = default 2; 1 = single launch)
  */
 #define ENVGS_DBG_TRACE 0
+#define ENVGS_DBG_TRACE_NO_SORT 64              /* no coherence sort of the rays */
+#define ENVGS_DBG_TRACE_SMALL_STACK 1024        /* packet stack limited to 2 entries (forces the stack-overflow hand-off to the K-buffer path; tests only) */
+#define ENVGS_DBG_TRACE_PREPARE_INLINE 16384    /* forward_prepare on the caller's stream after the coherence sort instead of beside it on the second stream (round-6 A/B) */
+#define ENVGS_DBG_TRACE_RETIRED (8 | 16 | 512 | 2048 | 4096 | 8192)   /* selected A/B kernels that have been deleted (profiles/DEAD_ENDS.md): envgs_trace_forward /
+                                                                         envgs_trace_backward answer ENVGS_ERR_BAD_ARG to any of them, in both builds */
 #define ENVGS_DBG_SEGMENTS 1
 #define ENVGS_DBG_COLLECT_WGS 2      /* workgroups per CU of the cooperative collection's persistent grid (0 = default: 4 for each of two segments in flight, 8 for a single one) */
 #define ENVGS_DBG_RASTER_EXACT 3     /* libenvgs_hip_diag.so only: R6 / R7 with IEEE divisions and the library expf instead of v_rcp_f32 (+ Newton) / v_exp_f32 -- the attribution run of the parity tests; no effect in the product library */

@@ -63,6 +63,49 @@ typedef struct envgs_trace_cfg {
 } envgs_trace_cfg;
 
 /*
+ * The counter block of a traced call: `counters`, ENVGS_TRACE_COUNTER_WORDS uint32 of caller-allocated device scratch, zeroed by every
+ * envgs_trace_forward and read by the caller afterwards (the first ENVGS_TRACE_COUNTER_MIRROR words are what a host mirror needs).
+ * Every word in use has a name; a word without one is free.
+ */
+#define ENVGS_TRACE_COUNTER_WORDS 96
+#define ENVGS_TRACE_COUNTER_MIRROR 72
+#define ENVGS_TRACE_MAX_SEG 4              /* forward batch segments that may run concurrently (the segment-indexed words below) */
+#define ENVGS_CTR_RAY_FETCH 0              /* next ray of the K-buffer kernels' persistent grids (zeroed again by the backward) */
+#define ENVGS_CTR_MAX_LIST 1               /* the largest hit_cnt of the call: the caller sizes `cap` of its next call from it */
+#define ENVGS_CTR_TOTALS 2                 /* ENVGS_TOT_COUNT uint64 totals (two words each; diagnostics, and the roofline accounting of bench.py:
+                                              BASELINE.md section 4 "hits / node_visits are data dependent"), indexed by ENVGS_TOT_*: */
+#define ENVGS_TOT_HITS 0                   /*   composited hits */
+#define ENVGS_TOT_NODE_VISITS 1            /*   BVH nodes visited by the K-buffer traversal */
+#define ENVGS_TOT_ROUNDS 2                 /*   K-buffer traversal rounds */
+#define ENVGS_TOT_FOUND 3                  /*   hits found by the collection (the caller sizes compact_rows of its next call from it) */
+#define ENVGS_TOT_PACKET_NODES 4           /*   wide nodes visited by the packet traversal */
+#define ENVGS_TOT_PACKET_LEAVES 5          /*   leaf tests of the packet traversal */
+#define ENVGS_TOT_COOP_EXPAND 6            /*   cycles of the cooperative collection: expanding the packet's frontier, */
+#define ENVGS_TOT_COOP_WALK 7              /*   walking subtrees, */
+#define ENVGS_TOT_COOP_WAIT 8              /*   waiting for the other wavefronts of the workgroup */
+#define ENVGS_TOT_COUNT 9
+#define ENVGS_CTR_STACK_OVERFLOWS 20       /* 64-ray batches whose packet traversal ran out of its shared stack (their rays were handed to the
+                                              K-buffer kernels, nothing is dropped) */
+#define ENVGS_CTR_RAYS_WITHOUT_ROWS 21     /* rays that found no room in the compact per-hit buffers (handed to the K-buffer kernels) */
+#define ENVGS_CTR_ROW_CLAIM 22             /* rows of the compact per-hit buffers claimed so far by the call's segments */
+#define ENVGS_CTR_LONG_QUEUE 24            /* + segment: length of the segment's queue of rays with more than 256 hits */
+#define ENVGS_CTR_SEG_FIRST_ROW 28         /* + segment: first row of the segment's claim */
+#define ENVGS_CTR_BATCH_FETCH 32           /* + ENVGS_CTR_BATCH_FETCH_STRIDE * segment: the segment's batch-fetch counters */
+#define ENVGS_CTR_BATCH_FETCH_STRIDE 8
+#define ENVGS_CTR_SPARSE_FILED 64          /* hits filed in sparse_hits (= slots of it handed out) */
+#define ENVGS_CTR_BATCH_ENTRIES 65         /* (batch, surfel) entries left to the batch kernel of the record backward */
+#define ENVGS_CTR_SPARSE_SKIPPED 66        /* sparse_hits entries the most recent envgs_trace_backward had to skip (zeroed by every backward;
+                                              always 0 unless the list is corrupt) */
+#ifdef __cplusplus
+static_assert(ENVGS_CTR_TOTALS + 2 * ENVGS_TOT_COUNT <= ENVGS_CTR_STACK_OVERFLOWS && ENVGS_CTR_ROW_CLAIM < ENVGS_CTR_LONG_QUEUE &&
+              ENVGS_CTR_LONG_QUEUE + ENVGS_TRACE_MAX_SEG <= ENVGS_CTR_SEG_FIRST_ROW &&
+              ENVGS_CTR_SEG_FIRST_ROW + ENVGS_TRACE_MAX_SEG <= ENVGS_CTR_BATCH_FETCH &&
+              ENVGS_CTR_BATCH_FETCH + ENVGS_CTR_BATCH_FETCH_STRIDE * ENVGS_TRACE_MAX_SEG <= ENVGS_CTR_SPARSE_FILED &&
+              ENVGS_CTR_SPARSE_SKIPPED < ENVGS_TRACE_COUNTER_MIRROR && ENVGS_TRACE_COUNTER_MIRROR <= ENVGS_TRACE_COUNTER_WORDS,
+              "envgs_trace counter block: the segment-indexed ranges overlap a neighbour");
+#endif
+
+/*
  * Scratch of the list path (bounce-free tracing; all DEVICE pointers, caller-allocated).  HBM is used deliberately here
  * (288 GB per MI355X): per-ray hit lists make the backward traversal-free, per-(batch, surfel) gradient records grouped by surfel make
  * it atomic-free (the L2 atomic units retire ~0.15 T dword-atomics/s, which is what bounded a scatter-add backward).
@@ -107,8 +150,8 @@ typedef struct envgs_trace_lists {
      * batch_rows[b] = {first row, rows} of entries / pairs (compact_rows elements each).  Each forward segment CLAIMS its rows from a counter
      * shared by the call's segments once its hit counts are known (round 4; a fixed share per segment starved whichever held the busier rays);
      * rays that do not fit are handed to the K-buffer kernels like rays whose list overflowed
-     * (hit_cnt := cap + 1, counters[21] counts them) -- slower, never wrong.  The caller sizes compact_rows from the previous call's
-     * total of hits found (counters[8..9]). */
+     * (hit_cnt := cap + 1, ENVGS_CTR_RAYS_WITHOUT_ROWS counts them) -- slower, never wrong.  The caller sizes compact_rows from the previous call's
+     * total of hits found (ENVGS_TOT_FOUND). */
     uint64_t compact_rows;   /* rows of hit_state / elements of entries and pairs; 0 = (R, cap) layouts */
     uint32_t *row_off;       /* (R) by sorted slot */
     uint32_t *batch_rows;    /* (ceil(R/64), 2) */
@@ -126,9 +169,9 @@ typedef struct envgs_trace_lists {
                                 (sorted ray slot, list position, surfel id, record slot) -- one gradient record PER HIT -- instead of creating the entry,
                                 and envgs_trace_backward differentiates them one lane per hit (sparse_hits_bwd).  NULL / 0 = every entry takes the batch
                                 kernel; hits that find no room here do too (space is claimed only when it fits and never given back: a smaller
-                                later claim may still fit).  counters[64] = hits filed, counters[65] = entries left to the batch kernel; the backward
-                                checks every filed entry before it uses it and counts the ones it had to skip in counters[66] (zeroed by every
-                                envgs_trace_backward; always 0 unless the list is corrupt).
+                                later claim may still fit).  ENVGS_CTR_SPARSE_FILED counts the hits filed, ENVGS_CTR_BATCH_ENTRIES the entries left to the batch
+                                kernel; the backward checks every filed entry before it uses it and counts the ones it had to skip in
+                                ENVGS_CTR_SPARSE_SKIPPED.
                                 Worth it for INCOHERENT batches only (a filed hit costs ~12x a hit of a full entry: bounce rays off rough geometry,
                                 1-2 hits per entry: 59 -> 48 ms per step; the coherent benchmark views: +-0): envgs_amd.tracing passes the buffer when
                                 the tracer's previous call averaged fewer than 6 composited hits per entry */
@@ -203,17 +246,11 @@ ENVGS_API int envgs_bvh_quality(int32_t P, const float *nodes, float *out2, void
 
 /*
  * SurfelTracer.forward (optix_utils.py:188-201): trace R rays through the surfel set, composite front to back.
- * srec (P,16) is scratch written here (and read again by the backward).  counters: 96 uint32 of scratch; after the
- * forward, words [2..13] hold six uint64 totals: composited hits, (unused), K-buffer traversal rounds, hits found, wide nodes
- * visited by the packet traversal, leaf tests of the packet traversal (diagnostics that the roofline accounting of bench.py
- * needs: BASELINE.md section 4 "hits / node_visits are data dependent").  Word [20] counts the 64-ray batches whose packet
- * traversal ran out of its shared stack (their rays were handed to the K-buffer kernels, nothing is dropped); words [24..27]
- * are the per-segment queues of rays with more than 256 hits.
+ * srec (P,16) is scratch written here (and read again by the backward).  counters: the counter block (ENVGS_CTR_* above).
  * final_T (R): stage-0 transmittance, kept for the backward.
  * List path (lists != NULL, lists->cap > 0, max_trace_depth == 0): each ray's hits are collected in ONE unordered traversal,
  * sorted by (t, id) in LDS and walked front to back; the backward walks the same lists and never touches the BVH.  Rays with
  * more than `cap` hits, and all rays when lists == NULL or bounces are requested, use the K-nearest-buffer traversal instead.
- * After the call counters[1] holds the largest hit_cnt (so the caller can size `cap` for the next call).
  */
 ENVGS_API size_t envgs_trace_ray_sort_temp_bytes(int32_t num_rays);
 /* The coherence order envgs_trace_forward forms its 64-ray batches in, on its own (parity tests; a caller that wants to reuse one order

@@ -24,9 +24,9 @@ ts = tpkg.SurfelTracingSettings(image_height=H, image_width=W, tanfovx=cam.tanfo
 for _ in range(2):
     outs, saved = tracing.trace_forward(tracer.nodes, ro, rd, envp["means3D"], envp["shs"], None, None, envp["opacities"], envp["scales"], envp["rotations"], ts, False)
 torch.cuda.synchronize()
-keep = saved["keep"]; R = ro.shape[0]
-order = keep["ray_order"][R:2 * R].long()
-found = keep["hit_cnt"].float()[order]
+keep = saved.keep; R = ro.shape[0]
+order = keep.ray_order[R:2 * R].long()
+found = keep.hit_cnt.float()[order]
 nb = R // 64
 cost = found[:nb * 64].reshape(nb, 64).amax(1) * 0 + found[:nb * 64].reshape(nb, 64).sum(1)      # proxy: hits found per batch
 c = cost.cpu().numpy()

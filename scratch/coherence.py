@@ -25,10 +25,10 @@ ts = tpkg.SurfelTracingSettings(image_height=H, image_width=W, tanfovx=cam.tanfo
 for _ in range(2):
     outs, saved = tracing.trace_forward(tracer.nodes, ro, rd, envp["means3D"], envp["shs"], None, None, envp["opacities"], envp["scales"], envp["rotations"], ts, False)
 torch.cuda.synchronize()
-keep = saved["keep"]; R = ro.shape[0]; cap = saved["cap"]
-sid = keep["hit_lists"][:, :, 1].long()
-nu = keep["n_used"].long(); nf = keep["hit_cnt"].long().clamp(max=cap)
-order = keep["ray_order"][R:2 * R].long()
+keep = saved.keep; R = ro.shape[0]; cap = saved.cap
+sid = keep.hit_lists[:, :, 1].long()
+nu = keep.n_used.long(); nf = keep.hit_cnt.long().clamp(max=cap)
+order = keep.ray_order[R:2 * R].long()
 print("R", R, "cap", cap, "used/ray", nu.float().mean().item(), "found/ray", nf.float().mean().item())
 kk = torch.arange(cap, device=dev)[None]
 

@@ -9,7 +9,7 @@ n = [0, 0]
 orig = tracing.trace_backward
 def counting(saved, *a, **kw):
     r = orig(saved, *a, **kw)
-    n[0] += 1; n[1] += int(saved["lists"].defer_reduce & 1) if saved["lists"] is not None else 0
+    n[0] += 1; n[1] += int(saved.lists.defer_reduce & 1) if saved.lists is not None else 0
     return r
 tracing.trace_backward = counting
 rc = pytest.main(["tests/test_train_convergence.py", "-x", "-q", "-m", "gpu"])

@@ -24,9 +24,9 @@ ts = tpkg.SurfelTracingSettings(image_height=H, image_width=W, tanfovx=cam.tanfo
 for _ in range(2):
     outs, saved = tracing.trace_forward(tracer.nodes, ro, rd, envp["means3D"], envp["shs"], None, None, envp["opacities"], envp["scales"], envp["rotations"], ts, False)
 torch.cuda.synchronize()
-keep = saved["keep"]
-ne = keep["n_entries"].long()
-ent = keep["entries"]
+keep = saved.keep
+ne = keep.n_entries.long()
+ent = keep.entries
 nb = ne.shape[0]
 D = ne[:, 0]
 idx = torch.arange(ent.shape[1], device=dev)[None]
@@ -43,13 +43,13 @@ print("entries per batch: mean %.0f max %d" % (float(D.float().mean()), int(D.ma
 # dump a sample of batches for offline packing simulations
 import numpy as np
 sel = torch.arange(0, nb, 50, device=dev)
-cap = saved["cap"]
+cap = saved.cap
 out = dict(D=D[sel].cpu().numpy(), entries=[], pairs=[])
 for b in sel.tolist():
     d = int(D[b])
     out["entries"].append(ent[b, :d].cpu().numpy())
     tot = int((((ent[b, :d] >> 24) & 63) + 1).sum())
-    out["pairs"].append(keep["pairs"][b, :tot].cpu().numpy())
+    out["pairs"].append(keep.pairs[b, :tot].cpu().numpy())
 os.makedirs("gpurun_out", exist_ok=True)
 np.savez_compressed("gpurun_out/batches_sample.npz", D=out["D"], entries=np.concatenate(out["entries"]), pairs=np.concatenate(out["pairs"]))
 print("dumped", len(sel), "batches")

@@ -31,13 +31,13 @@ def hist(label, S, o, d, sff):
     for _ in range(3):
         outs, saved = tracing.trace_forward(nodes, o, d, S["means3D"], S["shs"], None, None, S["opacities"], S["scales"], S["rotations"], ts, sff, caps=caps)
         torch.cuda.synchronize()
-    keep = saved["keep"]
-    ne = keep["n_entries"].long()                       # (nbatch, 2): table entries, single (unmerged) entries
-    br = keep["batch_rows"].view(-1, 2).long()          # (nbatch, 2): first row, rows
+    keep = saved.keep
+    ne = keep.n_entries.long()                       # (nbatch, 2): table entries, single (unmerged) entries
+    br = keep.batch_rows.view(-1, 2).long()          # (nbatch, 2): first row, rows
     D = ne[:, 0]
     start = br[:, 0]
     idx = torch.repeat_interleave(start, D) + (torch.arange(int(D.sum()), device=dev) - torch.repeat_interleave(torch.cumsum(D, 0) - D, D))
-    ent = keep["entries"][idx]
+    ent = keep.entries[idx]
     cnt = ((ent >> 24) & 63) + 1
     nsing = int(ne[:, 1].sum())
     print("%s: batches %d table entries %d (+ %d unmerged singles) hits %d mean %.1f hits/entry" % (label, ne.shape[0], int(cnt.numel()), nsing, int(cnt.sum()) + nsing, float(cnt.float().mean())))

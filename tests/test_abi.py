@@ -52,6 +52,24 @@ def test_struct_layouts_match_headers():
     assert names == [n for n, _ in _lib.TraceLists._fields_]
 
 
+def test_counter_block_and_trace_debug_names_match_headers():
+    """The tracer's counter block (envgs_trace.h: ENVGS_TRACE_COUNTER_* / _MAX_SEG, ENVGS_CTR_*, ENVGS_TOT_*) and the ENVGS_DBG_TRACE bits
+    (envgs_raster.h) against their mirror in envgs_amd/_lib.py: the same names without the ENVGS_ prefix, the same values, none missing on either side."""
+    from envgs_amd import _lib
+    pat = r"^#define\s+ENVGS_((?:CTR|TOT|TRACE_COUNTER|TRACE_MAX_SEG|DBG_TRACE)\w*)\s+(\([\d\s|]+\)|\d+)"
+    hdr = {}
+    for h in ("envgs_trace.h", "envgs_raster.h"):
+        for name, val in re.findall(pat, open(os.path.join(ROOT, "include", h)).read(), re.M):
+            assert name not in hdr, name
+            hdr[name] = eval(val, {"__builtins__": {}})
+    assert len(hdr) == 31 and hdr["TRACE_COUNTER_WORDS"] == 96 and hdr["CTR_TOTALS"] + 2 * hdr["TOT_COUNT"] == hdr["CTR_STACK_OVERFLOWS"]
+    mirror = {n: getattr(_lib, n) for n in dir(_lib) if re.match(r"(CTR|TOT|TRACE_COUNTER|TRACE_MAX_SEG|DBG_TRACE)", n)}
+    assert sorted(mirror) == sorted(hdr)
+    for name, val in hdr.items():
+        assert type(mirror[name]) is int and mirror[name] == val, (name, val, mirror[name])
+    assert _lib.DBG_TRACE_RETIRED & (_lib.DBG_TRACE_NO_SORT | _lib.DBG_TRACE_SMALL_STACK | _lib.DBG_TRACE_PREPARE_INLINE) == 0
+
+
 def test_bad_arguments_are_rejected_before_any_gpu_work(lib):
     from envgs_amd import _lib
     n = ctypes.c_uint32(7)

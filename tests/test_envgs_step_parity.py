@@ -234,7 +234,7 @@ def test_step_with_deferred_env_surfel_gradients_and_activated_parameters():
             orig = tracing.trace_backward
             def counting(saved, *a, **kw):
                 r = orig(saved, *a, **kw)
-                n[0] += int(saved["lists"].defer_reduce & 1)
+                n[0] += int(saved.lists.defer_reduce & 1)
                 return r
             tracing.trace_backward = counting
             try:
@@ -343,7 +343,7 @@ def test_step_with_deferred_env_surfel_gradients_and_env_opacity_loss(variant):
             orig = tracing.trace_backward
             def counting(saved, *a, **kw):
                 r = orig(saved, *a, **kw)
-                n_def[0] += int(saved["lists"].defer_reduce & 1)
+                n_def[0] += int(saved.lists.defer_reduce & 1)
                 return r
             tracing.trace_backward = counting
             try:

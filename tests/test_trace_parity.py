@@ -1386,7 +1386,7 @@ class _CountDeferred:
         self.tracing, self.orig, self.n = tracing, tracing.trace_backward, 0
         def counting(saved, *a, **kw):
             r = self.orig(saved, *a, **kw)
-            self.n += int(saved["lists"] is not None and (saved["lists"].defer_reduce & 1))
+            self.n += int(saved.lists is not None and (saved.lists.defer_reduce & 1))
             return r
         tracing.trace_backward = counting
         return self
@@ -1477,7 +1477,7 @@ def test_trace_deferred_surfel_gradients_over_a_bounce_chain(force_cap, request)
         orig = tracing.trace_backward
         def counting(saved, *a, chain=None, **kw):
             r = orig(saved, *a, chain=chain, **kw)
-            calls.append((None if chain is None else chain[1], saved["lists"].defer_reduce, sorted(k for k in ("means3D", "shs", "others_precomp", "ray_o") if r[k] is not None)))
+            calls.append((None if chain is None else chain[1], saved.lists.defer_reduce, sorted(k for k in ("means3D", "shs", "others_precomp", "ray_o") if r[k] is not None)))
             return r
         tracing.trace_backward = counting
         try:
@@ -1724,7 +1724,7 @@ def test_trace_c_abi_refuses_a_lists_struct_with_a_missing_buffer():
     outs, saved = tracing.trace_forward(nodes, ro.to(dev), rd.to(dev), gd["means3D"], gd["shs"], None, gd["others"], gd["opacities"], gd["scales"],
                                         gd["rotations"], st, False)
     torch.cuda.synchronize()
-    assert saved["cap"] > 0 and saved["lists"] is not None
+    assert saved.cap > 0 and saved.lists is not None
     lib = _lib.load()
     p = _lib.ptr
     s = saved
@@ -1733,11 +1733,11 @@ def test_trace_c_abi_refuses_a_lists_struct_with_a_missing_buffer():
     o = [torch.empty(R, c, **f32) for c in (3, 1, 1, 3, 1, 2, 16)] + [torch.empty(300, 1, **f32), torch.empty(R, **f32)]
 
     def fwd(lists):
-        return lib.envgs_trace_forward(s["cfg"], p(s["nodes"]), p(s["ro"]), p(s["rd"]), p(s["means3D"]), p(s["scales"]), p(s["rotations"]), p(s["opacities"]),
-                                       p(s["shs"]), None, p(s["others"]), p(s["bg"]), p(s["srec"]), p(s["counters"]), *[p(t) for t in o], lists, None)
+        return lib.envgs_trace_forward(s.cfg, p(s.nodes), p(s.ro), p(s.rd), p(s.means3D), p(s.scales), p(s.rotations), p(s.opacities),
+                                       p(s.shs), None, p(s.others), p(s.bg), p(s.srec), p(s.counters), *[p(t) for t in o], lists, None)
 
-    full = clone(s["lists"])
-    full.hit_lists = s["keep"]["hit_lists"].data_ptr() if "hit_lists" in s["keep"] else None
+    full = clone(s.lists)
+    full.hit_lists = s.keep.hit_lists.data_ptr() if s.keep.hit_lists is not None else None
     if full.hit_lists is not None:
         assert fwd(full) == 0                                                   # the complete struct is accepted
         torch.cuda.synchronize()
@@ -1748,8 +1748,8 @@ def test_trace_c_abi_refuses_a_lists_struct_with_a_missing_buffer():
     grads = [torch.empty(300, c, **f32) for c in (16, 3, 3, 2, 4, 1)] + [torch.empty(300, 16, 3, **f32), None, torch.empty(300, 2, **f32),
                                                                           torch.empty(R, 3, **f32), torch.empty(R, 3, **f32)]
     for field in ("surf_off", "n_used"):
-        bad = clone(s["lists"]); setattr(bad, field, None)
-        rc = lib.envgs_trace_backward(s["cfg"], p(s["nodes"]), p(s["ro"]), p(s["rd"]), p(s["means3D"]), p(s["scales"]), p(s["rotations"]), p(s["opacities"]),
-                                      p(s["shs"]), None, p(s["others"]), p(s["bg"]), p(s["srec"]), p(s["counters"]), p(s["rgb"]), p(s["dpt"]), p(s["acc"]),
-                                      p(s["norm"]), p(s["aux"]), p(s["final_T"]), p(gup), None, None, None, None, *[p(t) for t in grads], bad, None)
+        bad = clone(s.lists); setattr(bad, field, None)
+        rc = lib.envgs_trace_backward(s.cfg, p(s.nodes), p(s.ro), p(s.rd), p(s.means3D), p(s.scales), p(s.rotations), p(s.opacities),
+                                      p(s.shs), None, p(s.others), p(s.bg), p(s.srec), p(s.counters), p(s.rgb), p(s.dpt), p(s.acc),
+                                      p(s.norm), p(s.aux), p(s.final_T), p(gup), None, None, None, None, *[p(t) for t in grads], bad, None)
         assert rc == -1, field
