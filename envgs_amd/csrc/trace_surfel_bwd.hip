@@ -25,6 +25,20 @@ static_assert(BS_GROUP <= 16, "stage() assigns four lanes per entry");
 #define ENVGS_BSB_KO 0          // measurement builds only (scratch/ab_bsb.sh): 1 = no dothers, 2 = no aux-plane fetch, 4 = no plane-1 fetch, 8 = no plane-0 fetch -- results wrong by construction
 #endif
 
+// The workgroup is ONE wavefront: its LDS operations execute in program order, so what a hand-over through LDS needs is that the compiler keeps
+// the accesses in that order (a wavefront-scope fence) and an LDS-only wait -- not __syncthreads(), whose vmcnt(0) drains every global load in
+// flight (the staged loads of the next group, the state prefetch).
+#define ENVGS_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); ENVGS_LDS_FENCE(); } while (0)
+#ifndef ENVGS_BSB_TIMING
+#define ENVGS_BSB_TIMING 0      // measurement builds only (scratch/bsb_stage_split.py): 1 = wavefront cycles of the batch prologue / epilogue, stage(), the entry bodies and the
+#endif                          // group-top sync, added by the BACKWARD to the totals the forward's collection uses (ENVGS_TOT_ROUNDS, _COOP_EXPAND, _COOP_WALK, _COOP_WAIT)
+#if ENVGS_BSB_TIMING
+#define ENVGS_BSB_LAP(bucket) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_readcyclecounter(); \
+                                   bucket += t_ - cyc_last; cyc_last = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
+#else
+#define ENVGS_BSB_LAP(bucket) do { } while (0)
+#endif
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int BT_PITCH = 96;  // words per row of the reduction tile: 64 rays + the skew of 2 words per row (<= 30), never wrapped
 constexpr int RECW = 64;      // floats per (batch, surfel) gradient record: 48 SH (or 3 colour) + 15 geometry + pad
@@ -41,13 +55,14 @@ batch_surfel_bwd(const TraceArgs A)
     __shared__ float4 sdat[2][BS_GROUP][16];               // per entry: surfel record (4 x 16 B) + SH block (12 x 16 B)
     __shared__ unsigned long long sdesc[2][BS_GROUP];      // sid | (hits-1) << 24 ; record index << 32
     __shared__ unsigned short kmat[2][BS_GROUP][64];       // per entry and ray: list position of the hit + 1, 0 = the ray did not blend it
-    __shared__ unsigned spb[2][BS_GROUP];                  // per entry: index of its first pair
-    __shared__ unsigned scn[2][BS_GROUP];                  // per entry: hits
     __shared__ float btile[16][BT_PITCH];                  // B operand of the reduction MFMAs: 16 words per ray, skewed (see below)
     __shared__ float2 sox[2][BS_GROUP];                    // per entry: the surfel's two `others` values (generic form only)
     const int lane = threadIdx.x;
     const int nb = (A.D + 1) * (A.D + 1);
     const int nbatch = (A.R + 63) >> 6;
+#if ENVGS_BSB_TIMING
+    unsigned long long cyc_pro = 0, cyc_stage = 0, cyc_entry = 0, cyc_sync = 0, cyc_last = __builtin_readcyclecounter();
+#endif
     // which batch a dispatch slot takes: the forward's longest-first order (one workgroup per batch: the loop runs once), or the slot itself
     for (int slot = blockIdx.x; slot < nbatch; slot += gridDim.x) {
         const int batch = A.bwd_order ? (int)A.bwd_order[slot] : slot;
@@ -80,10 +95,10 @@ batch_surfel_bwd(const TraceArgs A)
         }
         // A operand of the reduction MFMAs, constant for the batch: lane l holds basis_{l & 15} of ray 4s + (l >> 4)
         float Areg[16];
-        __syncthreads();
+        ENVGS_WAVE_SYNC();
 #pragma unroll
         for (int k = 0; k < 16; k++) btile[k][lane + 2 * k] = (valid && k < nb) ? basis[k] : (k == 0 ? kC0 : 0.f);
-        __syncthreads();
+        ENVGS_WAVE_SYNC();
 #pragma unroll
         for (int sI = 0; sI < 16; sI++) Areg[sI] = btile[lane & 15][4 * sI + (lane >> 4) + 2 * (lane & 15)];
         // ... and of the COLOUR MFMAs (the other orientation: rows = rays): Acol[4 b + s] of lane l = basis_{4 s + (l >> 4)} of ray 16 b + (l & 15).
@@ -94,7 +109,7 @@ batch_surfel_bwd(const TraceArgs A)
             const int k = 4 * (q & 3) + (lane >> 4);
             Acol[q] = btile[k][16 * (q >> 2) + (lane & 15) + 2 * k];
         }
-        __syncthreads();
+        ENVGS_WAVE_SYNC();
         // dL/d(SH basis) of the rays, accumulated on the matrix cores in the MFMA output layout: SkM[b][i] of lane l = (ray 16 b + 4 (l >> 4) + i,
         // basis l & 15); handed to the rays through LDS at the end of the batch
         f32x4 SkM[4];
@@ -109,18 +124,57 @@ batch_surfel_bwd(const TraceArgs A)
         const unsigned *prs = A.pairs + rstart;
         const int D = A.n_entries[2 * batch], NE = D + A.n_entries[2 * batch + 1];
         unsigned poff = 0u;                                  // pairs of the table entries staged so far
-        // Stage one group of entries, a whole group ahead of its use: 4 lanes per entry fetch the surfel record and SH block, then the
-        // group's (lane, k) pairs (one contiguous run) are scattered into kmat -- so the main loop touches no global memory except
-        // each ray's per-hit state.
+        // this lane's entry descriptor of group g (four lanes per entry; 0 beyond the batch's entries): table entries from the bottom of the
+        // batch's region, the singles filed from its top
+        auto fetch_desc = [&](const int g) -> unsigned long long {
+            const int e = g * BS_GROUP + (lane >> 2);
+            const bool ok = (lane >> 2) < BS_GROUP && e < NE;
+            // unconditional (idle lanes read the buffer's first word): a load under a branch meets the branch's other arm in a full vmcnt(0)
+            const unsigned long long *p = ok ? ent + (e < D ? (size_t)e : region - 1 - (size_t)(e - D)) : A.entries;
+            const unsigned long long d = *p;
+            return ok ? d : 0ull;
+        };
+        unsigned long long dnext = fetch_desc(0);            // the descriptor stage() uses next: always one call ahead of it
+        // Stage one group of entries, a whole group ahead of its use: 4 lanes per entry fetch the surfel record and SH block, and the
+        // group's (lane, k) pairs are scattered into kmat -- so the main loop touches no global memory except each ray's per-hit state.
+        // Every global load of a call is issued before the first is waited for: ONE round trip per group (round 8; eleven until then: the
+        // descriptor, the record, the SH block, the slot words and one per 64 pairs, each waited for before the next was issued -- a third of
+        // the wavefront's cycles, profiles/r08_ab_bsb_stage.txt).
         auto stage = [&](int g, int buf) {
             const int el = lane >> 2, part = lane & 3;
             const int e = g * BS_GROUP + el;
             const bool elv = el < BS_GROUP;
-            unsigned long long d = 0ull;
+            const unsigned long long d = dnext;              // loaded by the previous call (or ahead of the first): nothing here waits for it
+            dnext = fetch_desc(g + 1);
+            if (lane * 32 < BS_GROUP * 128) {   // clear kmat[buf]: 128 B per entry, 32 B per lane
+                uint4 *km = reinterpret_cast<uint4 *>(&kmat[buf][0][0]);
+                km[lane * 2] = make_uint4(0u, 0u, 0u, 0u); km[lane * 2 + 1] = make_uint4(0u, 0u, 0u, 0u);
+            }
+            // The group's pairs, one load per entry (its run of `hits` pairs, lane = pair), all issued before anything is waited for.  The hit
+            // counts and with them every entry's first pair come from the descriptors by readlane: scalars, no hand-over through LDS.
+            const unsigned hits = (elv && e < NE) ? (unsigned)((d >> 24) & 63ull) + 1u : 0u;
+            unsigned pr[BS_GROUP];
+            unsigned tab_before = 0u;                        // hits of the group's TABLE entries before entry q (singles live elsewhere)
+#pragma unroll
+            for (int q = 0; q < BS_GROUP; q++) {
+                const unsigned cq = (unsigned)__builtin_amdgcn_readlane((int)hits, 4 * q);
+                const int eq = g * BS_GROUP + q;
+                const unsigned first = eq < D ? poff + tab_before : (unsigned)(region - 1 - (size_t)(eq - D));
+                if (eq < D) tab_before += cq;
+                pr[q] = *((unsigned)lane < cq ? prs + first + lane : A.pairs);      // unconditional (idle lanes read the buffer's first word): no branch, no wait
+            }
+            poff += tab_before;
+            // (the loads stay HERE: without the fence the compiler sinks each one to its use behind the record stores below -- a second round trip)
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_sched_barrier(0);
             if (elv && e < NE) {
-                d = e < D ? ent[e] : ent[region - 1 - (size_t)(e - D)];
                 const int sid = (int)(d & 0xFFFFFFull);
-                sdat[buf][el][part] = A.srec[(size_t)sid * 4 + part];
+                // the record and the entry's record-slot words are loaded BEFORE the SH block and stored after it: one round trip for the three
+                // (all four lanes of an entry load the slot words: a load under `part == 0` would be waited for where the branch ends)
+                const size_t ci = (size_t)sid * NCOPY + copy;
+                const float4 r4 = A.srec[(size_t)sid * 4 + part];
+                const unsigned s_off = A.surf_off[ci], s_cnt = A.surf_cnt[ci];
+                float2 s_ox = make_float2(0.f, 0.f);
+                if constexpr (OTH) s_ox = reinterpret_cast<const float2 *>(A.others)[sid];
                 if (A.M == 16 && A.f16) {
                     // fp16 storage: this lane's 12 coefficients are 24 B = three 8 B loads, each converted into one staged float4
                     const uint2 *s2 = reinterpret_cast<const uint2 *>(reinterpret_cast<const __half *>(A.shs) + (size_t)sid * 48);
@@ -161,48 +215,28 @@ batch_surfel_bwd(const TraceArgs A)
                         sdat[buf][el][4 + part * 3 + q] = make_float4(v[0], v[1], v[2], v[3]);
                     }
                 }
+                sdat[buf][el][part] = r4;
                 if (part == 0) {
-                    const size_t ci = (size_t)sid * NCOPY + copy;
-                    const unsigned rec = A.surf_off[ci] - A.surf_cnt[ci] + (unsigned)(d >> 32);
+                    const unsigned rec = s_off - s_cnt + (unsigned)(d >> 32);
                     sdesc[buf][el] = (d & 0x3FFFFFFFull) | ((unsigned long long)rec << 32);
-                    if constexpr (OTH) sox[buf][el] = reinterpret_cast<const float2 *>(A.others)[sid];
+                    if constexpr (OTH) sox[buf][el] = s_ox;
                 }
             }
-            if (part == 0 && elv) scn[buf][el] = e < NE ? (unsigned)((d >> 24) & 63ull) + 1u : 0u;
-            if (lane * 32 < BS_GROUP * 128) {   // clear kmat[buf]: 128 B per entry, 32 B per lane
-                uint4 *km = reinterpret_cast<uint4 *>(&kmat[buf][0][0]);
-                km[lane * 2] = make_uint4(0u, 0u, 0u, 0u); km[lane * 2 + 1] = make_uint4(0u, 0u, 0u, 0u);
-            }
-            __syncthreads();
-            // prefix of the hit counts (every lane reads the 16 counts as broadcasts) and each entry's first pair
-            unsigned pref[BS_GROUP + 1];
-            pref[0] = 0u;
 #pragma unroll
-            for (int q = 0; q < BS_GROUP; q++) pref[q + 1] = pref[q] + scn[buf][q];
-            unsigned tab_before = 0u;                        // hits of the group's TABLE entries before entry q (singles live elsewhere)
-#pragma unroll
-            for (int q = 0; q < BS_GROUP; q++) {
-                const int eq = g * BS_GROUP + q;
-                if (lane == q) spb[buf][q] = eq < D ? poff + tab_before : (unsigned)(region - 1 - (size_t)(eq - D));
-                if (eq < D) tab_before += scn[buf][q];
-            }
-            __syncthreads();
-            const unsigned total = pref[BS_GROUP];
-            for (unsigned q = lane; q < total; q += 64) {
-                int eli = 0;
-#pragma unroll
-                for (int t = 1; t < BS_GROUP; t++) eli += q >= pref[t] ? 1 : 0;
-                const unsigned pr = prs[spb[buf][eli] + (q - pref[eli])];
-                kmat[buf][eli][pr >> 16] = (unsigned short)((pr & 0xFFFFu) + 1u);
-            }
-            poff += tab_before;
+            for (int q = 0; q < BS_GROUP; q++)               // (after the clear above: one wavefront's LDS writes land in program order)
+                if ((unsigned)lane < (unsigned)__builtin_amdgcn_readlane((int)hits, 4 * q)) kmat[buf][q][pr[q] >> 16] = (unsigned short)((pr[q] & 0xFFFFu) + 1u);
         };
-        __syncthreads();
+        ENVGS_WAVE_SYNC();
+        ENVGS_BSB_LAP(cyc_pro);
         stage(0, 0);
+        ENVGS_BSB_LAP(cyc_stage);
         for (int g = 0; g * BS_GROUP < NE; g++) {
             const int buf = g & 1;
-            __syncthreads();                                   // group g staged; group g-1 fully consumed
+            ENVGS_BSB_LAP(cyc_entry);
+            ENVGS_WAVE_SYNC();                                 // group g staged; group g-1 fully consumed
+            ENVGS_BSB_LAP(cyc_sync);
             if ((g + 1) * BS_GROUP < NE) stage(g + 1, buf ^ 1);
+            ENVGS_BSB_LAP(cyc_stage);
             const int ne = min(BS_GROUP, NE - g * BS_GROUP);
             // software pipeline over the entries: the per-hit state of entry el+1 is in flight while entry el is evaluated
             int k1 = valid ? (int)kmat[buf][0][lane] : 0;
@@ -395,12 +429,13 @@ batch_surfel_bwd(const TraceArgs A)
                 entry.template operator()<4>(el + 4);
             }
         }
-        __syncthreads();
+        ENVGS_BSB_LAP(cyc_entry);
+        ENVGS_WAVE_SYNC();
 #pragma unroll
         for (int rb = 0; rb < 4; rb++)
 #pragma unroll
             for (int i = 0; i < 4; i++) btile[lane & 15][16 * rb + 4 * (lane >> 4) + i] = SkM[rb][i];
-        __syncthreads();
+        ENVGS_WAVE_SYNC();
         if (valid) {
             BwdRay B;
             bwd_load_ray(A, r, B);
@@ -411,7 +446,15 @@ batch_surfel_bwd(const TraceArgs A)
             for (int k = 0; k < 16; k++) acc.Sk[k] = btile[k][lane];
             bwd_store_ray(A, r, B, acc);
         }
+        ENVGS_BSB_LAP(cyc_pro);
     }
+#if ENVGS_BSB_TIMING
+    if (lane == 0) {
+        unsigned long long *tot = reinterpret_cast<unsigned long long *>(A.counter + ENVGS_CTR_TOTALS);
+        atomicAdd(tot + ENVGS_TOT_ROUNDS, cyc_pro); atomicAdd(tot + ENVGS_TOT_COOP_EXPAND, cyc_stage);
+        atomicAdd(tot + ENVGS_TOT_COOP_WALK, cyc_entry); atomicAdd(tot + ENVGS_TOT_COOP_WAIT, cyc_sync);
+    }
+#endif
 }
 
 template __global__ void __attribute__((amdgpu_waves_per_eu(ENVGS_BSB_WAVES, ENVGS_BSB_WAVES))) __launch_bounds__(64) batch_surfel_bwd<false, false>(const TraceArgs A);
