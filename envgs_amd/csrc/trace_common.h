@@ -50,6 +50,7 @@ __device__ __forceinline__ SurfHit hit_surfel(const float4 s0, const float4 s1, 
                                               const float dy, const float dz)
 {
     SurfHit h;
+    float qx, qy, qz;
     {
         // t is the SORT KEY of the per-ray hit lists (index work: bit-exact against the oracle, like the rasterizer's depth keys): fixed
         // evaluation order, no FMA contraction, IEEE division.  The normal in the surfel record is built the same way (make_surfel_records).
@@ -57,8 +58,11 @@ __device__ __forceinline__ SurfHit hit_surfel(const float4 s0, const float4 s1, 
         h.denom = s3.x * dx + s3.y * dy + s3.z * dz;
         const float num = s3.x * (s0.x - ox) + s3.y * (s0.y - oy) + s3.z * (s0.z - oz);
         h.t = num / h.denom;
+        // The hit point relative to the centre, in the oracle's order as well: o + t d - mu cancels |o| ~ |t d| down to a few sigma, so a contracted
+        // fma(t, d, o) and the plain product differ by an ulp of |t d|, and u, v by that over the scale -- 1e-3 of alpha on a needle (s ~ 2e-4) seen
+        // from 4 units away, on either side of the 1e-4 the outputs are compared at.
+        qx = ox + h.t * dx - s0.x; qy = oy + h.t * dy - s0.y; qz = oz + h.t * dz - s0.z;
     }
-    const float qx = ox + h.t * dx - s0.x, qy = oy + h.t * dy - s0.y, qz = oz + h.t * dz - s0.z;
     h.u = s1.x * qx + s1.y * qy + s1.z * qz;
     h.v = s2.x * qx + s2.y * qy + s2.z * qz;
     h.G = __expf(-0.5f * (h.u * h.u + h.v * h.v));
@@ -74,12 +78,13 @@ __device__ __forceinline__ SurfHit hit_surfel_at(const float4 s0, const float4 s
                                                  const float ox, const float oy, const float oz, const float dx, const float dy, const float dz)
 {
     SurfHit h;
+    float qx, qy, qz;
     {
 #pragma clang fp contract(off)
         h.denom = s3.x * dx + s3.y * dy + s3.z * dz;
+        h.t = t;
+        qx = ox + h.t * dx - s0.x; qy = oy + h.t * dy - s0.y; qz = oz + h.t * dz - s0.z;      // (as hit_surfel: no contraction)
     }
-    h.t = t;
-    const float qx = ox + h.t * dx - s0.x, qy = oy + h.t * dy - s0.y, qz = oz + h.t * dz - s0.z;
     h.u = s1.x * qx + s1.y * qy + s1.z * qz;
     h.v = s2.x * qx + s2.y * qy + s2.z * qz;
     h.G = __expf(-0.5f * (h.u * h.u + h.v * h.v));

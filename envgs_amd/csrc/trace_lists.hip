@@ -100,7 +100,11 @@ static __device__ void surfel_record(const int i, const float mod, const float *
     const float r = q0 * inv, x = q1 * inv, y = q2 * inv, z = q3 * inv;
     const float su = scales[2 * i] * mod, sv = scales[2 * i + 1] * mod;
     float4 *o = reinterpret_cast<float4 *>(srec + (size_t)i * SREC);
-    o[0] = make_float4(means[3 * i], means[3 * i + 1], means[3 * i + 2], opac[i]);
+    // A NaN opacity is culled here, like a negative one is by the alpha threshold: left in the record it would pass the hit test's clamp
+    // `a < 0.99 ? a : 0.99` as alpha = 0.99 (the comparison is false for NaN) on every ray that reaches the surfel -- over a tree without
+    // opacities its whole quad, over a tightened one (trace_bvh.hip collapses its leaf) the rays through its centre.
+    const float op = opac[i];
+    o[0] = make_float4(means[3 * i], means[3 * i + 1], means[3 * i + 2], op == op ? op : 0.f);
     o[1] = make_float4((1.f - 2.f * (y * y + z * z)) / su, (2.f * (x * y + r * z)) / su, (2.f * (x * z - r * y)) / su, su);
     o[2] = make_float4((2.f * (x * y - r * z)) / sv, (1.f - 2.f * (x * x + z * z)) / sv, (2.f * (y * z + r * x)) / sv, sv);
     o[3] = make_float4(2.f * (x * z + r * y), 2.f * (y * z - r * x), 1.f - 2.f * (x * x + y * y), 0.f);

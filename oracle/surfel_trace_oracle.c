@@ -75,7 +75,7 @@ static void make_surfel(const trc_cfg *cfg, int i, const float *means, const flo
     s->n[0] = 2.f * (x * z + r * y); s->n[1] = 2.f * (y * z - r * x); s->n[2] = 1.f - 2.f * (x * x + y * y);
     s->mu[0] = means[3 * i]; s->mu[1] = means[3 * i + 1]; s->mu[2] = means[3 * i + 2];
     s->su = scales[2 * i] * cfg->scale_modifier; s->sv = scales[2 * i + 1] * cfg->scale_modifier;
-    s->opa = opac[i];
+    s->opa = opac[i] == opac[i] ? opac[i] : 0.f;      /* a NaN opacity is culled (it would pass the clamp below as alpha = 0.99) */
 }
 
 typedef struct { float t, u, v, G, alpha, denom; } rhit_t;
@@ -377,7 +377,7 @@ static void make_surfel64(const trc_cfg *cfg, int i, const float *means, const f
     s->n[0] = 2. * (x * z + r * y); s->n[1] = 2. * (y * z - r * x); s->n[2] = 1. - 2. * (x * x + y * y);
     s->mu[0] = means[3 * i]; s->mu[1] = means[3 * i + 1]; s->mu[2] = means[3 * i + 2];
     s->su = (double)scales[2 * i] * (double)cfg->scale_modifier; s->sv = (double)scales[2 * i + 1] * (double)cfg->scale_modifier;
-    s->opa = opac[i];
+    s->opa = opac[i] == opac[i] ? opac[i] : 0.f;
 }
 
 /* the double shadow of one ray / surfel pair from the raw parameters (tf, uf, vf, af: the float values, kept where the double ray is parallel to the plane) */
