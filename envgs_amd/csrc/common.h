@@ -46,6 +46,9 @@ template <int CTRL, int ROW_MASK = 0xf, int BANK_MASK = 0xf, bool BOUND = true>
 __device__ __forceinline__ float dpp_mov(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, BANK_MASK, BOUND));
 }
+template <int CTRL> __device__ __forceinline__ int dpp_mov_i32(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
+// The sum over a quad in every one of its lanes: lane ^ 1, then lane ^ 2 (quad_perm).
+__device__ __forceinline__ float quad_sum(float v) { v += dpp_mov<0xB1>(v); v += dpp_mov<0x4E>(v); return v; }
 
 // Sum over the 64 lanes; the result is returned wave-uniform (in an SGPR via readlane 63).
 __device__ __forceinline__ float wave_sum(float v) {
@@ -112,6 +115,18 @@ __device__ __forceinline__ float wave_scan_mul(float v) {
 }
 __device__ __forceinline__ float wave_bcast(float v, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); }
 
+// The integer inclusive scan, same lane patterns as wave_scan_add (the binning / scan / sort kernels of raster_bin.hip, mesh.hip, mesh_clean.hip).
+template <int CTRL, int ROW_MASK = 0xf>
+__device__ __forceinline__ uint32_t dpp_fill_u32(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);
+}
+__device__ __forceinline__ uint32_t wave_scan_add_u32(uint32_t v) {
+    v += dpp_fill_u32<0x111>(v); v += dpp_fill_u32<0x112>(v); v += dpp_fill_u32<0x114>(v); v += dpp_fill_u32<0x118>(v);
+    v += dpp_fill_u32<0x142, 0xa>(v);
+    v += dpp_fill_u32<0x143, 0xc>(v);
+    return v;
+}
+
 // Transpose-reduce of 4*N4 per-lane values over the wavefront in ~(2+1+1)*N4 + ... instructions instead of 7 per value:
 //   v_permlane32_swap pairs value i with value i+2*N4 (one add leaves i's 32 partial sums in the low half, the other's in the high half),
 //   v_permlane16_swap pairs again (each 16-lane row now owns ONE value), four DPP row rotations finish the row sums, and N4-1 selects
@@ -143,6 +158,22 @@ __device__ __forceinline__ float wave_transpose_reduce(const float (&g)[4 * N4],
 }
 
 __device__ __forceinline__ int lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+
+// Exclusive prefix of `v` over the workgroup's NW wavefronts (thread order), and the workgroup total.  s_w: NW words of LDS.
+template <int NW>
+__device__ __forceinline__ uint32_t block_exclusive_u32(uint32_t v, uint32_t *s_w, uint32_t &total)
+{
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
+    const uint32_t inc = wave_scan_add_u32(v);
+    if (lane == 63) s_w[wave] = inc;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (int k = 0; k < NW; k++) { const uint32_t t = s_w[k]; all += t; before += (k < wave) ? t : 0u; }
+    total = all;
+    __syncthreads();
+    return before + inc - v;
+}
 
 __device__ __forceinline__ void atomic_add_f32(float *p, float v) { unsafeAtomicAdd(p, v); }
 

@@ -10,14 +10,15 @@
 //                     consecutive 4-byte words of one source tensor (compact_gather's shape) and stores each word to the 0 .. 2 + 2N rows it
 //                     becomes; kept rows stay in order inside every segment, so the stores are contiguous runs as well
 //
-//   weight_select     the pruning tail (device_schedule="all"): exact order statistics of the average weight by a three-pass radix select --
-//                     supervisor.hip's depth_select with the ranks as arguments, the key computed from two arrays and the count below each
-//                     selected value kept; visibility_mask turns a cut and a count into `prune_visibility`'s keep mask (ties by index order,
-//                     ranked with a scan); oversize_plan is `prune_max_scene_and_screen`'s masks and counts in one launch
+//   weight_select     the pruning tail (device_schedule="all"): exact order statistics of the average weight by the three-pass radix select of
+//                     radix_select.h, the key computed from two arrays and the count below each selected value kept; visibility_mask turns a
+//                     cut and a count into `prune_visibility`'s keep mask (ties by index order, ranked with a scan); oversize_plan is
+//                     `prune_max_scene_and_screen`'s masks and counts in one launch
 //
 // Compiled with -ffp-contract=off (build.py): the decisions repeat torch's compare / divide bit for bit and the gradient norm is a fixed
 // left-to-right sum, whatever the compiler would like to fuse.
 #include "common.h"
+#include "radix_select.h"
 
 #include "../../include/envgs_densify.h"
 
@@ -43,9 +44,7 @@ densify_stats(const long long P, const float *__restrict__ grad, const uint8_t *
 }
 
 // ---- plan -------------------------------------------------------------------------------------------------------------------------------
-// floats as unsigned words of the same order (0 = "nothing yet": it decodes to a negative NaN, below every number)
-__device__ __forceinline__ uint32_t ordered(float f) { const uint32_t b = __float_as_uint(f); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
-__device__ __forceinline__ float unordered(uint32_t e) { return __uint_as_float((e & 0x80000000u) ? (e & 0x7fffffffu) : ~e); }
+// the weight maxima travel as raw float_key words (float_key.h; 0 = "nothing yet": it decodes to a negative NaN, below every number)
 
 __device__ __forceinline__ float stat_avg(float x, float d) { const float a = x / d; return a != a ? 0.0f : a; }        // IEEE division; NaN -> 0
 
@@ -76,8 +75,8 @@ grow_plan(const envgs_densify_plan_args a)
         a.scan[4 * P + i] = split ? 1u : 0u;                         // S1, S2: the staged split selection, pruned or not (sample order)
         a.scan[5 * P + i] = (clone && split) ? 1u : 0u;
         n_clone = clone ? 1u : 0u;
-        w_all = ordered(wa);
-        if (clone) { w_clone_max = ordered(wa); w_clone_min = ~ordered(wa); }
+        w_all = float_key(wa);
+        if (clone) { w_clone_max = float_key(wa); w_clone_min = ~float_key(wa); }
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
@@ -110,10 +109,10 @@ __global__ void grow_counters(const long long P, const uint32_t *__restrict__ sc
 // so the largest product belongs to the largest (wmax0 >= 0) or the smallest (wmax0 < 0) cloned weight.
 __device__ __forceinline__ void grow_wmax(const uint32_t *__restrict__ counters, float &w0, float &w1)
 {
-    w0 = unordered(counters[ENVGS_GROW_W_ALL]);
+    w0 = float_of_key(counters[ENVGS_GROW_W_ALL]);
     w1 = w0;
     if (counters[ENVGS_GROW_N_CLONE]) {
-        const float sel = w0 < 0.0f ? unordered(~counters[ENVGS_GROW_W_CLONE_MIN]) : unordered(counters[ENVGS_GROW_W_CLONE_MAX]);
+        const float sel = w0 < 0.0f ? float_of_key(~counters[ENVGS_GROW_W_CLONE_MIN]) : float_of_key(counters[ENVGS_GROW_W_CLONE_MAX]);
         w1 = fmaxf(w0, __fmul_rn(sel, w0));
     }
 }
@@ -158,6 +157,8 @@ struct GrowCommon {
 };
 
 // row `col` of build_rotation(q) (envgs_amd/synth.py) applied to the sample (sx, sy, 0)
+// (the rotation of glue.hip's surfel_quads, written out again on purpose: torch normalises with an IEEE division by the correctly rounded norm,
+// and this must match it)
 __device__ __forceinline__ float rotated_offset(const float *__restrict__ q4, const int col, const float sx, const float sy)
 {
     const float n = __fsqrt_rn(q4[0] * q4[0] + q4[1] * q4[1] + q4[2] * q4[2] + q4[3] * q4[3]);
@@ -228,103 +229,16 @@ grow_rewrite(const GrowBatch B, const GrowCommon C)
 }
 
 // ---- the pruning tail: order statistics of the average weight --------------------------------------------------------------------------
-// Three-pass radix select on the order-preserving uint32 image of the key, digits of 11 + 11 + 10 bits (supervisor.hip: depth_select_*).  Up to
-// two ranks share the passes: after pass 0 each has its own 11-bit prefix, passes 1 / 2 histogram only the keys under either prefix.  Integer
-// atomics only (LDS per workgroup, then one global add per non-empty bin).
-constexpr int WSEL_BINS0 = 2048, WSEL_BINS1 = 2048, WSEL_BINS2 = 1024;
-constexpr int WSEL_H0 = 0, WSEL_H1 = WSEL_H0 + WSEL_BINS0, WSEL_H2 = WSEL_H1 + 2 * WSEL_BINS1, WSEL_STATE = WSEL_H2 + 2 * WSEL_BINS2;   // uint32 offsets
-constexpr int WSEL_WORDS = WSEL_STATE + 4;          // state: prefix of either statistic, rank of either inside its prefix
-constexpr int WSEL_THREADS = 256;
-
+// radix_select.h over the key below.  The functor stays in this file: the key contains a division and this file is compiled with contraction
+// off.
 // get_xyz_weight_avg as an ordered word; -0 orders (and decodes) as +0
-__device__ __forceinline__ uint32_t weight_key(const float wa, const float dn)
-{
-    uint32_t b = __float_as_uint(stat_avg(wa, dn));
-    if (b == 0x80000000u) b = 0u;
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
+__device__ __forceinline__ uint32_t weight_key(const float wa, const float dn) { return float_key_canon(stat_avg(wa, dn)); }
 __device__ __forceinline__ uint32_t cut_key(const float cut) { return weight_key(cut, 1.0f); }        // (x / 1 = x: the key of a selected value)
 
-template <int PASS>
-__global__ void __launch_bounds__(WSEL_THREADS)
-weight_select_hist(const long long P, const float *__restrict__ wa, const float *__restrict__ dn, uint32_t *__restrict__ temp)
-{
-    constexpr int BINS = PASS == 2 ? WSEL_BINS2 : WSEL_BINS0, SETS = PASS == 0 ? 1 : 2;
-    __shared__ uint32_t h[SETS * BINS];
-    const int tid = threadIdx.x;
-    for (int b = tid; b < SETS * BINS; b += WSEL_THREADS) h[b] = 0u;
-    uint32_t p0 = 0u, p1 = 0u;
-    if (PASS > 0) { p0 = temp[WSEL_STATE]; p1 = temp[WSEL_STATE + 1]; }
-    __syncthreads();
-    for (long long i = (long long)blockIdx.x * WSEL_THREADS + tid; i < P; i += (long long)gridDim.x * WSEL_THREADS) {
-        const uint32_t k = weight_key(wa[i], dn[i]);
-        if (PASS == 0) {
-            atomicAdd(&h[k >> 21], 1u);
-        } else {
-            const uint32_t top = PASS == 1 ? (k >> 21) : (k >> 10), dig = PASS == 1 ? ((k >> 10) & 2047u) : (k & 1023u);
-            if (top == p0) atomicAdd(&h[dig], 1u);
-            if (top == p1) atomicAdd(&h[BINS + dig], 1u);
-        }
-    }
-    __syncthreads();
-    uint32_t *g = temp + (PASS == 0 ? WSEL_H0 : PASS == 1 ? WSEL_H1 : WSEL_H2);
-    for (int b = tid; b < SETS * BINS; b += WSEL_THREADS) {
-        const uint32_t v = h[b];
-        if (v) atomicAdd(&g[b], v);
-    }
-}
-
-// One workgroup: the bin that holds rank r of a histogram (the first bin whose inclusive prefix sum exceeds r), for either statistic.  The rank
-// left inside the last bin is the number of equal keys before the statistic, so what is below the selected value is the rank minus that.
-template <int PASS>
-__global__ void __launch_bounds__(WSEL_THREADS)
-weight_select_pick(const uint32_t rank0, const uint32_t rank1, const int n_ranks, uint32_t *__restrict__ temp, float *__restrict__ values,
-                   uint32_t *__restrict__ below)
-{
-    constexpr int BINS = PASS == 2 ? WSEL_BINS2 : WSEL_BINS0, PER = BINS / WSEL_THREADS;
-    __shared__ uint32_t sums[WSEL_THREADS];
-    const int tid = threadIdx.x;
-    uint32_t rank[2], prefix[2];
-    if (PASS == 0) { rank[0] = rank0; rank[1] = rank1; prefix[0] = prefix[1] = 0u; }
-    else { rank[0] = temp[WSEL_STATE + 2]; rank[1] = temp[WSEL_STATE + 3]; prefix[0] = temp[WSEL_STATE]; prefix[1] = temp[WSEL_STATE + 1]; }
-    __syncthreads();                                  // every lane holds the state before any lane replaces it
-    for (int which = 0; which < 2; which++) {
-        const uint32_t *hist = temp + (PASS == 0 ? WSEL_H0 : (PASS == 1 ? WSEL_H1 : WSEL_H2) + which * BINS);
-        uint32_t c[PER], s = 0u;
-#pragma unroll
-        for (int q = 0; q < PER; q++) { c[q] = hist[tid * PER + q]; s += c[q]; }
-        sums[tid] = s;
-        __syncthreads();
-        for (int off = 1; off < WSEL_THREADS; off <<= 1) {
-            const uint32_t v = tid >= off ? sums[tid - off] : 0u;
-            __syncthreads();
-            sums[tid] += v;
-            __syncthreads();
-        }
-        const uint32_t incl = sums[tid];
-        uint32_t run = incl - s;
-        const uint32_t r = rank[which];
-        if (r >= run && r < incl) {                   // true in exactly one lane (the total is the number of keys under the prefix, > r)
-            int bin = PER - 1;
-            bool found = false;
-#pragma unroll
-            for (int q = 0; q < PER; q++) {           // the first bin whose running total passes r; `run` ends as the count in the bins before it
-                if (!found) {
-                    if (r < run + c[q]) { bin = q; found = true; }
-                    else run += c[q];
-                }
-            }
-            const uint32_t digit = (uint32_t)(tid * PER + bin);
-            if (PASS == 0) { temp[WSEL_STATE + which] = digit; temp[WSEL_STATE + 2 + which] = r - run; }
-            if (PASS == 1) { temp[WSEL_STATE + which] = (prefix[which] << 11) | digit; temp[WSEL_STATE + 2 + which] = r - run; }
-            if (PASS == 2 && which < n_ranks) {
-                values[which] = unordered((prefix[which] << 10) | digit);
-                below[which] = (which ? rank1 : rank0) - (r - run);
-            }
-        }
-        __syncthreads();
-    }
-}
+struct WeightKeys {
+    const float *wa, *dn;
+    __device__ __forceinline__ uint32_t operator()(long long i) const { return weight_key(wa[i], dn[i]); }
+};
 
 // ---- prune_visibility's mask ------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
@@ -462,7 +376,7 @@ int envgs_densify_rewrite(const envgs_densify_rewrite_args *a, void *stream_)
     return (int)hipGetLastError();
 }
 
-size_t envgs_weight_select_temp_bytes(void) { return (size_t)WSEL_WORDS * sizeof(uint32_t); }
+size_t envgs_weight_select_temp_bytes(void) { return radix_select_temp_bytes(); }
 
 int envgs_weight_select(int64_t P, const float *wa, const float *dn, int32_t n_ranks, int64_t rank0, int64_t rank1, float *values, uint32_t *below,
                         void *temp, size_t temp_bytes, void *stream_)
@@ -471,19 +385,7 @@ int envgs_weight_select(int64_t P, const float *wa, const float *dn, int32_t n_r
     if (n_ranks == 1) rank1 = rank0;
     if (rank0 < 0 || rank0 >= P || rank1 < 0 || rank1 >= P) return ENVGS_ERR_BAD_ARG;
     if (temp_bytes < envgs_weight_select_temp_bytes()) return ENVGS_ERR_TEMP_TOO_SMALL;
-    hipStream_t s = (hipStream_t)stream_;
-    uint32_t *t = (uint32_t *)temp;
-    hipError_t e = hipMemsetAsync(t, 0, (size_t)WSEL_WORDS * sizeof(uint32_t), s);
-    if (e != hipSuccess) return (int)e;
-    const int blocks = (int)min((long long)512, (long long)((P + WSEL_THREADS * 8 - 1) / (WSEL_THREADS * 8)));
-    const uint32_t r0 = (uint32_t)rank0, r1 = (uint32_t)rank1;
-    hipLaunchKernelGGL(weight_select_hist<0>, dim3(blocks), dim3(WSEL_THREADS), 0, s, (long long)P, wa, dn, t);
-    hipLaunchKernelGGL(weight_select_pick<0>, dim3(1), dim3(WSEL_THREADS), 0, s, r0, r1, (int)n_ranks, t, values, below);
-    hipLaunchKernelGGL(weight_select_hist<1>, dim3(blocks), dim3(WSEL_THREADS), 0, s, (long long)P, wa, dn, t);
-    hipLaunchKernelGGL(weight_select_pick<1>, dim3(1), dim3(WSEL_THREADS), 0, s, r0, r1, (int)n_ranks, t, values, below);
-    hipLaunchKernelGGL(weight_select_hist<2>, dim3(blocks), dim3(WSEL_THREADS), 0, s, (long long)P, wa, dn, t);
-    hipLaunchKernelGGL(weight_select_pick<2>, dim3(1), dim3(WSEL_THREADS), 0, s, r0, r1, (int)n_ranks, t, values, below);
-    return (int)hipGetLastError();
+    return radix_select((long long)P, WeightKeys{wa, dn}, (uint32_t)rank0, (uint32_t)rank1, (int)n_ranks, values, below, temp, (hipStream_t)stream_);
 }
 
 static size_t tie_flag_bytes(int64_t P) { return ((size_t)(P > 0 ? P : 1) * sizeof(uint32_t) + 255) & ~(size_t)255; }

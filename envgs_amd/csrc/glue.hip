@@ -8,7 +8,7 @@
 
 namespace envgs {
 
-// (the SH basis, its gradient and the quad sum: sh_basis.h, shared with model.hip)
+// (the SH basis and its gradient: sh_basis.h, shared with model.hip; the quad sum: common.h)
 __global__ void __launch_bounds__(256)
 sh_colors_fwd(int P, int D, int M, int S, const float *__restrict__ means, const float *__restrict__ shs, const float *__restrict__ campos,
               const float *__restrict__ spec, const float *__restrict__ rough, float *__restrict__ colors, uint8_t *__restrict__ clamped)
@@ -19,7 +19,7 @@ sh_colors_fwd(int P, int D, int M, int S, const float *__restrict__ means, const
     const float dx = means[3 * i] - campos[0], dy = means[3 * i + 1] - campos[1], dz = means[3 * i + 2] - campos[2];
     const float il = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);
     float b[16];
-    basis16(D, dx * il, dy * il, dz * il, b);
+    basis16_exact(D, dx * il, dy * il, dz * il, b);
     const float *sh = shs + (size_t)i * M * 3;
     const int nb = (D + 1) * (D + 1);
     float r0 = 0.f, r1 = 0.f, r2 = 0.f;
@@ -48,8 +48,8 @@ sh_colors_bwd(int P, int D, int M, int S, const float *__restrict__ means, const
     const float sum2 = dx * dx + dy * dy + dz * dz, il = 1.0f / sqrtf(sum2);
     const float x = dx * il, y = dy * il, z = dz * il;
     float b[16], gx[16], gy[16], gz[16];
-    basis16(D, x, y, z, b);
-    basis16_grad(D, x, y, z, gx, gy, gz);
+    basis16_exact(D, x, y, z, b);
+    basis16_grad_exact(D, x, y, z, gx, gy, gz);
     const float *sh = shs + (size_t)i * M * 3;
     float *dsh = dshs + (size_t)i * M * 3;
     const int nb = (D + 1) * (D + 1);
@@ -87,7 +87,7 @@ sh_colors_fwd_q16(int P, int D, int S, const float *__restrict__ means, const fl
     float b[16];
 #pragma unroll
     for (int k = 0; k < 16; k++) b[k] = 0.f;
-    basis16(D, dx * il, dy * il, dz * il, b);
+    basis16_exact(D, dx * il, dy * il, dz * il, b);
     const int nb = (D + 1) * (D + 1);
     float bq[4];
 #pragma unroll
@@ -129,8 +129,8 @@ sh_colors_bwd_q16(int P, int D, int S, const float *__restrict__ means, const fl
     float b[16], gx[16], gy[16], gz[16];
 #pragma unroll
     for (int k = 0; k < 16; k++) b[k] = 0.f;
-    basis16(D, x, y, z, b);
-    basis16_grad(D, x, y, z, gx, gy, gz);
+    basis16_exact(D, x, y, z, b);
+    basis16_grad_exact(D, x, y, z, gx, gy, gz);
     const int nb = (D + 1) * (D + 1);
     float bq[4], gxq[4], gyq[4], gzq[4];
 #pragma unroll
@@ -195,8 +195,8 @@ sh_record_bwd_q16(int P, int D, const float *__restrict__ means, const float *__
     float b[16], gx[16], gy[16], gz[16];
 #pragma unroll
     for (int k = 0; k < 16; k++) b[k] = 0.f;
-    basis16(D, x, y, z, b);
-    basis16_grad(D, x, y, z, gx, gy, gz);
+    basis16_exact(D, x, y, z, b);
+    basis16_grad_exact(D, x, y, z, gx, gy, gz);
     const int nb = (D + 1) * (D + 1);
     float bq[4], gxq[4], gyq[4], gzq[4];
 #pragma unroll
@@ -497,7 +497,9 @@ surface_normal_bwd(int H, int W, float ratio, float fx, float fy, const float *_
     dallmap[6 * HW + p] = 0.f;
 }
 
-// get_disks (optix_utils.py:39-69): one lane per surfel, the four corners of its 3-sigma quad (+ the two triangles' indices)
+// get_disks (optix_utils.py:39-69): one lane per surfel, the four corners of its 3-sigma quad (+ the two triangles' indices).  model.hip's
+// surfel_inputs_fwd writes out the same expressions; they are not one function: this file lets the compiler contract, which product of
+// x * z - r * y gets fused depends on the surrounding code, and behind a shared inlined body this kernel fused the other one.
 __global__ void __launch_bounds__(256)
 surfel_quads(int P, const float *__restrict__ means, const float *__restrict__ scales, const float *__restrict__ rots, float *__restrict__ v,
              int32_t *__restrict__ f)

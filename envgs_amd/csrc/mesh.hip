@@ -14,7 +14,6 @@
 //
 // The 6 x 16 case table of the Kuhn split is GENERATED at compile time from geometry (make_mt_table), orientation included: nothing is typed in.
 #include "common.h"
-#include "mesh_scan.h"
 
 #include "../../include/envgs_mesh.h"
 
@@ -287,7 +286,7 @@ mesh_count(const int nx, const int ny, const int nz, const uint8_t *__restrict__
         mask[lin] = (uint8_t)m;
     }
     uint32_t total;
-    const uint32_t ex = mesh_block_exclusive((uint32_t)__popc(m) | (nt << 16), s_w, total);      // <= 1792 vertices, <= 3072 triangles per workgroup
+    const uint32_t ex = block_exclusive_u32<4>((uint32_t)__popc(m) | (nt << 16), s_w, total);      // <= 1792 vertices, <= 3072 triangles per workgroup
     if (lin < n) vlocal[lin] = (uint16_t)(ex & 0xffffu);
     if (threadIdx.x == 0) { cnt_v[blockIdx.x] = total & 0xffffu; cnt_t[blockIdx.x] = total >> 16; }
 }
@@ -351,7 +350,7 @@ mesh_emit(const envgs_tsdf_volume vol, const float level, const uint8_t *__restr
         }
     }
     uint32_t total;
-    uint32_t fi = mesh_block_exclusive(nt, s_w, total) + (blockIdx.x ? cnt_t[blockIdx.x - 1] : 0u);
+    uint32_t fi = block_exclusive_u32<4>(nt, s_w, total) + (blockIdx.x ? cnt_t[blockIdx.x - 1] : 0u);
     if (!nt) return;
     for (int t = 0; t < 6; t++) {
         const int cs = tet_case(cube, t);

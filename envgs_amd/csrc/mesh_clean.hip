@@ -28,7 +28,6 @@
 //   sel_emit_v / sel_emit_f   survivors written at scanned base + block rank, faces re-indexed through the vertices' ranks.  No atomics hand out
 //                    slots: relative order is part of the contract.
 #include "common.h"
-#include "mesh_scan.h"
 #include "mesh_unionfind.h"
 
 #include "../../include/envgs_mesh.h"
@@ -139,7 +138,7 @@ cc_vertex_count(const uint32_t V, const uint32_t *__restrict__ parent, const uin
     block_add_by_key(nv, ref, r, s_key, s_cnt);
     const bool owns = ref && r == v;
     uint32_t total;
-    const uint32_t ex = mesh_block_exclusive(owns ? 1u : 0u, s_w, total);
+    const uint32_t ex = block_exclusive_u32<4>(owns ? 1u : 0u, s_w, total);
     if (owns) rloc[v] = ex;
     if (threadIdx.x == 0) tot[blockIdx.x] = total;
 }
@@ -185,7 +184,7 @@ sel_mark(const uint32_t V, const uint32_t F, const int32_t *__restrict__ faces, 
     const bool on = f < F && keep[f] != 0 && face_in_range(faces, f, V, idx);
     if (on) { vused[idx[0]] = 1; vused[idx[1]] = 1; vused[idx[2]] = 1; }
     uint32_t total;
-    (void)mesh_block_exclusive(on ? 1u : 0u, s_w, total);
+    (void)block_exclusive_u32<4>(on ? 1u : 0u, s_w, total);
     if (threadIdx.x == 0) cnt_f[blockIdx.x] = total;
 }
 
@@ -196,7 +195,7 @@ sel_vscan(const uint32_t V, const uint8_t *__restrict__ vused, uint8_t *__restri
     const uint32_t v = blockIdx.x * 256u + threadIdx.x;
     const uint32_t u = (v < V && vused[v]) ? 1u : 0u;
     uint32_t total;
-    const uint32_t ex = mesh_block_exclusive(u, s_w, total);      // <= 255
+    const uint32_t ex = block_exclusive_u32<4>(u, s_w, total);      // <= 255
     if (v < V) vloc[v] = (uint8_t)ex;
     if (threadIdx.x == 0) cnt_v[blockIdx.x] = total;
 }
@@ -236,7 +235,7 @@ sel_emit_f(const uint32_t V, const uint32_t F, const int32_t *__restrict__ faces
     uint32_t idx[3];
     const bool on = f < F && keep[f] != 0 && face_in_range(faces, f, V, idx);
     uint32_t total;
-    const uint32_t n = mesh_block_exclusive(on ? 1u : 0u, s_w, total) + (blockIdx.x ? cnt_f[blockIdx.x - 1] : 0u);
+    const uint32_t n = block_exclusive_u32<4>(on ? 1u : 0u, s_w, total) + (blockIdx.x ? cnt_f[blockIdx.x - 1] : 0u);
     if (!on || n >= Fout) return;
 #pragma unroll
     for (int e = 0; e < 3; e++) {

@@ -102,7 +102,7 @@ surfel_inputs_fwd(const ModelArgs A)
         const float dx = A.xyz[3 * i] - A.campos[0], dy = A.xyz[3 * i + 1] - A.campos[1], dz = A.xyz[3 * i + 2] - A.campos[2];
         const float il = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);
         float b[16], bq[4];
-        basis16(D, dx * il, dy * il, dz * il, b);
+        basis16_exact(D, dx * il, dy * il, dz * il, b);
         quad_slice(b, q, nb, bq);
         float r[3] = {0.f, 0.f, 0.f};
 #pragma unroll
@@ -137,7 +137,8 @@ surfel_inputs_fwd(const ModelArgs A)
             if (A.others) A.others[2 * i + 1] = ro;
         }
     } else if (q == 3 && A.vertices) {
-        // get_disks, the arithmetic of surfel_quads (glue.hip) on exp(scaling) and the raw quaternion
+        // get_disks, the expressions of surfel_quads (glue.hip) on exp(scaling) and the raw quaternion; the two kernels contract differently (see
+        // there) and agree to rounding, not to the bit
         float r = A.rotation[4 * i], x1 = A.rotation[4 * i + 1], y = A.rotation[4 * i + 2], z = A.rotation[4 * i + 3];
         const float inv = 1.0f / sqrtf(r * r + x1 * x1 + y * y + z * z);
         r *= inv; x1 *= inv; y *= inv; z *= inv;
@@ -175,8 +176,8 @@ surfel_inputs_bwd(const ModelArgs A)
         sum2 = dx * dx + dy * dy + dz * dz; il = 1.0f / sqrtf(sum2);
         const float x = dx * il, y = dy * il, z = dz * il;
         float b[16], gx[16], gy[16], gz[16], bq[4], gxq[4], gyq[4], gzq[4];
-        basis16(D, x, y, z, b);
-        basis16_grad(D, x, y, z, gx, gy, gz);
+        basis16_exact(D, x, y, z, b);
+        basis16_grad_exact(D, x, y, z, gx, gy, gz);
         quad_slice(b, q, nb, bq); quad_slice(gx, q, nb, gxq); quad_slice(gy, q, nb, gyq); quad_slice(gz, q, nb, gzq);
         float xs[12];
 #pragma unroll

@@ -21,40 +21,13 @@
 //
 // The same machinery (histogram rows -> column scan -> bucket scan -> scatter -> per-bucket LDS sort) also orders the tracer's rays
 // (launch_ray_sort: buckets = top bits of the coherence key) and the LBVH's Morton keys (launch_key_sort), at the end of this file: the
-// library contains no other scan or sort.
+// library contains no other device-wide scan or sort.  (The wave / workgroup integer scan they are built on is common.h's wave_scan_add_u32 /
+// block_exclusive_u32, which mesh.hip and mesh_clean.hip use as well.)
 #include "common.h"
 #include "ray_key.h"
 #include "tile_sort.h"
 
 namespace envgs {
-
-// ---- wave64 integer scan / sum (DPP, same lane patterns as common.h's float versions) ------------
-template <int CTRL, int ROW_MASK = 0xf>
-__device__ __forceinline__ uint32_t dpp_fill_u32(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);
-}
-__device__ __forceinline__ uint32_t wave_scan_add_u32(uint32_t v) {
-    v += dpp_fill_u32<0x111>(v); v += dpp_fill_u32<0x112>(v); v += dpp_fill_u32<0x114>(v); v += dpp_fill_u32<0x118>(v);
-    v += dpp_fill_u32<0x142, 0xa>(v);
-    v += dpp_fill_u32<0x143, 0xc>(v);
-    return v;
-}
-
-// Exclusive prefix of `v` over the workgroup's NW wavefronts (thread order), and the workgroup total.  s_w: NW + 1 words of LDS.
-template <int NW>
-__device__ __forceinline__ uint32_t block_exclusive_u32(uint32_t v, uint32_t *s_w, uint32_t &total)
-{
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
-    const uint32_t inc = wave_scan_add_u32(v);
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (int k = 0; k < NW; k++) { const uint32_t t = s_w[k]; all += t; before += (k < wave) ? t : 0u; }
-    total = all;
-    __syncthreads();
-    return before + inc - v;
-}
 
 // ---- R2: inclusive prefix sum over n uint32 counters (two launches: block sums, then apply) ------
 constexpr int SCAN_ITEMS = 1024;                 // per workgroup: 256 lanes x 4 consecutive counters

@@ -9,16 +9,14 @@
 // Stands behind GaussianRasterizer.forward's preprocess stage; boundary: easyvolcap/utils/gaussian2d_utils.py:1089-1099,
 // transMat definition: :1050-1061, quaternion convention: :145-178, SH basis: easyvolcap/utils/sh_utils.py:642-727.
 #include "common.h"
+#include "sh_basis.h"
 
 namespace envgs {
 
-__device__ __constant__ float kC2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f,
-                                        -1.0925484305920792f, 0.5462742152960396f};
-__device__ __constant__ float kC3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f,
-                                        0.3731763325901154f, -0.4570457994644658f, 1.445305721320277f,
-                                        -0.5900435899266435f};
-constexpr float kC0 = 0.28209479177387814f;
-constexpr float kC1 = 0.4886025119029199f;
+// sh_basis.h's degree 2 / 3 tables again, with external linkage: a table with internal linkage is folded into literals, and this kernel (on the
+// timed path, bit-exact keys) keeps the instruction stream it has always had, its factors loaded from constant memory
+__device__ __constant__ float pC2[5] = {kC2xy, -kC2xy, kC2zz, -kC2xy, kC2xx};
+__device__ __constant__ float pC3[7] = {-kC3a, kC3b, -kC3c, kC3d, -kC3c, kC3e, -kC3a};
 
 __device__ __forceinline__ int clampi(int a, int lo, int hi) { return a < lo ? lo : (a > hi ? hi : a); }
 
@@ -63,6 +61,8 @@ project_surfels(int P, int D, int M, int f16, int C, int W, int H, float mod,
         const float qn = sqrtf(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
         const float inv = 1.0f / qn;
         const float r = q0 * inv, x = q1 * inv, y = q2 * inv, z = q3 * inv;
+        // raster_project_bwd.hip repeats these nine expressions and must round like them; behind a shared function this kernel compiled to another
+        // instruction stream (53 VGPRs for 50), so the text stays in both files
         float R[9];
         R[0] = 1.f - 2.f * (y * y + z * z); R[1] = 2.f * (x * y - r * z);       R[2] = 2.f * (x * z + r * y);
         R[3] = 2.f * (x * y + r * z);       R[4] = 1.f - 2.f * (x * x + z * z); R[5] = 2.f * (y * z - r * x);
@@ -122,15 +122,15 @@ project_surfels(int P, int D, int M, int f16, int C, int W, int H, float mod,
                 r = r - kC1 * y * sh[1 * 3 + c] + kC1 * z * sh[2 * 3 + c] - kC1 * x * sh[3 * 3 + c];
                 if (D > 1) {
                     const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-                    r = r + kC2[0] * xy * sh[4 * 3 + c] + kC2[1] * yz * sh[5 * 3 + c] +
-                        kC2[2] * (2.0f * zz - xx - yy) * sh[6 * 3 + c] + kC2[3] * xz * sh[7 * 3 + c] +
-                        kC2[4] * (xx - yy) * sh[8 * 3 + c];
+                    r = r + pC2[0] * xy * sh[4 * 3 + c] + pC2[1] * yz * sh[5 * 3 + c] +
+                        pC2[2] * (2.0f * zz - xx - yy) * sh[6 * 3 + c] + pC2[3] * xz * sh[7 * 3 + c] +
+                        pC2[4] * (xx - yy) * sh[8 * 3 + c];
                     if (D > 2) {
-                        r = r + kC3[0] * y * (3.0f * xx - yy) * sh[9 * 3 + c] + kC3[1] * xy * z * sh[10 * 3 + c] +
-                            kC3[2] * y * (4.0f * zz - xx - yy) * sh[11 * 3 + c] +
-                            kC3[3] * z * (2.0f * zz - 3.0f * xx - 3.0f * yy) * sh[12 * 3 + c] +
-                            kC3[4] * x * (4.0f * zz - xx - yy) * sh[13 * 3 + c] +
-                            kC3[5] * z * (xx - yy) * sh[14 * 3 + c] + kC3[6] * x * (xx - 3.0f * yy) * sh[15 * 3 + c];
+                        r = r + pC3[0] * y * (3.0f * xx - yy) * sh[9 * 3 + c] + pC3[1] * xy * z * sh[10 * 3 + c] +
+                            pC3[2] * y * (4.0f * zz - xx - yy) * sh[11 * 3 + c] +
+                            pC3[3] * z * (2.0f * zz - 3.0f * xx - 3.0f * yy) * sh[12 * 3 + c] +
+                            pC3[4] * x * (4.0f * zz - xx - yy) * sh[13 * 3 + c] +
+                            pC3[5] * z * (xx - yy) * sh[14 * 3 + c] + pC3[6] * x * (xx - 3.0f * yy) * sh[15 * 3 + c];
                     }
                 }
             }

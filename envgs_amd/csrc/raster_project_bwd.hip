@@ -6,16 +6,13 @@
 // Stands behind GaussianRasterizer.backward's preprocess stage (call site easyvolcap/utils/gaussian2d_utils.py:1089-1099;
 // the consumer of means2D.grad is :901-909).  Restated in oracle/surfel_raster_oracle.c::orc_preprocess_bwd.
 #include "common.h"
+#include "sh_basis.h"
 
 namespace envgs {
 
-constexpr float kC0 = 0.28209479177387814f;
-constexpr float kC1 = 0.4886025119029199f;
-__device__ __constant__ float bC2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f,
-                                        -1.0925484305920792f, 0.5462742152960396f};
-__device__ __constant__ float bC3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f,
-                                        0.3731763325901154f, -0.4570457994644658f, 1.445305721320277f,
-                                        -0.5900435899266435f};
+// sh_basis.h's degree 2 / 3 tables again, with external linkage (as raster_project.hip: loaded from constant memory, not folded into literals)
+__device__ __constant__ float bC2[5] = {kC2xy, -kC2xy, kC2zz, -kC2xy, kC2xx};
+__device__ __constant__ float bC3[7] = {-kC3a, kC3b, -kC3c, kC3d, -kC3c, kC3e, -kC3a};
 
 __global__ void __launch_bounds__(256)
 project_surfels_bwd(int P, int D, int M, int f16, int C, int W, int H, float mod, const float *__restrict__ geom,
@@ -80,7 +77,7 @@ project_surfels_bwd(int P, int D, int M, int f16, int C, int W, int H, float mod
             const float q0 = rotations[4 * i], q1 = rotations[4 * i + 1], q2 = rotations[4 * i + 2], q3 = rotations[4 * i + 3];
             const float inv = 1.0f / sqrtf(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
             const float r = q0 * inv, x = q1 * inv, y = q2 * inv, z = q3 * inv;
-            float R[9];
+            float R[9];             // the forward's R, raster_project.hip, expression for expression (see there)
             R[0] = 1.f - 2.f * (y * y + z * z); R[1] = 2.f * (x * y - r * z);       R[2] = 2.f * (x * z + r * y);
             R[3] = 2.f * (x * y + r * z);       R[4] = 1.f - 2.f * (x * x + z * z); R[5] = 2.f * (y * z - r * x);
             R[6] = 2.f * (x * z - r * y);       R[7] = 2.f * (y * z + r * x);       R[8] = 1.f - 2.f * (x * x + y * y);

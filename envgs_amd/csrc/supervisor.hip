@@ -1,103 +1,17 @@
 // supervisor.hip -- fused geometry regularisers of the EnvGS supervisor and the exact depth percentiles they scale with (include/envgs_supervisor.h).
 #include "common.h"
+#include "radix_select.h"
 
 #include "../../include/envgs_supervisor.h"
 
 namespace envgs {
 
-// ---- exact order statistics: three-pass radix select on the order-preserving uint32 image of the float ---------------------------------
-// digits: bits 31..21 (2048 bins), 20..10 (2048 bins), 9..0 (1024 bins).  The n-th smallest and the n-th largest value are selected in the same
-// passes: after pass 0 each has its own 11-bit prefix, and passes 1 / 2 histogram only the elements under either prefix.  Integer atomics only
-// (LDS per workgroup, then one global add per non-empty bin), so the result does not depend on the order of execution.
-constexpr int SEL_BINS0 = 2048, SEL_BINS1 = 2048, SEL_BINS2 = 1024;
-constexpr int SEL_H0 = 0, SEL_H1 = SEL_H0 + SEL_BINS0, SEL_H2 = SEL_H1 + 2 * SEL_BINS1, SEL_STATE = SEL_H2 + 2 * SEL_BINS2;   // uint32 offsets
-constexpr int SEL_WORDS = SEL_STATE + 4;            // state: prefix of the low / high statistic, rank of either inside its prefix
-constexpr int SEL_THREADS = 256;
-
-__device__ __forceinline__ uint32_t depth_key(float d)
-{
-    uint32_t u = __float_as_uint(d);
-    if (u == 0x80000000u) u = 0u;                    // -0 orders with +0
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_depth(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-template <int PASS>
-__global__ void __launch_bounds__(SEL_THREADS)
-depth_select_hist(const long long N, const float *__restrict__ depth, const long long stride, uint32_t *__restrict__ temp)
-{
-    constexpr int BINS = PASS == 2 ? SEL_BINS2 : SEL_BINS0, SETS = PASS == 0 ? 1 : 2;
-    __shared__ uint32_t h[SETS * BINS];
-    const int tid = threadIdx.x;
-    for (int b = tid; b < SETS * BINS; b += SEL_THREADS) h[b] = 0u;
-    uint32_t p_lo = 0u, p_hi = 0u;
-    if (PASS > 0) { p_lo = temp[SEL_STATE]; p_hi = temp[SEL_STATE + 1]; }
-    __syncthreads();
-    for (long long i = (long long)blockIdx.x * SEL_THREADS + tid; i < N; i += (long long)gridDim.x * SEL_THREADS) {
-        const uint32_t k = depth_key(depth[i * stride]);
-        if (PASS == 0) {
-            atomicAdd(&h[k >> 21], 1u);
-        } else {
-            const uint32_t top = PASS == 1 ? (k >> 21) : (k >> 10), dig = PASS == 1 ? ((k >> 10) & 2047u) : (k & 1023u);
-            if (top == p_lo) atomicAdd(&h[dig], 1u);
-            if (top == p_hi) atomicAdd(&h[BINS + dig], 1u);
-        }
-    }
-    __syncthreads();
-    uint32_t *g = temp + (PASS == 0 ? SEL_H0 : PASS == 1 ? SEL_H1 : SEL_H2);
-    for (int b = tid; b < SETS * BINS; b += SEL_THREADS) {
-        const uint32_t v = h[b];
-        if (v) atomicAdd(&g[b], v);
-    }
-}
-
-// One workgroup: the bin that holds rank r of a histogram (the first bin whose inclusive prefix sum exceeds r), for both statistics.
-template <int PASS>
-__global__ void __launch_bounds__(SEL_THREADS)
-depth_select_pick(const long long N, uint32_t *__restrict__ temp, float *__restrict__ near_far)
-{
-    constexpr int BINS = PASS == 2 ? SEL_BINS2 : SEL_BINS0, PER = BINS / SEL_THREADS;
-    __shared__ uint32_t sums[SEL_THREADS];
-    const int tid = threadIdx.x;
-    const uint32_t n = (uint32_t)(N / 100);
-    uint32_t rank[2], prefix[2];
-    if (PASS == 0) { rank[0] = n - 1u; rank[1] = (uint32_t)N - n; prefix[0] = prefix[1] = 0u; }
-    else { rank[0] = temp[SEL_STATE + 2]; rank[1] = temp[SEL_STATE + 3]; prefix[0] = temp[SEL_STATE]; prefix[1] = temp[SEL_STATE + 1]; }
-    __syncthreads();                                  // every lane holds the state before any lane replaces it
-    for (int which = 0; which < 2; which++) {
-        const uint32_t *hist = temp + (PASS == 0 ? SEL_H0 : (PASS == 1 ? SEL_H1 : SEL_H2) + which * BINS);
-        uint32_t c[PER], s = 0u;
-#pragma unroll
-        for (int q = 0; q < PER; q++) { c[q] = hist[tid * PER + q]; s += c[q]; }
-        sums[tid] = s;
-        __syncthreads();
-        for (int off = 1; off < SEL_THREADS; off <<= 1) {
-            const uint32_t v = tid >= off ? sums[tid - off] : 0u;
-            __syncthreads();
-            sums[tid] += v;
-            __syncthreads();
-        }
-        const uint32_t incl = sums[tid];
-        uint32_t run = incl - s;
-        const uint32_t r = rank[which];
-        if (r >= run && r < incl) {                   // true in exactly one lane (the total is the number of elements under the prefix, > r)
-            int bin = PER - 1;
-            bool found = false;
-#pragma unroll
-            for (int q = 0; q < PER; q++) {           // the first bin whose running total passes r; `run` ends as the count in the bins before it
-                if (!found) {
-                    if (r < run + c[q]) { bin = q; found = true; }
-                    else run += c[q];
-                }
-            }
-            const uint32_t digit = (uint32_t)(tid * PER + bin);
-            if (PASS == 0) { temp[SEL_STATE + which] = digit; temp[SEL_STATE + 2 + which] = r - run; }
-            if (PASS == 1) { temp[SEL_STATE + which] = (prefix[which] << 11) | digit; temp[SEL_STATE + 2 + which] = r - run; }
-            if (PASS == 2) near_far[which] = key_depth((prefix[which] << 10) | digit);
-        }
-        __syncthreads();
-    }
-}
+// ---- exact depth percentiles: radix_select.h over the canonical key of a strided depth read ------------------------------------------------
+struct DepthKeys {
+    const float *depth;
+    long long stride;
+    __device__ __forceinline__ uint32_t operator()(long long i) const { return float_key_canon(depth[i * stride]); }
+};
 
 // ---- the per-pixel terms ----------------------------------------------------------------------------------------------------------------
 constexpr int SUP_THREADS = 256;
@@ -294,24 +208,14 @@ using namespace envgs;
 
 extern "C" {
 
-size_t envgs_depth_percentiles_temp_bytes(void) { return (size_t)SEL_WORDS * sizeof(uint32_t); }
+size_t envgs_depth_percentiles_temp_bytes(void) { return radix_select_temp_bytes(); }
 
 int envgs_depth_percentiles(int64_t N, const float *depth, int64_t stride, float *near_far, void *temp, size_t temp_bytes, void *stream)
 {
     if (N < 100 || N >= (1ll << 31) || !depth || !near_far || !temp) return ENVGS_ERR_BAD_ARG;
     if (temp_bytes < envgs_depth_percentiles_temp_bytes()) return ENVGS_ERR_TEMP_TOO_SMALL;
-    hipStream_t s = (hipStream_t)stream;
-    uint32_t *t = (uint32_t *)temp;
-    hipError_t e = hipMemsetAsync(t, 0, (size_t)SEL_WORDS * sizeof(uint32_t), s);
-    if (e != hipSuccess) return (int)e;
-    const int blocks = (int)min((long long)512, (long long)((N + SEL_THREADS * 8 - 1) / (SEL_THREADS * 8)));
-    hipLaunchKernelGGL(depth_select_hist<0>, dim3(blocks), dim3(SEL_THREADS), 0, s, (long long)N, depth, (long long)stride, t);
-    hipLaunchKernelGGL(depth_select_pick<0>, dim3(1), dim3(SEL_THREADS), 0, s, (long long)N, t, near_far);
-    hipLaunchKernelGGL(depth_select_hist<1>, dim3(blocks), dim3(SEL_THREADS), 0, s, (long long)N, depth, (long long)stride, t);
-    hipLaunchKernelGGL(depth_select_pick<1>, dim3(1), dim3(SEL_THREADS), 0, s, (long long)N, t, near_far);
-    hipLaunchKernelGGL(depth_select_hist<2>, dim3(blocks), dim3(SEL_THREADS), 0, s, (long long)N, depth, (long long)stride, t);
-    hipLaunchKernelGGL(depth_select_pick<2>, dim3(1), dim3(SEL_THREADS), 0, s, (long long)N, t, near_far);
-    return (int)hipGetLastError();
+    const uint32_t n = (uint32_t)(N / 100);           // the n-th smallest and the n-th largest depth
+    return radix_select((long long)N, DepthKeys{depth, (long long)stride}, n - 1u, (uint32_t)N - n, 2, near_far, nullptr, temp, (hipStream_t)stream);
 }
 
 int64_t envgs_supervisor_partial_count(int64_t N, int64_t P)

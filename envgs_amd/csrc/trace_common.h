@@ -1,6 +1,7 @@
 // trace_common.h -- shared device code of the tracer (T2 forward, T3 backward; list path and K-buffer path): constants, the argument block,
-// the ray / surfel math, the SH basis, the per-ray backward helpers, the batch scheduling helpers, and the declarations of every kernel
-// (defined in trace_kbuffer.hip, trace_collect.hip, trace_lists.hip, trace_surfel_bwd.hip; launched from trace_api.hip).
+// the ray / surfel math, the per-ray backward helpers (the SH basis they evaluate is sh_basis.h's contracted pair), the batch scheduling
+// helpers, and the declarations of every kernel (defined in trace_kbuffer.hip, trace_collect.hip, trace_lists.hip, trace_surfel_bwd.hip;
+// launched from trace_api.hip).
 //
 // CDNA4 mapping of the K-buffer path: persistent wavefronts (one 64-lane workgroup each, grid = a few per CU) pull batches of 64 rays
 // from a global counter; one lane = one ray.  Traversal keeps the per-lane node stack in LDS ([level][lane], so a
@@ -18,6 +19,7 @@
 
 #include "common.h"
 #include "prof.h"
+#include "sh_basis.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -34,14 +36,6 @@ constexpr float UV_MAX = 3.0f;
 constexpr int MID = ENVGS_MID_CHANNELS;
 constexpr int SREC = ENVGS_SREC_STRIDE;
 constexpr int NODE = ENVGS_NODE_STRIDE;
-
-constexpr float kC0 = 0.28209479177387814f;
-constexpr float kC1 = 0.4886025119029199f;
-static __device__ __constant__ float tC2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f,
-                                        -1.0925484305920792f, 0.5462742152960396f};
-static __device__ __constant__ float tC3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f,
-                                        0.3731763325901154f, -0.4570457994644658f, 1.445305721320277f,
-                                        -0.5900435899266435f};
 
 struct SurfHit { float t, u, v, G, alpha, denom; bool ok; };
 
@@ -92,49 +86,6 @@ __device__ __forceinline__ SurfHit hit_surfel_at(const float4 s0, const float4 s
     h.alpha = a < ALPHA_CAP ? a : ALPHA_CAP;
     h.ok = true;
     return h;
-}
-
-__device__ __forceinline__ void sh_basis(int D, float x, float y, float z, float *b)
-{
-    b[0] = kC0;
-    if (D > 0) {
-        b[1] = -kC1 * y; b[2] = kC1 * z; b[3] = -kC1 * x;
-        if (D > 1) {
-            const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-            b[4] = tC2[0] * xy; b[5] = tC2[1] * yz; b[6] = tC2[2] * (2.0f * zz - xx - yy); b[7] = tC2[3] * xz; b[8] = tC2[4] * (xx - yy);
-            if (D > 2) {
-                b[9] = tC3[0] * y * (3.0f * xx - yy); b[10] = tC3[1] * xy * z; b[11] = tC3[2] * y * (4.0f * zz - xx - yy);
-                b[12] = tC3[3] * z * (2.0f * zz - 3.0f * xx - 3.0f * yy); b[13] = tC3[4] * x * (4.0f * zz - xx - yy);
-                b[14] = tC3[5] * z * (xx - yy); b[15] = tC3[6] * x * (xx - 3.0f * yy);
-            }
-        }
-    }
-}
-
-__device__ __forceinline__ void sh_basis_grad(int D, float x, float y, float z, float *gx, float *gy, float *gz)
-{
-#pragma unroll
-    for (int k = 0; k < 16; k++) { gx[k] = 0.f; gy[k] = 0.f; gz[k] = 0.f; }
-    if (D > 0) {
-        gy[1] = -kC1; gz[2] = kC1; gx[3] = -kC1;
-        if (D > 1) {
-            const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-            gx[4] = tC2[0] * y; gy[4] = tC2[0] * x;
-            gy[5] = tC2[1] * z; gz[5] = tC2[1] * y;
-            gx[6] = tC2[2] * -2.f * x; gy[6] = tC2[2] * -2.f * y; gz[6] = tC2[2] * 4.f * z;
-            gx[7] = tC2[3] * z; gz[7] = tC2[3] * x;
-            gx[8] = tC2[4] * 2.f * x; gy[8] = tC2[4] * -2.f * y;
-            if (D > 2) {
-                gx[9] = tC3[0] * 6.f * xy; gy[9] = tC3[0] * 3.f * (xx - yy);
-                gx[10] = tC3[1] * yz; gy[10] = tC3[1] * xz; gz[10] = tC3[1] * xy;
-                gx[11] = tC3[2] * -2.f * xy; gy[11] = tC3[2] * (4.f * zz - xx - 3.f * yy); gz[11] = tC3[2] * 8.f * yz;
-                gx[12] = tC3[3] * -6.f * xz; gy[12] = tC3[3] * -6.f * yz; gz[12] = tC3[3] * 3.f * (2.f * zz - xx - yy);
-                gx[13] = tC3[4] * (4.f * zz - 3.f * xx - yy); gy[13] = tC3[4] * -2.f * xy; gz[13] = tC3[4] * 8.f * xz;
-                gx[14] = tC3[5] * 2.f * xz; gy[14] = tC3[5] * -2.f * yz; gz[14] = tC3[5] * (xx - yy);
-                gx[15] = tC3[6] * 3.f * (xx - yy); gy[15] = tC3[6] * -6.f * xy;
-            }
-        }
-    }
 }
 
 // t_min of the first stage: camera rays skip the near 0.2 (the rasterizer's near plane), reflected rays start at 0, and the secondary rays of a
@@ -364,22 +315,22 @@ __device__ __forceinline__ int ray_index(int slot, int R, int rh, int rw)
 // SH basis k as (l0 + l1 x + l2 y + l3 z) * (q0 + q1 xx + q2 yy + q3 zz + q4 xy + q5 yz + q6 xz): lets lane j evaluate
 // "its" basis function (k = j / 3) of ANOTHER lane's ray direction during the cooperative gradient flush.
 static __device__ __constant__ float kShForm[16][11] = {
-    {1, 0, 0, 0, 0.28209479177387814f, 0, 0, 0, 0, 0, 0},
-    {0, 0, 1, 0, -0.4886025119029199f, 0, 0, 0, 0, 0, 0},
-    {0, 0, 0, 1, 0.4886025119029199f, 0, 0, 0, 0, 0, 0},
-    {0, 1, 0, 0, -0.4886025119029199f, 0, 0, 0, 0, 0, 0},
-    {1, 0, 0, 0, 0, 0, 0, 0, 1.0925484305920792f, 0, 0},
-    {1, 0, 0, 0, 0, 0, 0, 0, 0, -1.0925484305920792f, 0},
-    {1, 0, 0, 0, 0, -0.31539156525252005f, -0.31539156525252005f, 2.f * 0.31539156525252005f, 0, 0, 0},
-    {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, -1.0925484305920792f},
-    {1, 0, 0, 0, 0, 0.5462742152960396f, -0.5462742152960396f, 0, 0, 0, 0},
-    {0, 0, 1, 0, 0, 3.f * -0.5900435899266435f, 0.5900435899266435f, 0, 0, 0, 0},
-    {0, 0, 0, 1, 0, 0, 0, 0, 2.890611442640554f, 0, 0},
-    {0, 0, 1, 0, 0, 0.4570457994644658f, 0.4570457994644658f, 4.f * -0.4570457994644658f, 0, 0, 0},
-    {0, 0, 0, 1, 0, -3.f * 0.3731763325901154f, -3.f * 0.3731763325901154f, 2.f * 0.3731763325901154f, 0, 0, 0},
-    {0, 1, 0, 0, 0, 0.4570457994644658f, 0.4570457994644658f, 4.f * -0.4570457994644658f, 0, 0, 0},
-    {0, 0, 0, 1, 0, 1.445305721320277f, -1.445305721320277f, 0, 0, 0, 0},
-    {0, 1, 0, 0, 0, -0.5900435899266435f, 3.f * 0.5900435899266435f, 0, 0, 0, 0},
+    {1, 0, 0, 0, kC0, 0, 0, 0, 0, 0, 0},
+    {0, 0, 1, 0, -kC1, 0, 0, 0, 0, 0, 0},
+    {0, 0, 0, 1, kC1, 0, 0, 0, 0, 0, 0},
+    {0, 1, 0, 0, -kC1, 0, 0, 0, 0, 0, 0},
+    {1, 0, 0, 0, 0, 0, 0, 0, kC2xy, 0, 0},
+    {1, 0, 0, 0, 0, 0, 0, 0, 0, -kC2xy, 0},
+    {1, 0, 0, 0, 0, -kC2zz, -kC2zz, 2.f * kC2zz, 0, 0, 0},
+    {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, -kC2xy},
+    {1, 0, 0, 0, 0, kC2xx, -kC2xx, 0, 0, 0, 0},
+    {0, 0, 1, 0, 0, 3.f * -kC3a, kC3a, 0, 0, 0, 0},
+    {0, 0, 0, 1, 0, 0, 0, 0, kC3b, 0, 0},
+    {0, 0, 1, 0, 0, kC3c, kC3c, 4.f * -kC3c, 0, 0, 0},
+    {0, 0, 0, 1, 0, -3.f * kC3d, -3.f * kC3d, 2.f * kC3d, 0, 0, 0},
+    {0, 1, 0, 0, 0, kC3c, kC3c, 4.f * -kC3c, 0, 0, 0},
+    {0, 0, 0, 1, 0, kC3e, -kC3e, 0, 0, 0, 0},
+    {0, 1, 0, 0, 0, -kC3a, 3.f * kC3a, 0, 0, 0, 0},
 };
 
 constexpr int NFLD = 22;   // LDS hand-off fields per lane: sid, dc[3], geo[15], dir[3]
@@ -595,7 +546,7 @@ __device__ __forceinline__ void bwd_store_ray(const TraceArgs &A, int r, const B
     float dd0 = 0.f, dd1 = 0.f, dd2 = 0.f;
     if (A.M > 0) {
         float bgx[16], bgy[16], bgz[16];
-        sh_basis_grad(A.D, B.ux, B.uy, B.uz, bgx, bgy, bgz);
+        basis16_grad_contracted(A.D, B.ux, B.uy, B.uz, bgx, bgy, bgz);
 #pragma unroll
         for (int k = 0; k < 16; k++) { dd0 += bgx[k] * a.Sk[k]; dd1 += bgy[k] * a.Sk[k]; dd2 += bgz[k] * a.Sk[k]; }
     }

@@ -41,7 +41,7 @@ trace_fwd(const TraceArgs A, const int ray_h, const int ray_w)
             float basis[16];
             {
                 const float il = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);
-                sh_basis(A.D, dx * il, dy * il, dz * il, basis);
+                basis16_contracted(A.D, dx * il, dy * il, dz * il, basis);
             }
             bool done = !chain || A.P == 0;
             float tlo = tmin; int idlo = 0x7fffffff;
@@ -160,7 +160,7 @@ trace_bwd(const TraceArgs A, const int ray_h, const int ray_w)
         bwd_init_acc(acc);
         const float tmin = first_tmin(A.start_from_first);
         float basis[16];
-        sh_basis(A.D, B.ux, B.uy, B.uz, basis);
+        basis16_contracted(A.D, B.ux, B.uy, B.uz, basis);
         __syncthreads();                                  // previous batch's flush reads are done
         fld[19][lane] = B.ux; fld[20][lane] = B.uy; fld[21][lane] = B.uz;
         bool done = !valid || A.P == 0;

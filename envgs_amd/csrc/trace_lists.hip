@@ -91,6 +91,8 @@ static __device__ void permute_sh_word(const size_t i, int P, int nb, int f16, c
 }
 
 // ---- per-surfel record ----------------------------------------------------------------------------
+// (the rotation of glue.hip's surfel_quads, written out again on purpose: contraction is off here and the columns are divided by the scale,
+// because the record feeds the bit-exact sort key t)
 static __device__ void surfel_record(const int i, const float mod, const float *__restrict__ means, const float *__restrict__ scales,
                                      const float *__restrict__ rots, const float *__restrict__ opac, float *__restrict__ srec)
 {
@@ -134,9 +136,6 @@ forward_prepare(const ForwardPrepare F)
     permute_sh_word((size_t)b * 256 + threadIdx.x, F.P, F.nb, F.f16, F.shs, F.shp);
 }
 
-template <int CTRL> __device__ __forceinline__ float quad_f(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true)); }
-template <int CTRL> __device__ __forceinline__ int quad_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
-
 // SH colour of the 64 hits of a chunk, four lanes per surfel.  A lane-per-hit gather of the 192 B blocks is twelve 16 B loads whose 64 lanes
 // touch 64 different cache lines EACH -- the L1's tag pipeline (one line per cycle), not bandwidth or arithmetic, is what the kernel waits
 // for.  All 64 hits belong to ONE ray, so the SH basis is the same in every lane: lane q of a quad takes coefficients 4q .. 4q+3 of all four
@@ -149,9 +148,9 @@ __device__ __forceinline__ void quad_sh_color(const void *shp, const int sid, co
     float acc[4][3];
 #pragma unroll
     for (int s = 0; s < 4; s++) {
-        const int sid_s = s == 0 ? quad_i<0x00>(sid) : s == 1 ? quad_i<0x55>(sid) : s == 2 ? quad_i<0xAA>(sid) : quad_i<0xFF>(sid);
+        const int sid_s = s == 0 ? dpp_mov_i32<0x00>(sid) : s == 1 ? dpp_mov_i32<0x55>(sid) : s == 2 ? dpp_mov_i32<0xAA>(sid) : dpp_mov_i32<0xFF>(sid);
         const int us = use ? 1 : 0;
-        const int use_s = s == 0 ? quad_i<0x00>(us) : s == 1 ? quad_i<0x55>(us) : s == 2 ? quad_i<0xAA>(us) : quad_i<0xFF>(us);
+        const int use_s = s == 0 ? dpp_mov_i32<0x00>(us) : s == 1 ? dpp_mov_i32<0x55>(us) : s == 2 ? dpp_mov_i32<0xAA>(us) : dpp_mov_i32<0xFF>(us);
         acc[s][0] = acc[s][1] = acc[s][2] = 0.f;
         if (use_s) {
             float x[12];
@@ -180,12 +179,12 @@ __device__ __forceinline__ void quad_sh_color(const void *shp, const int sid, co
 #pragma unroll
         for (int c = 0; c < 3; c++) {
             const float keep = b0 ? acc[2 * h + 1][c] : acc[2 * h][c], send = b0 ? acc[2 * h][c] : acc[2 * h + 1][c];
-            t[h][c] = keep + quad_f<0xB1>(send);
+            t[h][c] = keep + dpp_mov<0xB1>(send);
         }
 #pragma unroll
     for (int c = 0; c < 3; c++) {
         const float keep = b1 ? t[1][c] : t[0][c], send = b1 ? t[0][c] : t[1][c];
-        r[c] = keep + quad_f<0x4E>(send) + 0.5f;
+        r[c] = keep + dpp_mov<0x4E>(send) + 0.5f;
         cl[c] = r[c] < 0.f;
         col[c] = cl[c] ? 0.f : r[c];
     }
@@ -219,7 +218,7 @@ __device__ __forceinline__ void sort_composite_ray(const TraceArgs &A, const int
         const float il = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);
 #pragma unroll
         for (int k = 0; k < 16; k++) basis[k] = 0.f;
-        sh_basis(A.D, dx * il, dy * il, dz * il, basis);
+        basis16_contracted(A.D, dx * il, dy * il, dz * il, basis);
     }
     float bk[4];                                        // this lane's four basis values of the quad-cooperative colour evaluation
     {

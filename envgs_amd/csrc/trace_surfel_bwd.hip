@@ -79,7 +79,7 @@ batch_surfel_bwd(const TraceArgs A)
             bwd_load_ray(A, rr, B);
 #pragma unroll
             for (int k = 0; k < 16; k++) basis[k] = 0.f;
-            sh_basis(A.D, B.ux, B.uy, B.uz, basis);
+            basis16_contracted(A.D, B.ux, B.uy, B.uz, basis);
             if (A.M == 0) basis[0] = kC0;
             if (!(B.il > 0.0f && B.il < 3.0e38f)) {
                 // a ray without a direction (zero, NaN or infinite d) composited nothing, but its basis is a row of the MFMA operand that sums the
@@ -495,7 +495,7 @@ sparse_hits_bwd(const TraceArgs A, const int rgbo)
         float basis[16];
 #pragma unroll
         for (int q = 0; q < 16; q++) basis[q] = 0.f;
-        sh_basis(A.D, B.ux, B.uy, B.uz, basis);
+        basis16_contracted(A.D, B.ux, B.uy, B.uz, basis);
         const size_t row = state_row0(A, slot, r) + (size_t)k;
         const float4 st0 = A.state[row];
         float4 st1 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -548,7 +548,7 @@ sparse_hits_bwd(const TraceArgs A, const int rgbo)
         float dd0 = 0.f, dd1 = 0.f, dd2 = 0.f;
         if (A.M > 0) {
             float bgx[16], bgy[16], bgz[16];
-            sh_basis_grad(A.D, B.ux, B.uy, B.uz, bgx, bgy, bgz);
+            basis16_grad_contracted(A.D, B.ux, B.uy, B.uz, bgx, bgy, bgz);
 #pragma unroll
             for (int q = 0; q < 16; q++) {
                 const float sk = q < nb ? shv[q * 3] * dc[0] + shv[q * 3 + 1] * dc[1] + shv[q * 3 + 2] * dc[2] : 0.f;

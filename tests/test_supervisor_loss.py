@@ -216,23 +216,25 @@ def _check_grads(got, ref, zero, noise=None, tol=1e-4, what=""):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("N", [7680, 640000, 100003])
+@pytest.mark.parametrize("N", [100, 199, 257, 7680, 640000, 100003])
 def test_device_percentiles_are_bit_exact(N):
+    """N = 100 is the smallest legal count (n = 1: the ranks are 0 and N - 1), 199 the largest with n = 1, 257 one workgroup plus one element; at
+    N = 100 an all-equal input too, whose two ranks share every prefix in all three passes of the select."""
     from envgs_amd import _lib
     lib = _lib.load()
     dev = torch.device("cuda", 0)
-    d = _tie_inputs(N, N + 1)
-    near, far = twin.percentiles(np.where(d == 0, np.float32(0.0), d))                  # (-0 counts as +0 on the device)
     st = _lib.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     tb = lib.envgs_depth_percentiles_temp_bytes()
-    for stride in (1, 3):                                                               # contiguous, and one channel of an interleaved map
-        buf = torch.full((N, stride), 1e30, device=dev)
-        buf[:, 0] = torch.from_numpy(d).to(dev)
-        nf = torch.full((2,), -1.0, device=dev)
-        temp = torch.full(((tb + 3) // 4,), 0x55555555, dtype=torch.int32, device=dev)    # dirty scratch: the call clears what it uses
-        assert lib.envgs_depth_percentiles(N, _lib.ptr(buf), stride, _lib.ptr(nf), _lib.ptr(temp), tb, st) == 0
-        got = nf.cpu().numpy()
-        assert got[0].tobytes() == np.float32(near).tobytes() and got[1].tobytes() == np.float32(far).tobytes(), (got, near, far)
+    for d in [_tie_inputs(N, N + 1)] + ([np.full(N, 1.5, np.float32)] if N == 100 else []):
+        near, far = twin.percentiles(np.where(d == 0, np.float32(0.0), d))              # (-0 counts as +0 on the device)
+        for stride in (1, 3):                                                           # contiguous, and one channel of an interleaved map
+            buf = torch.full((N, stride), 1e30, device=dev)
+            buf[:, 0] = torch.from_numpy(d).to(dev)
+            nf = torch.full((2,), -1.0, device=dev)
+            temp = torch.full(((tb + 3) // 4,), 0x55555555, dtype=torch.int32, device=dev)    # dirty scratch: the call clears what it uses
+            assert lib.envgs_depth_percentiles(N, _lib.ptr(buf), stride, _lib.ptr(nf), _lib.ptr(temp), tb, st) == 0
+            got = nf.cpu().numpy()
+            assert got[0].tobytes() == np.float32(near).tobytes() and got[1].tobytes() == np.float32(far).tobytes(), (got, near, far)
 
 
 @pytest.mark.gpu
