@@ -1,5 +1,6 @@
-"""Mesh extraction (include/envgs_mesh.h, csrc/mesh.hip, csrc/mesh_clean.hip): TSDF fusion of rendered depth into a dense volume, marching
-tetrahedra over it, and the clean-up of the mesh: connected components, order-preserving face selection, removal of small components.
+"""Mesh extraction (include/envgs_mesh.h, csrc/mesh.hip, csrc/mesh_clean.hip, csrc/mesh_simplify.hip): TSDF fusion of rendered depth into a dense
+volume, marching tetrahedra over it, the clean-up of the mesh (connected components, order-preserving face selection, removal of small
+components) and its simplification by vertex clustering.
 
 PARITY UNPINNED: the reference ships a fuser (easyvolcap/utils/tsdf_utils.py, fusion_utils.py, runners/visualizers/geometry_visualizer.py) that
 cannot run as it stands and leaves the marching step to libraries outside it, so the semantics are this project's ("Mesh extraction");
@@ -8,6 +9,7 @@ tests/mesh_oracle.py restates them independently.  There is no CPU path: CPU ten
     vol = TSDFVolume((-1, -1, -1), (1, 1, 1), voxel_size=0.01)
     fuse_surfels(vol, cameras, base, sh_degree=3)
     mesh = clean(vol.extract())                 # csrc/mesh_clean.hip: components(), select_faces() and the 2DGS rule built on them
+    mesh = simplify(clean(vol.extract()), 2 * voxel_size, origin=vol.origin)      # csrc/mesh_simplify.hip: vertex clustering on a uniform grid
     ckpt.save_mesh_ply("scene.ply", mesh.vertices, mesh.faces, mesh.colors)
 """
 import math
@@ -242,6 +244,103 @@ def clean(mesh, keep_largest=50, min_faces=50):
         threshold = torch.maximum(threshold, torch.sort(comp.faces, descending=True).values[int(keep_largest) - 1])
     kept = torch.cat([comp.faces >= threshold, torch.zeros(1, dtype=torch.bool, device=comp.faces.device)])      # row -1: the ignored faces
     return select_faces(mesh, kept[comp.face_label.long()])
+
+
+# ---- simplification (csrc/mesh_simplify.hip) --------------------------------------------------------------------------------------------------------
+def _grid_dims(extent, cell_size):
+    """Cells per axis that cover [0, extent]: floor(extent / cell_size) + 1, at least 1 (Python ints, so they may exceed any machine range)."""
+    dims = []
+    for e in extent:
+        r = e / cell_size if e > 0.0 else 0.0
+        dims.append(max(1, int(math.floor(r)) + 1) if math.isfinite(r) else 2 ** 62)
+    return dims
+
+
+def simplify_grid(vertices, cell_size, origin=None, dims=None):
+    """The clustering grid simplify() uses: -> (origin (ox, oy, oz), dims (nx, ny, nz)).  origin None: the per-axis minimum of the vertices whose
+    three coordinates are finite; dims[a] = floor((max[a] - origin[a]) / cell_size) + 1 over the same vertices, at least 1 (in double; positions
+    outside the grid are clamped into its border cells, so the rounding of this formula never loses a vertex).  One host sync: the read-back of
+    the six extrema (a second one when some vertex is not finite); none when origin and dims are both given (dims: (nx, ny, nz) cells, used as they are).  Raises ValueError for a grid of
+    2^31 cells or more, naming the smallest admissible cell_size."""
+    _need_gpu(vertices, "simplify")
+    cell_size = float(cell_size)
+    if not (cell_size > 0.0 and math.isfinite(cell_size)) or not float(torch.tensor(cell_size, dtype=torch.float32)) > 0.0:
+        raise ValueError("simplify: cell_size must be positive and finite")
+    if origin is not None:
+        origin = [float(o) for o in origin]
+        if len(origin) != 3 or not all(math.isfinite(o) for o in origin):
+            raise ValueError("simplify: origin must be three finite numbers")
+    if dims is not None:
+        dims = tuple(int(n) for n in dims)
+        if len(dims) != 3 or min(dims) < 1 or math.prod(dims) >= 2 ** 31:
+            raise ValueError("simplify: dims %s must be three counts of at least 1 whose product is below 2^31" % (dims,))
+        if origin is not None:
+            return tuple(origin), dims
+    lo, hi = [0.0] * 3, [0.0] * 3
+    if vertices.shape[0]:
+        # column by column: a full reduction of a strided column is 15 x faster here than amin(dim=0) over (V,3) (0.08 against 1.2 ms at V = 1.6 M)
+        columns = lambda t: [torch.aminmax(t[:, a]) for a in range(3)]
+        read = lambda lows, highs: torch.stack([torch.stack(lows), torch.stack(highs)]).tolist()
+        cols = columns(vertices)
+        ext = read([c.min for c in cols], [c.max for c in cols])
+        if not all(math.isfinite(x) for x in ext[0] + ext[1]):    # a NaN or an infinity somewhere: again, over the finite vertices alone
+            finite = torch.isfinite(vertices).all(dim=1, keepdim=True)
+            ext = read([c.min for c in columns(torch.where(finite, vertices, float("inf")))],
+                       [c.max for c in columns(torch.where(finite, vertices, float("-inf")))])
+        if all(math.isfinite(x) for x in ext[0] + ext[1]):        # else: no finite vertex, any grid will do
+            lo, hi = ext
+    if origin is not None:
+        lo = origin
+    if dims is not None:
+        return tuple(lo), dims
+    extent = [h - l for l, h in zip(lo, hi)]
+    cells = lambda c: math.prod(_grid_dims(extent, c))
+    if cells(cell_size) >= 2 ** 31:
+        bad, good = cell_size, 2.0 * cell_size
+        while cells(good) >= 2 ** 31:
+            bad, good = good, 2.0 * good
+        for _ in range(60):
+            mid = 0.5 * (bad + good)
+            bad, good = (bad, mid) if cells(mid) < 2 ** 31 else (mid, good)
+        raise ValueError("simplify: cell_size %g gives a grid of %d cells, 2^31 or more; the smallest admissible cell_size here is %r"
+                         % (cell_size, cells(cell_size), good))
+    return tuple(lo), tuple(_grid_dims(extent, cell_size))
+
+
+def simplify(mesh, cell_size, origin=None, return_index=False, dims=None):
+    """Vertex clustering on a uniform grid of edge cell_size (include/envgs_mesh.h, "simplification"): the vertices of one cell become one vertex,
+    at the integer-accumulated mean of their positions and colours (a cell of one vertex keeps it bit for bit); faces are re-mapped, and those
+    that collapse, name a vertex without a cell, or repeat an earlier face up to rotation are dropped.  Clusters are numbered by ascending cell
+    index and faces keep their order, so the result does not depend on scheduling or on the numbering of the input vertices: two runs give
+    identical bytes.  origin: the grid's corner (e.g. the volume's origin, cell_size = k voxel_size); None = the minimum of the finite vertices.
+    dims: the grid's (nx, ny, nz) cells; None = as many as cover the finite vertices.  Vertices outside the grid are clamped into its border cells.
+    -> Mesh, or (Mesh, vertex_cluster (V,) i32: the new index of each input vertex, -1 if none) with return_index.
+    Two host syncs: the read-back of the vertex extrema that size the grid (simplify_grid; none when origin and dims are both given), and the
+    read-back of (V', F') of the selection; the cluster count stays on the device."""
+    v, f, c = _mesh_tensors(mesh, "simplify")
+    (ox, oy, oz), (nx, ny, nz) = simplify_grid(v, cell_size, origin, dims)
+    lib = _lib.load()
+    dev = v.device
+    V, F = v.shape[0], f.shape[0]
+    R = min(V, nx * ny * nz)
+    tb = lib.envgs_mesh_simplify_temp_bytes(V, F, nx, ny, nz)
+    temp = torch.empty(tb, dtype=torch.uint8, device=dev)
+    cl_vertices = torch.empty(R, 3, dtype=torch.float32, device=dev)
+    cl_colors = torch.empty(R, 3, dtype=torch.float32, device=dev) if c is not None else None
+    cl_faces = torch.empty(F, 3, dtype=torch.int32, device=dev)
+    keep = torch.empty(F, dtype=torch.uint8, device=dev)
+    vertex_cluster = torch.empty(V, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    p = _lib.ptr
+    _lib.check(lib.envgs_mesh_simplify_cluster(V, F, p(v), p(c), p(f), ox, oy, oz, float(cell_size), nx, ny, nz, p(temp), tb, p(cl_vertices), p(cl_colors),
+                                               p(cl_faces), p(keep), p(vertex_cluster), p(count), _stream(dev)), "envgs_mesh_simplify_cluster")
+    clustered = Mesh(vertices=cl_vertices, faces=cl_faces, colors=cl_colors)
+    if not return_index:
+        return select_faces(clustered, keep)
+    out, index = select_faces(clustered, keep, return_index=True)
+    new_of_cluster = torch.full((R + 1,), -1, dtype=torch.int32, device=dev)                 # row -1: the vertices without a cluster
+    new_of_cluster[index.long()] = torch.arange(index.shape[0], dtype=torch.int32, device=dev)
+    return out, new_of_cluster[vertex_cluster.long()]
 
 
 def surface_depth(allmap, depth_ratio=0.0):

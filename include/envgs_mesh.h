@@ -121,6 +121,52 @@ ENVGS_API int envgs_mesh_select_emit(uint32_t V, uint32_t F, const float *vertic
                                      const void *temp, size_t temp_bytes, uint32_t Vout, uint32_t Fout, float *out_vertices, float *out_colors,
                                      int32_t *out_faces, int32_t *vertex_index, void *stream);
 
+/* ---- simplification of an indexed triangle mesh: vertex clustering on a uniform grid (csrc/mesh_simplify.hip) ---------------------------------
+ * The mesh is as for the clean-up (V and F below 2^31, any origin).  The grid has nx ny nz cells of edge `cell`, cell (i,j,k) covering
+ * [o + (i,j,k) cell, o + (i+1,j+1,k+1) cell); its linear index is i + nx (j + ny k), x fastest.  1 <= n* and nx ny nz < 2^31; cell > 0; cell and
+ * the origin are finite.  All float arithmetic is fp32, left to right, no FMA, IEEE division.
+ *
+ * 1. Cell of a vertex, per axis (x shown):  u = (x - ox) / cell;  fl = floor(u);
+ *      i = 0 unless fl >= 1;  i = nx - 1 if fl >= 2^31;  i = min((int)fl, nx - 1) otherwise      (decided on the float, before any conversion)
+ *    so positions outside the grid are clamped into its border cells.  A vertex with a coordinate that is not finite has NO cell (cluster -1).
+ * 2. The clusters are the occupied cells, numbered 0 .. C-1 by ascending linear cell index: independent of scheduling and of the numbering
+ *    of the input vertices.
+ * 3. Representative of a cluster of n members.  n = 1: the member's position and colour, bit for bit.  n > 1, per axis and member:
+ *      f = u - (float)i, then f = 0 unless f > 0, f = 1 if f > 1;   q = (uint32) floor(f * 1048576 + 0.5)                 (step 2^-20 of a cell)
+ *      S = sum of q over the members, in 64-bit integers;   q_mean = (2 S + n) / (2 n), integer division                  (the rounded mean)
+ *      coordinate = ox + ((float)i + (float)q_mean * 2^-20) * cell
+ *    and per colour channel and member:
+ *      c = 0 unless c > 0 (so NaN gives 0), c = 255 if c > 255;   q = (uint32) floor(c * 65536 + 0.5)                      (step 2^-16)
+ *      S, q_mean as above;   channel = (float)q_mean * 2^-16
+ *    Integer sums do not depend on the order of the adds: no float atomic is issued, two runs give identical bytes, and so do two numberings
+ *    of the same vertices.
+ * 4. Faces.  A face is mapped corner by corner to cluster numbers, in its corner order.  It is DROPPED if an index is outside [0, V) (such an
+ *    index is never dereferenced), if a corner has no cell, if two corners share a cluster, or if a face of lower index that is not dropped by
+ *    the preceding rules maps to the same oriented triple up to cyclic rotation: of equal faces the lowest index survives.  The reversed
+ *    triple is a different face.
+ * 5. The simplified mesh is envgs_mesh_select_count / _emit applied to the clustered mesh below: surviving faces in their old relative order,
+ *    re-indexed; the clusters a surviving face names, in ascending cluster order.  On the output of envgs_mesh_extract with the volume's
+ *    origin and cell = k voxel that is again a canonical order. */
+
+/* Scratch bytes of envgs_mesh_simplify_cluster: 1 B per cell, 60 B per row of min(V, cells), 4 B per face, 4 B per slot of the face table (the
+ * power of two >= 2 F), plus the per-workgroup totals.  0 if a count or the grid is out of range. */
+ENVGS_API size_t envgs_mesh_simplify_temp_bytes(uint32_t V, uint32_t F, int32_t nx, int32_t ny, int32_t nz);
+
+/* Steps 1-4.  No host sync: the outputs are sized by the bound R = min(V, nx ny nz) >= C.
+ *   cl_vertices (R,3), cl_colors (R,3; NULL: none, else `colors` must be given)   rows 0 .. C-1 are written: the representatives
+ *   cl_faces (F,3)     the mapped faces; a corner whose index is out of range or whose vertex has no cell is written as -1
+ *   keep (F)           1 = the face survives rule 4, 0 = dropped
+ *   vertex_cluster (V) cluster of each vertex, -1 = none
+ *   count              C, left on the device
+ * envgs_mesh_select_count / _emit on (R, F, cl_vertices, cl_colors, cl_faces, keep) then give the simplified mesh; rows C .. R-1 are never read.
+ * V = 0 or F = 0 are valid (no face survives).  Pointers to arrays of zero rows may be NULL; every other NULL, a count at or above 2^31, a grid
+ * out of range, a cell that is not positive and finite, an origin that is not finite and a `temp` that is not 16-byte aligned return
+ * ENVGS_ERR_BAD_ARG before any GPU work, a short `temp` ENVGS_ERR_TEMP_TOO_SMALL. */
+ENVGS_API int envgs_mesh_simplify_cluster(uint32_t V, uint32_t F, const float *vertices, const float *colors, const int32_t *faces, float ox, float oy,
+                                          float oz, float cell, int32_t nx, int32_t ny, int32_t nz, void *temp, size_t temp_bytes,
+                                          float *cl_vertices, float *cl_colors, int32_t *cl_faces, uint8_t *keep, int32_t *vertex_cluster,
+                                          uint32_t *count, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

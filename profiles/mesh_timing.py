@@ -6,6 +6,8 @@ Per volume size N^3 (bounds [-1,1]^3, colour on):
   extract     envgs_mesh_count + the read-back + envgs_mesh_extract of the fused volume
   components  envgs_mesh_components of that mesh + the read-back of C;  select: envgs_mesh_select_count + read-back + envgs_mesh_select_emit of its largest
               component;  clean: mesh.clean with its defaults (components, the rule in torch, select)
+  simplify    mesh.simplify of that mesh on cells of 2 voxels (envgs_mesh_simplify_cluster + the selection), with the grid given and with the grid
+              sized from a read-back;  torch: the same clustering in torch ops (torch_simplify below)
 The byte model of integrate: every voxel's tsdf, weight and rgb read once (20 B), and written back (20 B) in the 16 B granules where a voxel changed;
 of extract: 8 B read + 1 B written (classify), 1 B read + 3 B written (count), 4 B read (emit) per voxel, plus 24 B per vertex and 12 B per face
 written.  Fractions are of 6.3 TB/s (the achievable HBM rate, not the 8 TB/s peak).  Nothing is asserted; the table goes to DESIGN.md."""
@@ -57,6 +59,33 @@ def torch_integrate_view(vol, grid, depth, rgb, K, R, T):
     for c in range(3):
         vol.rgb[c].copy_(torch.where(ok, (vol.weight * vol.rgb[c] + rgb[c].reshape(-1)[pix]) / w1, vol.rgb[c]))
     vol.weight.copy_(torch.where(ok, torch.clamp_max(w1, vol.w_max), vol.weight))
+
+
+def torch_simplify(m, origin, cell, dims):
+    """The clustering of include/envgs_mesh.h ("simplification") in torch ops: float means (index_add_, so neither bit-defined nor reproducible),
+    the same face rules.  -> (vertices, faces, colors)"""
+    v, dev = m.vertices, m.vertices.device
+    o = torch.tensor(origin, dtype=torch.float32, device=dev)
+    n = torch.tensor(dims, dtype=torch.int64, device=dev)
+    ijk = torch.minimum(torch.floor((v - o) / cell).clamp_min(0).long(), n - 1)
+    lin = ijk[:, 0] + n[0] * (ijk[:, 1] + n[1] * ijk[:, 2])
+    _, cluster, members = torch.unique(lin, return_inverse=True, return_counts=True)
+    C = members.shape[0]
+    mean = lambda a: torch.zeros(C, 3, dtype=torch.float32, device=dev).index_add_(0, cluster, a) / members[:, None]
+    cl_v, cl_c = mean(v), mean(m.colors)
+    f = cluster[m.faces.long()]
+    ok = (f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 2] != f[:, 0])
+    first = f.argmin(dim=1, keepdim=True)
+    rot = torch.gather(f, 1, (first + torch.arange(3, device=dev)[None, :]) % 3)          # the smallest cluster first
+    key = (rot[:, 0] * C + rot[:, 1]) * C + rot[:, 2]
+    _, klass = torch.unique(key, return_inverse=True)
+    idx = torch.arange(f.shape[0], device=dev)
+    lowest = torch.full((int(klass.max()) + 1,), f.shape[0], dtype=torch.int64, device=dev).scatter_reduce_(0, klass[ok], idx[ok], "amin")
+    g = f[ok & (lowest[klass] == idx)]
+    used = torch.zeros(C, dtype=torch.bool, device=dev)
+    used[g.reshape(-1)] = True
+    new = torch.cumsum(used, 0) - 1
+    return cl_v[used], new[g].int(), cl_c[used]
 
 
 def median_ms(fn, reps):
@@ -127,7 +156,29 @@ def main():
         t_clean = median_ms(lambda: mesh.clean(m), args.reps)
         print("%-6d %-10s %10.3f %12s %10s   components + the rule in torch (sort of C counts, gather of F labels) + select: %.2fx the extraction"
               % (N, "clean", t_clean, "-", "-", t_clean / t_ext))
-        del vol, m, comp, s
+        # the simplification of that mesh (csrc/mesh_simplify.hip) on cells of 2 voxels from the volume's origin.  Model: 41 B per vertex (assign and
+        # accumulate read it twice, vertex_cluster written, colours read), 3 B per cell (cleared, scanned, rank written), 144 B per row of the sums
+        # (cleared, read, representative written), 79 B per face (map, enter with one probe, keep), 4 B per slot, plus the selection's own model
+        cell = 2 * vol.voxel_size
+        dims = tuple((d - 1) // 2 + 1 for d in vol.dims)
+        sm = mesh.simplify(m, cell, origin=vol.origin, dims=dims)
+        Vs, Fs = sm.vertices.shape[0], sm.faces.shape[0]
+        cells = dims[0] * dims[1] * dims[2]
+        rows = min(V, cells)
+        slots = 2
+        while slots < 2 * F:
+            slots *= 2
+        t_simp = median_ms(lambda: mesh.simplify(m, cell, origin=vol.origin, dims=dims), args.reps)
+        by = V * 41.0 + cells * 3.0 + rows * 144.0 + F * 79.0 + slots * 4.0 + F * 26.0 + rows * 4.0 + Vs * 48.0 + Fs * 15.0
+        print("%-6d %-10s %10.3f %12.1f %9.1f%%   cells of 2 voxels, grid given: V' %d F' %d; includes the (V', F') read-back and the output allocation"
+              % (N, "simplify", t_simp, by / 1e6, 100 * by / (t_simp * 1e-3) / ACHIEVABLE, Vs, Fs))
+        t_auto = median_ms(lambda: mesh.simplify(m, cell), args.reps)
+        print("%-6d %-10s %10.3f %12s %10s   the same with origin=None: the grid is sized from the read-back of the vertex extrema" % (N, "simplify*", t_auto, "-", "-"))
+        ts = torch_simplify(m, vol.origin, cell, dims)
+        t_ts = median_ms(lambda: torch_simplify(m, vol.origin, cell, dims), args.torch_reps)
+        print("%-6d %-10s %10.3f %12s %10s   the same clustering in torch (unique on cell keys, index_add_ means, unique on face keys): V' %d F' %d, %.1fx simplify"
+              % (N, "torch", t_ts, "-", "-", ts[0].shape[0], ts[1].shape[0], t_ts / t_simp))
+        del vol, m, comp, s, sm, ts
         torch.cuda.empty_cache()
 
 
