@@ -18,7 +18,13 @@ __device__ __forceinline__ void adam_one(float &p, const float g, float &m, floa
     m = (float)((double)(m * beta1) + (1.0 - (double)beta1) * (double)g);
     v = (float)((double)(v * beta2) + (1.0 - (double)beta2) * (double)g * (double)g);
     const float denom = sqrtf(v) / bc2_sqrt + eps;
-    p -= (m / denom) * step_size;
+    {
+        // the update is rounded to float BEFORE it leaves p, as in the reference's statement (oracle/adam_oracle.c); contracted into one fma,
+        // p' depends on bits of the product that no float update has, and a step from p != 0 is not `p - update` of the same step from p == 0
+#pragma clang fp contract(off)
+        const float update = (m / denom) * step_size;
+        p = p - update;
+    }
 }
 
 __global__ void __launch_bounds__(256)

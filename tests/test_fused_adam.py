@@ -72,6 +72,14 @@ def test_fused_adam_matches_oracle(sizes):
             np.testing.assert_allclose(got, ref[i][0], rtol=1e-5, atol=1e-7)                    # tolerance: powf / sqrt / div ulps
             np.testing.assert_allclose(st["exp_avg"].cpu().numpy(), ref[i][1], rtol=1e-6, atol=1e-9)
             np.testing.assert_allclose(st["exp_avg_sq"].cpu().numpy(), ref[i][2], rtol=1e-6, atol=1e-12)
+            # and without any atol: one step of the oracle from the KERNEL's own state before this step (so that an earlier last-bit difference
+            # is not carried along) gives moments within one float32 ulp -- one float multiply, double arithmetic, one rounding; only a fused
+            # instead of an unfused double multiply-add can move them, by one rounding
+            m0, v0 = ((before[i][1][k].cpu().numpy() if k in before[i][1] else np.zeros(sizes[i], np.float32)) for k in ("exp_avg", "exp_avg_sq"))
+            _, m1, v1 = oracle_adam(before[i][0].cpu().numpy(), ps[i].grad.cpu().numpy(), m0, v0, float(step), 0.9, 0.999, lrs[i], 1e-15)
+            for name, a, b in (("exp_avg", st["exp_avg"].cpu().numpy(), m1), ("exp_avg_sq", st["exp_avg_sq"].cpu().numpy(), v1)):
+                far = np.abs(a.astype(np.float64) - b.astype(np.float64)) > np.spacing(np.abs(b)).astype(np.float64)
+                assert not far.any(), "%s of tensor %d at step %d: %d elements beyond 1 ulp of the oracle" % (name, i, step, far.sum())
             zt = torch.from_numpy(zero).to(dev)                                                  # skipped elements: bit-exact, untouched
             assert torch.equal(p.detach()[zt], before[i][0][zt])
             if "exp_avg" in before[i][1]:
