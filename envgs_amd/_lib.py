@@ -197,6 +197,12 @@ SYMBOLS = {
     "envgs_mesh_select_emit": (c_int, [c_uint32, c_uint32] + [_P] * 4 + [_P, c_size_t, c_uint32, c_uint32] + [_P] * 4 + [_P]),
     "envgs_mesh_simplify_temp_bytes": (c_size_t, [c_uint32, c_uint32] + [ctypes.c_int32] * 3),
     "envgs_mesh_simplify_cluster": (c_int, [c_uint32, c_uint32, _P, _P, _P] + [ctypes.c_float] * 4 + [ctypes.c_int32] * 3 + [_P, c_size_t] + [_P] * 6 + [_P]),
+    "envgs_mesh_sample_temp_bytes": (c_size_t, [c_uint32, c_uint32]),
+    "envgs_mesh_sample_count": (c_int, [c_uint32, c_uint32, _P, _P, ctypes.c_float, c_uint32, _P, c_size_t, _P, _P]),
+    "envgs_mesh_sample_emit": (c_int, [c_uint32, c_uint32, _P, _P, _P, c_uint32, _P, c_size_t, c_uint32, _P, _P, _P, _P]),
+    "envgs_points_grid_temp_bytes": (c_size_t, [c_uint32] + [ctypes.c_int32] * 3),
+    "envgs_points_grid_build": (c_int, [c_uint32, _P] + [ctypes.c_float] * 4 + [ctypes.c_int32] * 3 + [_P, c_size_t, _P, _P, _P]),
+    "envgs_points_nearest": (c_int, [c_uint32, _P] + [ctypes.c_float] * 5 + [ctypes.c_int32] * 3 + [_P] * 4 + [_P]),
     "envgs_l1_ssim_partial_count": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "envgs_l1_ssim_forward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P]),
     "envgs_l1_ssim_backward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, ctypes.c_float, ctypes.c_float, _P, _P]),

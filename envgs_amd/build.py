@@ -28,9 +28,10 @@ COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++20", "-fPIC", "-munsafe-fp-a
 # densify_device.hip: its decisions must equal torch's compare / divide on the same fp32 values and the gradient norm is a fixed sum
 # mesh.hip: the TSDF integration follows the NumPy oracle's fp32 sequence (multiply, add, IEEE divide, floor) decision for decision
 # mesh_simplify.hip: likewise the cell and the fixed-point offset of a vertex (subtract, IEEE divide, floor, multiply, add)
+# mesh_eval.hip: likewise the face area (products, differences, IEEE sqrt), the samples, the cell of a point and the squared distances
 _NO_SLP = ["-fno-slp-vectorize"]
 EXTRA = {"raster_project.hip": ["-ffp-contract=off"], "raster_project_bwd.hip": ["-ffp-contract=off"], "densify_device.hip": ["-ffp-contract=off"],
-         "mesh.hip": ["-ffp-contract=off"], "mesh_simplify.hip": ["-ffp-contract=off"],
+         "mesh.hip": ["-ffp-contract=off"], "mesh_simplify.hip": ["-ffp-contract=off"], "mesh_eval.hip": ["-ffp-contract=off"],
          "trace_kbuffer.hip": _NO_SLP, "trace_collect.hip": _NO_SLP, "trace_lists.hip": _NO_SLP,
          "trace_surfel_bwd.hip": _NO_SLP, "trace_api.hip": _NO_SLP}
 

@@ -224,8 +224,11 @@ def load_mesh_ply(path):
                 props[cur].append(w[1:])
             elif w[0] == "end_header":
                 break
+        if list(counts) == ["vertex"]:                          # a point cloud (a ground-truth scan for mesh.evaluate): no face element at all
+            counts["face"] = 0
+            props["face"] = [["list", "uchar", "int", "vertex_indices"]]
         if fmt != "binary_little_endian" or list(counts)[:2] != ["vertex", "face"]:
-            raise ValueError("load_mesh_ply reads binary little-endian files with a vertex element followed by a face element")
+            raise ValueError("load_mesh_ply reads binary little-endian files with a vertex element, followed by a face element or by nothing")
         if any(p[0] == "list" for p in props["vertex"]) or [p[:3] for p in props["face"]] != [["list", "uchar", "int"]]:
             raise ValueError("load_mesh_ply: unsupported vertex / face properties in %s" % path)
         vdt = np.dtype([(p[1], ("<" + _PLY_TYPES[p[0]]) if _PLY_TYPES[p[0]][1] != "1" else _PLY_TYPES[p[0]]) for p in props["vertex"]])

@@ -1,6 +1,7 @@
-"""Mesh extraction (include/envgs_mesh.h, csrc/mesh.hip, csrc/mesh_clean.hip, csrc/mesh_simplify.hip): TSDF fusion of rendered depth into a dense
-volume, marching tetrahedra over it, the clean-up of the mesh (connected components, order-preserving face selection, removal of small
-components) and its simplification by vertex clustering.
+"""Mesh extraction (include/envgs_mesh.h, csrc/mesh.hip, csrc/mesh_clean.hip, csrc/mesh_simplify.hip, csrc/mesh_eval.hip): TSDF fusion of rendered
+depth into a dense volume, marching tetrahedra over it, the clean-up of the mesh (connected components, order-preserving face selection, removal
+of small components), its simplification by vertex clustering, and its evaluation against a ground-truth cloud (surface samples, exact nearest
+points, Chamfer and F-score).
 
 PARITY UNPINNED: the reference ships a fuser (easyvolcap/utils/tsdf_utils.py, fusion_utils.py, runners/visualizers/geometry_visualizer.py) that
 cannot run as it stands and leaves the marching step to libraries outside it, so the semantics are this project's ("Mesh extraction");
@@ -11,6 +12,7 @@ tests/mesh_oracle.py restates them independently.  There is no CPU path: CPU ten
     mesh = clean(vol.extract())                 # csrc/mesh_clean.hip: components(), select_faces() and the 2DGS rule built on them
     mesh = simplify(clean(vol.extract()), 2 * voxel_size, origin=vol.origin)      # csrc/mesh_simplify.hip: vertex clustering on a uniform grid
     ckpt.save_mesh_ply("scene.ply", mesh.vertices, mesh.faces, mesh.colors)
+    score = evaluate(mesh, scan_points, max_distance=0.2, threshold=0.01, density=1e4)      # csrc/mesh_eval.hip: .chamfer, .fscore, ...
 """
 import math
 from types import SimpleNamespace
@@ -256,6 +258,25 @@ def _grid_dims(extent, cell_size):
     return dims
 
 
+def _finite_extent(vertices):
+    """-> (lo, hi): the per-axis extrema of the rows of (V,3) whose three coordinates are finite; zeros when there is none.  One host sync, a
+    second one when some row is not finite."""
+    lo, hi = [0.0] * 3, [0.0] * 3
+    if vertices.shape[0]:
+        # column by column: a full reduction of a strided column is 15 x faster here than amin(dim=0) over (V,3) (0.08 against 1.2 ms at V = 1.6 M)
+        columns = lambda t: [torch.aminmax(t[:, a]) for a in range(3)]
+        read = lambda lows, highs: torch.stack([torch.stack(lows), torch.stack(highs)]).tolist()
+        cols = columns(vertices)
+        ext = read([c.min for c in cols], [c.max for c in cols])
+        if not all(math.isfinite(x) for x in ext[0] + ext[1]):    # a NaN or an infinity somewhere: again, over the finite vertices alone
+            finite = torch.isfinite(vertices).all(dim=1, keepdim=True)
+            ext = read([c.min for c in columns(torch.where(finite, vertices, float("inf")))],
+                       [c.max for c in columns(torch.where(finite, vertices, float("-inf")))])
+        if all(math.isfinite(x) for x in ext[0] + ext[1]):        # else: no finite vertex, any grid will do
+            lo, hi = ext
+    return lo, hi
+
+
 def simplify_grid(vertices, cell_size, origin=None, dims=None):
     """The clustering grid simplify() uses: -> (origin (ox, oy, oz), dims (nx, ny, nz)).  origin None: the per-axis minimum of the vertices whose
     three coordinates are finite; dims[a] = floor((max[a] - origin[a]) / cell_size) + 1 over the same vertices, at least 1 (in double; positions
@@ -276,19 +297,7 @@ def simplify_grid(vertices, cell_size, origin=None, dims=None):
             raise ValueError("simplify: dims %s must be three counts of at least 1 whose product is below 2^31" % (dims,))
         if origin is not None:
             return tuple(origin), dims
-    lo, hi = [0.0] * 3, [0.0] * 3
-    if vertices.shape[0]:
-        # column by column: a full reduction of a strided column is 15 x faster here than amin(dim=0) over (V,3) (0.08 against 1.2 ms at V = 1.6 M)
-        columns = lambda t: [torch.aminmax(t[:, a]) for a in range(3)]
-        read = lambda lows, highs: torch.stack([torch.stack(lows), torch.stack(highs)]).tolist()
-        cols = columns(vertices)
-        ext = read([c.min for c in cols], [c.max for c in cols])
-        if not all(math.isfinite(x) for x in ext[0] + ext[1]):    # a NaN or an infinity somewhere: again, over the finite vertices alone
-            finite = torch.isfinite(vertices).all(dim=1, keepdim=True)
-            ext = read([c.min for c in columns(torch.where(finite, vertices, float("inf")))],
-                       [c.max for c in columns(torch.where(finite, vertices, float("-inf")))])
-        if all(math.isfinite(x) for x in ext[0] + ext[1]):        # else: no finite vertex, any grid will do
-            lo, hi = ext
+    lo, hi = _finite_extent(vertices)
     if origin is not None:
         lo = origin
     if dims is not None:
@@ -381,3 +390,175 @@ def fuse_surfels(volume, cameras, base, sh_degree, depth_ratio=0.0, alpha_min=0.
                                  torch.stack([c.T.cpu().reshape(3) for c in cs]), rgb=torch.stack([m.rgb for m in ms]),
                                  mask=torch.stack([m.alpha > alpha_min for m in ms]))
     return maps
+
+
+# ---- evaluation (csrc/mesh_eval.hip) ------------------------------------------------------------------------------------------------------------------
+POINTS_MAX_DIM, POINTS_MAX_CELLS = 1024, 2 ** 27                 # ENVGS_POINTS_MAX_DIM, ENVGS_POINTS_MAX_CELLS
+
+
+def sample_surface(mesh, density, seed=0, return_face=False):
+    """Area-proportional surface samples with canonical bytes (include/envgs_mesh.h, "evaluation"): face f gets floor(area density + u_f) samples,
+    u_f and the samples themselves coming from a counter hash of (seed, f, k), ordered by ascending (face, k).  Faces with an index outside
+    [0, V), a corner or an area that is not finite, or no area get none.  density: samples per unit area, positive and finite; seed: 0 .. 2^32-1.
+    -> (points (S,3) f32, colors (S,3) f32 or None), plus face (S,) i32 with return_face.  One host sync: the read-back of S.  Raises ValueError
+    when a face would get 2^24 samples or more, or the mesh 2^31 or more."""
+    v, f, c = _mesh_tensors(mesh, "sample_surface")
+    density, seed = float(density), int(seed)
+    if not (density > 0.0 and math.isfinite(density)) or not 0.0 < float(torch.tensor(density, dtype=torch.float32)) < float("inf"):
+        raise ValueError("sample_surface: density must be positive and finite")
+    if not 0 <= seed < 2 ** 32:
+        raise ValueError("sample_surface: seed must be in 0 .. 2^32 - 1")
+    lib = _lib.load()
+    dev = v.device
+    V, F = v.shape[0], f.shape[0]
+    tb = lib.envgs_mesh_sample_temp_bytes(V, F)
+    temp = torch.empty(tb, dtype=torch.uint8, device=dev)
+    totals = torch.empty(2, dtype=torch.int64, device=dev)
+    p = _lib.ptr
+    _lib.check(lib.envgs_mesh_sample_count(V, F, p(v), p(f), density, seed, p(temp), tb, p(totals), _stream(dev)), "envgs_mesh_sample_count")
+    S, over = totals.tolist()
+    if over:
+        raise ValueError("sample_surface: density %g gives one face 2^24 samples or more" % density)
+    if not 0 <= S < 2 ** 31:
+        raise ValueError("sample_surface: density %g gives %d samples, 2^31 or more" % (density, S & (2 ** 64 - 1)))
+    points = torch.empty(S, 3, dtype=torch.float32, device=dev)
+    colors = torch.empty(S, 3, dtype=torch.float32, device=dev) if c is not None else None
+    face = torch.empty(S, dtype=torch.int32, device=dev) if return_face else None
+    _lib.check(lib.envgs_mesh_sample_emit(V, F, p(v), p(c), p(f), seed, p(temp), tb, S, p(points), p(colors), p(face), _stream(dev)),
+               "envgs_mesh_sample_emit")
+    return (points, colors, face) if return_face else (points, colors)
+
+
+def _points_tensor(t, what):
+    _need_gpu(t, what)
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous() or t.shape[0] >= 2 ** 31:
+        raise ValueError("%s: points must be a contiguous (N,3) float32 tensor of fewer than 2^31 rows" % what)
+    return t
+
+
+def _f32(x):
+    return float(torch.tensor(float(x), dtype=torch.float32))
+
+
+class PointGrid:
+    """A uniform grid over the finite rows of points (N,3), for exact nearest-point queries within max_distance (include/envgs_mesh.h).  The grid
+    is sized as simplify_grid sizes its own: the origin is the per-axis minimum of the finite points, dims[a] = floor(extent[a] / cell_size) + 1;
+    at most 1024 cells per axis and 2^27 in all.  cell_size None: max(max_distance / 16, the edge at which the bounding box holds about 4 cells
+    per point), raised until the limits hold -- a guess that nobody has tuned ("Mesh evaluation"); an explicit cell_size outside the
+    limits raises ValueError, naming the smallest admissible value.  The result of nearest() does not depend on cell_size.
+    One host sync: the read-back of the extrema (a second one when some point is not finite).  `points` itself is not kept."""
+
+    def __init__(self, points, max_distance, cell_size=None):
+        points = _points_tensor(points, "PointGrid")
+        max_distance = float(max_distance)
+        if not (max_distance >= 0.0 and math.isfinite(max_distance) and math.isfinite(_f32(max_distance))):
+            raise ValueError("PointGrid: max_distance must be finite and not negative")
+        lo, hi = _finite_extent(points)
+        extent = [h - l for l, h in zip(lo, hi)]
+        N = points.shape[0]
+
+        def admissible(c):
+            d = _grid_dims(extent, c)
+            return max(d) <= POINTS_MAX_DIM and math.prod(d) <= POINTS_MAX_CELLS
+
+        if cell_size is None:
+            spans = [e for e in extent if e > 0.0]
+            per_point = (math.prod(spans) / (4.0 * max(N, 1))) ** (1.0 / len(spans)) if spans else 0.0
+            cell_size = max(max_distance / 16.0, per_point)
+            if not (cell_size > 0.0 and math.isfinite(cell_size) and _f32(cell_size) > 0.0):
+                cell_size = 1.0
+            while not admissible(cell_size):
+                cell_size *= 1.125
+        else:
+            cell_size = float(cell_size)
+            if not (cell_size > 0.0 and math.isfinite(cell_size)) or not 0.0 < _f32(cell_size) < float("inf"):
+                raise ValueError("PointGrid: cell_size must be positive and finite")
+            if not admissible(cell_size):
+                bad, good = cell_size, 2.0 * cell_size
+                while not admissible(good):
+                    bad, good = good, 2.0 * good
+                for _ in range(60):
+                    mid = 0.5 * (bad + good)
+                    bad, good = (bad, mid) if admissible(mid) else (mid, good)
+                raise ValueError("PointGrid: cell_size %g gives a grid of %s cells, beyond 1024 per axis or 2^27 in all; the smallest admissible "
+                                 "cell_size here is %r" % (cell_size, _grid_dims(extent, cell_size), good))
+        self.origin, self.dims = tuple(lo), tuple(_grid_dims(extent, cell_size))
+        self.cell_size, self.max_distance, self.count, self.device = cell_size, max_distance, N, points.device
+        lib = _lib.load()
+        nx, ny, nz = self.dims
+        tb = lib.envgs_points_grid_temp_bytes(N, nx, ny, nz)
+        temp = torch.empty(tb, dtype=torch.uint8, device=points.device)
+        self.cell_end = torch.empty(nx * ny * nz, dtype=torch.int32, device=points.device)
+        self.records = torch.empty(N, 4, dtype=torch.float32, device=points.device)
+        p = _lib.ptr
+        _lib.check(lib.envgs_points_grid_build(N, p(points), lo[0], lo[1], lo[2], cell_size, nx, ny, nz, p(temp), tb, p(self.cell_end), p(self.records),
+                                               _stream(points.device)), "envgs_points_grid_build")
+
+    def nearest(self, queries):
+        """-> (dist2 (Q,) f32, index (Q,) i32): per query the finite point of least squared distance among those within max_distance, of equal ones
+        the lowest index; +inf and -1 when there is none or the query is not finite.  No host sync."""
+        queries = _points_tensor(queries, "PointGrid.nearest")
+        if queries.device != self.device:
+            raise ValueError("PointGrid.nearest: the queries must be on the grid's device")
+        Q = queries.shape[0]
+        dist2 = torch.empty(Q, dtype=torch.float32, device=self.device)
+        index = torch.empty(Q, dtype=torch.int32, device=self.device)
+        nx, ny, nz = self.dims
+        p = _lib.ptr
+        _lib.check(_lib.load().envgs_points_nearest(Q, p(queries), self.max_distance, self.origin[0], self.origin[1], self.origin[2], self.cell_size, nx, ny, nz,
+                                                    p(self.cell_end), p(self.records), p(dist2), p(index), _stream(self.device)), "envgs_points_nearest")
+        return dist2, index
+
+
+def nearest_points(queries, points, max_distance, cell_size=None):
+    """PointGrid(points, max_distance, cell_size).nearest(queries) -> (dist2 (Q,) f32, index (Q,) i32)."""
+    return PointGrid(points, max_distance, cell_size).nearest(queries)
+
+
+def _eval_points(x, density, seed, what):
+    if isinstance(x, torch.Tensor):
+        return _points_tensor(x, what)
+    if density is None:
+        raise ValueError("%s: a mesh needs a sampling density" % what)
+    return sample_surface(x, density, seed)[0]
+
+
+def evaluate(mesh_or_points, reference_points, max_distance, threshold, density=None, seed=0):
+    """A prediction -- a Mesh, sampled at `density` with `seed`, or a (N,3) point tensor -- against a ground-truth cloud (M,3), by the conventions
+    of the DTU and Tanks-and-Temples evaluations (adopted here as this project's choice).  With d = sqrt(dist2) in float64 of the nearest point
+    within max_distance:
+      accuracy      mean d over the prediction samples that found a neighbour (the DTU rule: what lies beyond max_distance is left out)
+      completeness  the same from the reference to the prediction;     chamfer  (accuracy + completeness) / 2
+      precision     share of ALL prediction samples with d <= threshold (no neighbour is a miss);   recall  the same the other way
+      fscore        2 P R / (P + R), 0 when both are 0
+    plus the counts n_pred, n_ref, found_pred, found_ref, within_pred, within_ref and the per-point distances d_pred (N,), d_ref (M,) (float64
+    device tensors, +inf = no neighbour).  A mean over no sample is nan, a share of no sample 0.  threshold <= max_distance is required.
+    Two grids, two searches; the reductions are torch in float64 with one read-back."""
+    max_distance, threshold = float(max_distance), float(threshold)
+    if not 0.0 <= threshold <= max_distance:
+        raise ValueError("evaluate: 0 <= threshold <= max_distance is required")
+    pred = _eval_points(mesh_or_points, density, seed, "evaluate")
+    ref = _points_tensor(reference_points, "evaluate")
+    if pred.device != ref.device:
+        raise ValueError("evaluate: the prediction and the reference must be on one device")
+    d_pred = torch.sqrt(PointGrid(ref, max_distance).nearest(pred)[0].double())
+    d_ref = torch.sqrt(PointGrid(pred, max_distance).nearest(ref)[0].double())
+    rows = []
+    for d in (d_pred, d_ref):
+        found = torch.isfinite(d)
+        rows += [torch.where(found, d, torch.zeros((), dtype=torch.float64, device=d.device)).sum(), found.sum().double(), (d <= threshold).sum().double()]
+    sum_p, found_p, within_p, sum_r, found_r, within_r = torch.stack(rows).tolist()
+    n_pred, n_ref = pred.shape[0], ref.shape[0]
+    accuracy = sum_p / found_p if found_p else float("nan")
+    completeness = sum_r / found_r if found_r else float("nan")
+    precision = within_p / n_pred if n_pred else 0.0
+    recall = within_r / n_ref if n_ref else 0.0
+    fscore = 2.0 * precision * recall / (precision + recall) if precision + recall > 0.0 else 0.0
+    return SimpleNamespace(accuracy=accuracy, completeness=completeness, chamfer=0.5 * (accuracy + completeness), precision=precision, recall=recall,
+                           fscore=fscore, n_pred=n_pred, n_ref=n_ref, found_pred=int(found_p), found_ref=int(found_r), within_pred=int(within_p),
+                           within_ref=int(within_r), d_pred=d_pred, d_ref=d_ref)
+
+
+def compare_meshes(a, b, max_distance, threshold, density, seed=0):
+    """evaluate() of the surface samples of mesh `a` against those of mesh `b`, both at `density` with `seed`: what simplify() or clean() cost."""
+    return evaluate(a, sample_surface(b, density, seed)[0], max_distance, threshold, density=density, seed=seed)

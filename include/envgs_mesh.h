@@ -167,6 +167,80 @@ ENVGS_API int envgs_mesh_simplify_cluster(uint32_t V, uint32_t F, const float *v
                                           float *cl_vertices, float *cl_colors, int32_t *cl_faces, uint8_t *keep, int32_t *vertex_cluster,
                                           uint32_t *count, void *stream);
 
+/* ---- evaluation: surface samples and exact nearest points (csrc/mesh_eval.hip, csrc/mesh_rng.h) ---------------------------------------------------
+ * PARITY UNPINNED like the rest of this header: the reference has no mesh evaluation.  tests/mesh_eval_oracle.py restates what follows in NumPy.
+ * All float arithmetic is fp32, left to right, no FMA, IEEE division and square root.
+ *
+ * Counter hash, on uint32:  mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ *                           h(seed, f, j) = mix(mix(mix(seed) ^ f) ^ j);   bits(h) = h >> 8;   uniform(h) = (float)bits(h) * 2^-24  (exact)
+ *
+ * Surface samples.  The mesh is as for the clean-up (V and F below 2^31, any origin); density > 0 is samples per unit area.
+ * 1. Count of face f with corners a, b, c:  e1 = b - a, e2 = c - a, n = e1 x e2 with every component p*q - r*s as written;
+ *      area = 0.5f * sqrtf((nx*nx + ny*ny) + nz*nz);   n_f = floor(area * density + uniform(h(seed, f, 0xFFFFFFFF)))
+ *    n_f = 0 if an index is outside [0, V) (such an index is never dereferenced), if a corner coordinate or the area is not finite, or if the
+ *    area is 0.  A face whose area * density + uniform is 2^24 or more sets the over-limit flag (and counts 0).
+ * 2. The samples are ordered by ascending (f, k), k = 0 .. n_f - 1; S = sum of n_f.
+ * 3. Sample k of face f:  hu = h(seed, f, 2k), hv = h(seed, f, 2k + 1);  u = uniform(hu), v = uniform(hv);
+ *      if bits(hu) + bits(hv) > 2^24 (that is u + v > 1, decided on the integers) then u = 1 - u, v = 1 - v (both exact);
+ *      point = (a + u * e1) + v * e2 per component; the colour is the same expression on the corner colours. */
+
+/* Scratch bytes of envgs_mesh_sample_count / _emit: 4 B per face plus the per-workgroup totals (0 if a count is out of range). */
+ENVGS_API size_t envgs_mesh_sample_temp_bytes(uint32_t V, uint32_t F);
+
+/* Counts and scans, and leaves totals[0] = S as a 64-bit sum and totals[1] != 0 iff a face was over the limit, on the device; the caller reads
+ * both back at once (the one host sync), refuses a flagged mesh or an S of 2^31 or more, and sizes the outputs.  `temp` carries the plan to
+ * envgs_mesh_sample_emit and must not be touched in between; V, F, vertices, faces and seed must be the same there.  Pointers to arrays of zero
+ * rows may be NULL; every other NULL, a count at or above 2^31, a density that is not positive and finite and a `temp` that is not 16-byte
+ * aligned return ENVGS_ERR_BAD_ARG before any GPU work, a short `temp` ENVGS_ERR_TEMP_TOO_SMALL. */
+ENVGS_API int envgs_mesh_sample_count(uint32_t V, uint32_t F, const float *vertices, const int32_t *faces, float density, uint32_t seed, void *temp,
+                                      size_t temp_bytes, uint64_t *totals, void *stream);
+
+/* points (S,3); out_colors (S,3; NULL: none, else `colors` must be given); out_face (S) the face of each sample (NULL: not wanted).  S is the
+ * total read back; nothing at or beyond row S is written, and a row at or beyond the counted total is left alone.  No atomics: two runs give
+ * identical bytes. */
+ENVGS_API int envgs_mesh_sample_emit(uint32_t V, uint32_t F, const float *vertices, const float *colors, const int32_t *faces, uint32_t seed,
+                                     const void *temp, size_t temp_bytes, uint32_t S, float *points, float *out_colors, int32_t *out_face, void *stream);
+
+/* Nearest point within a radius.  For a query q and the points p_0 .. p_{N-1}:
+ *      d2(q, p) = ((dx*dx) + (dy*dy)) + (dz*dz), d = q - p;   r2 = max_distance * max_distance
+ *    the candidates are the points whose three coordinates are finite and whose d2 <= r2; the result is the candidate of least d2, of equal ones
+ *    the one of lowest index; with no candidate, or a query that is not finite: dist2 = +inf, index = -1.
+ * The result is a lexicographic minimum over a set, so it depends on no order inside the kernel: two runs, and two grids, give identical bytes.
+ *
+ * The grid is that of the simplification: nx ny nz cells of edge `cell` from the origin, x fastest, and the cell of a point is its rule 1, with
+ * positions outside clamped into the border cells; here 1 <= n* <= ENVGS_POINTS_MAX_DIM and nx ny nz <= ENVGS_POINTS_MAX_CELLS.  A query starts
+ * in its own cell by the same rule and visits the Chebyshev shells r = 0, 1, 2 .. around it, clipped to the grid.  After shell r, with
+ *      b = ((float)r * cell) * (1 - 2^-10)
+ * it stops if best_d2 <= b*b or b > max_distance; and it stops after the last shell that holds a cell of the grid, an integer known before the
+ * loop, so no input makes a lane spin.
+ *
+ * Why the stop is exact.  The cell index of rule 1 is monotone in the coordinate, and the quotient (x - o) / cell it floors carries a relative
+ * error of at most 2^-22 (one rounding of the difference, one of the division, and slack).  A point that is not in shells 0 .. r has a clamped index
+ * that differs from the query's by at least r + 1 on some axis.  Between the two lie r whole cells, so with exact quotients the two coordinates
+ * would differ by more than r cell; each computed quotient is off by at most 2^-22 of its magnitude, which is at most about n* <= 1024 cells inside
+ * the grid (outside it clamping only moves the true position farther away), so the coordinates differ by more than cell (r - 2^-21 n*) >=
+ * r cell (1 - 2^-11) for r >= 1 (for r = 0 the bound b = 0 claims nothing).  The computed d2 of such a point is at least the square of that
+ * axis difference less 3 * 2^-24 relative rounding, and b = r cell (1 - 2^-10), rounded twice, stays below it.  So every point outside the
+ * visited shells has d2 > b*b: it cannot beat, or tie, a best at or below b*b, and once b > max_distance it is no candidate. */
+#define ENVGS_POINTS_MAX_DIM 1024
+#define ENVGS_POINTS_MAX_CELLS (1u << 27)
+
+/* Scratch bytes of envgs_points_grid_build: 4 B per point plus the per-workgroup totals of the cells (0 if a count or the grid is out of range). */
+ENVGS_API size_t envgs_points_grid_temp_bytes(uint32_t N, int32_t nx, int32_t ny, int32_t nz);
+
+/* Builds the grid over points (N,3): cell_end (nx ny nz) u32, the end of each cell in `records`, the end of cell c - 1 being the start of cell c;
+ * records (N,4), 16-byte aligned: (x, y, z, index bits) of the finite points in cell order -- rows at or beyond their number are not written, and
+ * the order inside a cell may depend on scheduling.  `temp` is free again when the call returns.  N = 0 is valid (records may be NULL).  Every
+ * other NULL, a count at or above 2^31, a grid out of range, a cell that is not positive and finite, an origin that is not finite and a `temp`
+ * or `records` that is not 16-byte aligned return ENVGS_ERR_BAD_ARG before any GPU work, a short `temp` ENVGS_ERR_TEMP_TOO_SMALL. */
+ENVGS_API int envgs_points_grid_build(uint32_t N, const float *points, float ox, float oy, float oz, float cell, int32_t nx, int32_t ny, int32_t nz,
+                                      void *temp, size_t temp_bytes, uint32_t *cell_end, float *records, void *stream);
+
+/* dist2 (Q) and index (Q) of queries (Q,3) against a grid built with the same origin, cell and dimensions; one query per lane in the given
+ * order.  max_distance must be finite and >= 0.  Q = 0 is valid. */
+ENVGS_API int envgs_points_nearest(uint32_t Q, const float *queries, float max_distance, float ox, float oy, float oz, float cell, int32_t nx, int32_t ny,
+                                   int32_t nz, const uint32_t *cell_end, const float *records, float *dist2, int32_t *index, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
