@@ -177,6 +177,135 @@ __device__ __forceinline__ uint32_t block_exclusive_u32(uint32_t v, uint32_t *s_
 
 __device__ __forceinline__ void atomic_add_f32(float *p, float v) { unsafeAtomicAdd(p, v); }
 
+// The XCD (0..7, each with a private L2) the calling wavefront really runs on.
+__device__ __forceinline__ int xcc_id()
+{
+    unsigned v;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
+    return (int)(v & 7u);
+}
+
+// ---- tile queues of the persistent compositing grids (R6 / R7, raster_render.hip) ----------------
+// A call's tile queue block (include/envgs_raster.h: tile_queue), in 32-bit words:
+//   [0, 256)      R6's eight queue heads, one per 128 B line        [256, 512)  R7's
+//   then order6[ntiles], order7[ntiles], tile_cost[ntiles]
+// order[x * per .. ) with per = ceil(ntiles / 8) is queue x: the tiles of band x (the contiguous eighth xcd_tile() gives XCD x), heaviest
+// cost class first, tile index ascending inside a class.
+constexpr int TQ_CLASSES = 32;
+constexpr int TQ_HEAD_STRIDE = 32;
+constexpr int TQ_HEADS = 8 * TQ_HEAD_STRIDE;
+struct TileQueue {
+    uint32_t *heads6, *heads7, *order6, *order7, *tile_cost;
+};
+__host__ __device__ inline size_t tile_queue_words(int ntiles) { return 2 * (size_t)TQ_HEADS + 3 * (size_t)ntiles; }
+inline TileQueue tile_queue_of(uint32_t *block, int ntiles)
+{
+    return TileQueue{block, block + TQ_HEADS, block + 2 * TQ_HEADS, block + 2 * TQ_HEADS + ntiles, block + 2 * TQ_HEADS + 2 * (size_t)ntiles};
+}
+constexpr uint32_t TQ_COST_MAX = (1u << 27) - 1u;         // costs saturate here: cost * TQ_CLASSES stays inside 32 bits
+__host__ __device__ inline int tile_cost_class(uint32_t cost, uint32_t max_cost)
+{
+    return (int)((cost * (uint32_t)TQ_CLASSES) / (max_cost + 1u));                  // 0 .. TQ_CLASSES - 1
+}
+
+// Builds the queues from the tiles' costs and clears the eight heads: a counting sort into TQ_CLASSES classes, per band -- or, with one_queue,
+// over all tiles into ONE queue (head 0; inside a class the bands follow each other, so tile index still ascends).  Called by every thread of ONE
+// workgroup (a whole number of wavefronts).  cost(t) = hi[t * stride] - (lo ? lo[t * stride] : 0); hi == nullptr = every cost 0 (index order).
+// The costs are read once, coalesced, and staged in LDS; an image of more than TQ_STAGE tiles (2 M pixels) gets index order.
+// One workgroup runs this code once: what it costs is instruction fetch, so the loops stay rolled and there is one division, 32 bits wide.
+constexpr int TQ_STAGE = 8192;
+struct TileOrderLds {
+    uint32_t hist[8 * TQ_CLASSES];     // tiles per (band, class)
+    uint32_t base[8 * TQ_CLASSES];     // per (band, class): the next place in the order
+    uint32_t max_cost;
+    uint32_t cls[TQ_STAGE];            // per tile: its cost, then its class
+};
+__device__ __forceinline__ void build_tile_order(const uint32_t *hi, const uint32_t *lo, const int stride, const int ntiles, const bool one_queue,
+                                                 uint32_t *__restrict__ order, uint32_t *__restrict__ heads, TileOrderLds &S)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nthreads = blockDim.x, nw = nthreads >> 6;
+    if (tid < 8) heads[tid * TQ_HEAD_STRIDE] = 0u;
+    if (ntiles > TQ_STAGE || !hi) {
+        for (int t = tid; t < ntiles; t += nthreads) order[t] = (uint32_t)t;
+        return;
+    }
+    for (int i = tid; i < 8 * TQ_CLASSES; i += nthreads) S.hist[i] = 0u;
+    if (tid == 0) S.max_cost = 0u;
+    __syncthreads();
+    uint32_t m = 0u;
+#pragma nounroll
+    for (int t = tid; t < ntiles; t += nthreads) {
+        uint32_t c = hi[(size_t)t * stride];
+        if (lo) c -= lo[(size_t)t * stride];
+        c = min(c, TQ_COST_MAX);
+        S.cls[t] = c;
+        m = max(m, c);
+    }
+#pragma nounroll
+    for (int d = 1; d < 64; d <<= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d));
+    if (lane == 0) atomicMax(&S.max_cost, m);
+    __syncthreads();
+    const uint32_t max_cost = S.max_cost;
+    const int per = (ntiles + 7) >> 3;
+#pragma nounroll
+    for (int t = tid; t < ntiles; t += nthreads) {
+        const int k = tile_cost_class(S.cls[t], max_cost);
+        S.cls[t] = (uint32_t)k;
+        atomicAdd(&S.hist[(t / per) * TQ_CLASSES + k], 1u);
+    }
+    __syncthreads();
+    // one wavefront per band takes its tiles to their places, 64 at a time: the lanes of one class (found with one ballot per class bit, no
+    // loop over the classes) take consecutive places behind the class's running base, which the first of them moves on
+    static_assert(TQ_CLASSES == 32, "five class bits");
+    const unsigned long long lanes_before = (1ull << lane) - 1ull;
+#pragma nounroll
+    for (int row = wave; row < 8; row += nw) {
+        const int first = row * per, cnt = max(0, min(per, ntiles - first));
+        if (cnt == 0) continue;
+        // lane k: where this band's tiles of class k start = the tiles of the heavier classes (of this band, or with one queue of every
+        // band) + with one queue the earlier bands' tiles of class k
+        uint32_t heavier = 0u, base = one_queue ? 0u : (uint32_t)first;
+        if (lane < TQ_CLASSES) {
+            if (one_queue) {
+#pragma nounroll
+                for (int x = 0; x < 8; x++) {
+                    const uint32_t h = S.hist[x * TQ_CLASSES + lane];
+                    heavier += h;
+                    base += x < row ? h : 0u;
+                }
+            } else {
+                heavier = S.hist[row * TQ_CLASSES + lane];
+            }
+        }
+#pragma nounroll
+        for (int k = 1; k < TQ_CLASSES; k++) {
+            const uint32_t h = (uint32_t)__builtin_amdgcn_readlane((int)heavier, k);
+            base += k > lane ? h : 0u;
+        }
+        uint32_t *bases = S.base + row * TQ_CLASSES;         // this wavefront's alone
+        if (lane < TQ_CLASSES) __hip_atomic_store(&bases[lane], base, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+#pragma nounroll
+        for (int start = 0; start < cnt; start += 64) {
+            const int i = start + lane;
+            const bool valid = i < cnt;
+            const uint32_t c = valid ? S.cls[first + i] : 0u;
+            unsigned long long same = __builtin_amdgcn_ballot_w64(valid);
+#pragma unroll
+            for (int bit = 0; bit < 5; bit++) {
+                const bool on = (c >> bit) & 1u;
+                const unsigned long long b = __builtin_amdgcn_ballot_w64(on);
+                same &= on ? b : ~b;
+            }
+            if (valid) {
+                const uint32_t rank = (uint32_t)__builtin_popcountll(same & lanes_before);
+                const uint32_t b0 = __hip_atomic_load(&bases[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                order[b0 + rank] = (uint32_t)(first + i);
+                if (rank == 0u) __hip_atomic_store(&bases[c], b0 + (uint32_t)__builtin_popcountll(same), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+        }
+    }
+}
+
 // ---- launchers implemented in the kernel translation units ---------------------------------------
 int launch_project(const envgs_raster_cfg *cfg, const float *means3D, const float *scales, const float *rotations,
                    const float *opacities, const float *shs, const float *transmat_precomp, const float *viewmatrix,
@@ -186,7 +315,10 @@ int launch_scan(const uint32_t *in, uint32_t *out, int n, void *temp, size_t tem
 size_t scan_temp_bytes(int n);
 size_t sort_temp_bytes(uint32_t n, int width, int height);
 int launch_bin(const envgs_raster_cfg *cfg, uint32_t N, const float *geom, const int32_t *radii, uint64_t *tile_pairs,
-               uint64_t *keys_sorted, uint32_t *point_list, void *bin_temp, size_t bin_temp_bytes, uint32_t *ranges, hipStream_t stream);
+               uint64_t *keys_sorted, uint32_t *point_list, void *bin_temp, size_t bin_temp_bytes, uint32_t *ranges, hipStream_t stream,
+               uint32_t *tile_queue = nullptr);
+void launch_tile_order(int ntiles, const uint32_t *hi, const uint32_t *lo, int stride, uint32_t *order, uint32_t *heads, hipStream_t stream);
+inline bool tile_one_queue() { return (debug_switch(ENVGS_DBG_BALANCE) & 4) == 0; }      // ENVGS_DBG_BALANCE value 4: one queue per band instead
 size_t key_sort_temp_bytes(int n);
 int launch_key_sort(int n, const uint64_t *keys_in, uint64_t *keys_out, int top_bit, void *temp, size_t temp_bytes, hipStream_t stream);
 size_t ray_sort_temp_bytes(int R);
@@ -195,11 +327,11 @@ int launch_ray_sort(int R, const float *ray_o, const float *ray_d, const float4 
 int launch_render_fwd(const envgs_raster_cfg *cfg, const uint32_t *ranges, const uint32_t *point_list, const float *geom,
                       const float *colors, const float *bg, float *out_color, float *allmap, float *final_T,
                       int32_t *n_contrib, float *weight, hipStream_t stream, uint8_t *audit_contrib = nullptr, int audit_lmax = 0, int colors_f16 = 0,
-                      uint8_t *contrib_mask = nullptr, const uint8_t *audit_skip = nullptr);
+                      uint8_t *contrib_mask = nullptr, const uint8_t *audit_skip = nullptr, uint32_t *tile_queue = nullptr);
 int launch_render_bwd(const envgs_raster_cfg *cfg, const uint32_t *ranges, const uint32_t *point_list, const float *geom,
                       const float *colors, const float *bg, const float *final_T, const int32_t *n_contrib,
                       const float *dL_dcolor, const float *dL_dallmap, float *grad_rec, hipStream_t stream, int colors_f16 = 0,
-                      const uint8_t *contrib_mask = nullptr);
+                      const uint8_t *contrib_mask = nullptr, uint32_t *tile_queue = nullptr);
 int launch_project_bwd(const envgs_raster_cfg *cfg, const float *geom, const float *means3D, const float *scales,
                        const float *rotations, const float *shs, const uint8_t *clamped, const float *transmat_precomp,
                        const int32_t *radii, const float *viewmatrix, const float *projmatrix, const float *campos,

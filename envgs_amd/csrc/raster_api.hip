@@ -49,10 +49,25 @@ int envgs_raster_project(const envgs_raster_cfg *cfg, const float *means3D, cons
     return (int)e;
 }
 
+size_t envgs_raster_tile_queue_bytes(int32_t width, int32_t height)
+{
+    if (width <= 0 || height <= 0) return 0;
+    return sizeof(uint32_t) * tile_queue_words(((width + TILE - 1) / TILE) * ((height + TILE - 1) / TILE));
+}
+
 int envgs_raster_bin_and_render(const envgs_raster_cfg *cfg, uint32_t N, const float *geom, const int32_t *radii,
                                 const float *colors, const float *bg, uint64_t *tile_pairs, uint64_t *keys_sorted, uint32_t *point_list,
                                 void *bin_temp, size_t bin_temp_bytes_, uint32_t *ranges, float *out_color, float *allmap,
                                 float *final_T, int32_t *n_contrib, float *weight, uint8_t *contrib_mask, void *stream_)
+{
+    return envgs_raster_bin_and_render_queued(cfg, N, geom, radii, colors, bg, tile_pairs, keys_sorted, point_list, bin_temp, bin_temp_bytes_, ranges,
+                                              out_color, allmap, final_T, n_contrib, weight, contrib_mask, nullptr, stream_);
+}
+
+int envgs_raster_bin_and_render_queued(const envgs_raster_cfg *cfg, uint32_t N, const float *geom, const int32_t *radii,
+                                       const float *colors, const float *bg, uint64_t *tile_pairs, uint64_t *keys_sorted, uint32_t *point_list,
+                                       void *bin_temp, size_t bin_temp_bytes_, uint32_t *ranges, float *out_color, float *allmap,
+                                       float *final_T, int32_t *n_contrib, float *weight, uint8_t *contrib_mask, uint32_t *tile_queue, void *stream_)
 {
     int rc = check_cfg(cfg);
     if (rc) return rc;
@@ -60,11 +75,12 @@ int envgs_raster_bin_and_render(const envgs_raster_cfg *cfg, uint32_t N, const f
     if (cfg->P > 0 && (!geom || !radii || !colors || !weight)) return ENVGS_ERR_BAD_ARG;
     if (N > 0 && (!tile_pairs || !point_list || !bin_temp)) return ENVGS_ERR_BAD_ARG;
     hipStream_t stream = (hipStream_t)stream_;
-    rc = launch_bin(cfg, N, geom, radii, tile_pairs, keys_sorted, point_list, bin_temp, bin_temp_bytes_, ranges, stream);
+    if (tile_queue && (reinterpret_cast<size_t>(tile_queue) & 127)) return ENVGS_ERR_BAD_ARG;
+    rc = launch_bin(cfg, N, geom, radii, tile_pairs, keys_sorted, point_list, bin_temp, bin_temp_bytes_, ranges, stream, tile_queue);
     if (rc) return rc;
     // `colors` is the caller's (possibly half) colors_precomp only when no SH were given; the SH -> RGB result of _project is fp32
     return launch_render_fwd(cfg, ranges, point_list, geom, colors, bg, out_color, allmap, final_T, n_contrib, weight, stream, nullptr, 0,
-                             (cfg->feature_f16 && cfg->sh_coeffs == 0) ? 1 : 0, contrib_mask);
+                             (cfg->feature_f16 && cfg->sh_coeffs == 0) ? 1 : 0, contrib_mask, nullptr, tile_queue);
 }
 
 int envgs_raster_render_audit(const envgs_raster_cfg *cfg, const float *geom, const float *colors, const float *bg,
@@ -91,6 +107,20 @@ int envgs_raster_backward(const envgs_raster_cfg *cfg, uint32_t N, const float *
                           float *dscales, float *drots, float *dshs, float *dcolors, float *dopacities,
                           float *dtransmat_precomp, void *stream_)
 {
+    return envgs_raster_backward_queued(cfg, N, geom, colors, bg, point_list, ranges, final_T, n_contrib, contrib_mask, dL_dcolor, dL_dallmap, means3D,
+                                        scales, rotations, shs, clamped, transmat_precomp, radii, viewmatrix, projmatrix, campos, grad_rec, dmeans3D,
+                                        dmeans2D, dscales, drots, dshs, dcolors, dopacities, dtransmat_precomp, nullptr, stream_);
+}
+
+int envgs_raster_backward_queued(const envgs_raster_cfg *cfg, uint32_t N, const float *geom, const float *colors, const float *bg,
+                                 const uint32_t *point_list, const uint32_t *ranges, const float *final_T,
+                                 const int32_t *n_contrib, const uint8_t *contrib_mask, const float *dL_dcolor, const float *dL_dallmap, const float *means3D,
+                                 const float *scales, const float *rotations, const float *shs, const uint8_t *clamped,
+                                 const float *transmat_precomp, const int32_t *radii, const float *viewmatrix,
+                                 const float *projmatrix, const float *campos, float *grad_rec, float *dmeans3D, float *dmeans2D,
+                                 float *dscales, float *drots, float *dshs, float *dcolors, float *dopacities,
+                                 float *dtransmat_precomp, uint32_t *tile_queue, void *stream_)
+{
     int rc = check_cfg(cfg);
     if (rc) return rc;
     if (cfg->P == 0) return 0;
@@ -102,7 +132,7 @@ int envgs_raster_backward(const envgs_raster_cfg *cfg, uint32_t N, const float *
     if (transmat_precomp ? !dtransmat_precomp : (!scales || !rotations || !means3D || !dmeans3D || !dscales || !drots)) return ENVGS_ERR_BAD_ARG;
     hipStream_t stream = (hipStream_t)stream_;
     rc = launch_render_bwd(cfg, ranges, point_list, geom, colors, bg, final_T, n_contrib, dL_dcolor, dL_dallmap, grad_rec, stream,
-                           (cfg->feature_f16 && !shs) ? 1 : 0, contrib_mask);
+                           (cfg->feature_f16 && !shs) ? 1 : 0, contrib_mask, tile_queue);
     if (rc) return rc;
     return launch_project_bwd(cfg, geom, means3D, scales, rotations, shs, clamped, transmat_precomp, radii, viewmatrix,
                               projmatrix, campos, grad_rec, dmeans3D, dmeans2D, dscales, drots, dshs, dcolors, dopacities,

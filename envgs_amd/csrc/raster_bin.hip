@@ -220,9 +220,10 @@ bin_column_scan(int rows, int ntiles, uint32_t *hist, uint32_t *__restrict__ til
 // One workgroup: exclusive scan of the tile totals -> tile_start, ranges (R5; empty tiles read [0,0) like the reference's zeroed buffer).
 __global__ void __launch_bounds__(1024)
 bin_tile_scan(int ntiles, const uint32_t *__restrict__ tile_count, uint32_t *__restrict__ tile_start, uint32_t *__restrict__ ranges,
-              uint32_t cap, uint32_t *__restrict__ hdr)
+              uint32_t cap, uint32_t *__restrict__ hdr, uint32_t *__restrict__ order = nullptr, uint32_t *__restrict__ heads = nullptr, int one_queue = 0)
 {
     __shared__ uint32_t s_w[17];
+    __shared__ TileOrderLds s_order;
     const int per = (ntiles + 1023) / 1024, b = min(ntiles, (int)threadIdx.x * per), e = min(ntiles, b + per);
     uint32_t s = 0;
     for (int k = b; k < e; k++) s += tile_count[k];
@@ -237,6 +238,23 @@ bin_tile_scan(int ntiles, const uint32_t *__restrict__ tile_count, uint32_t *__r
         run += c;
     }
     if (threadIdx.x == 0) { tile_start[ntiles] = total; hdr[0] = total; hdr[1] = 0u; hdr[2] = 0u; hdr[3] = 0u; }      // [1] long lists; sort_long_lists: [2] items claimed, [3] items done
+    // the raster binning only: R6's tile queues (cost = list length; every list is empty when the capacity was too small), and their heads
+    if (order) build_tile_order(ok ? tile_count : nullptr, nullptr, 1, ntiles, one_queue != 0, order, heads, s_order);
+}
+
+// The same queues in a launch of their own: R7's, from the pass counts R6 left in tile_cost (or from the list lengths in `ranges`, stride 2),
+// and R6's where no binning ran (hi == nullptr: index order).
+__global__ void __launch_bounds__(512)
+tile_order_kernel(int ntiles, const uint32_t *__restrict__ hi, const uint32_t *__restrict__ lo, int stride, int one_queue,
+                  uint32_t *__restrict__ order, uint32_t *__restrict__ heads)
+{
+    __shared__ TileOrderLds s_order;
+    build_tile_order(hi, lo, stride, ntiles, one_queue != 0, order, heads, s_order);
+}
+
+void launch_tile_order(int ntiles, const uint32_t *hi, const uint32_t *lo, int stride, uint32_t *order, uint32_t *heads, hipStream_t stream)
+{
+    hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(512), 0, stream, ntiles, hi, lo, stride, tile_one_queue() ? 1 : 0, order, heads);
 }
 
 // Sort the power-of-two padded LDS array of 1 << lp entries (tile_sort.h: register-blocked bitonic network, one barrier per 4 steps;
@@ -462,13 +480,18 @@ static int long_sort_grid()
 }
 
 int launch_bin(const envgs_raster_cfg *cfg, uint32_t N, const float *geom, const int32_t *radii, uint64_t *tile_pairs,
-               uint64_t *keys_sorted, uint32_t *point_list, void *bin_temp, size_t bin_temp_bytes, uint32_t *ranges, hipStream_t stream)
+               uint64_t *keys_sorted, uint32_t *point_list, void *bin_temp, size_t bin_temp_bytes, uint32_t *ranges, hipStream_t stream,
+               uint32_t *tile_queue)
 {
     // N is the CAPACITY of the N-sized buffers: the exact instance count when the caller waited for it, or a guess made before the count was
     // known on the host (no host sync between projection and binning).  The count itself is re-derived here (sum of the tile totals); a
     // capacity below it leaves every range empty and writes nothing out of bounds.
     const BinPlan pl = bin_plan(cfg->P, cfg->width, cfg->height);
-    if (N == 0 || cfg->P <= 0) return (int)hipMemsetAsync(ranges, 0, sizeof(uint32_t) * 2 * (size_t)pl.ntiles, stream);
+    const TileQueue tq = tile_queue_of(tile_queue, pl.ntiles);
+    if (N == 0 || cfg->P <= 0) {
+        if (tile_queue) { launch_tile_order(pl.ntiles, nullptr, nullptr, 1, tq.order6, tq.heads6, stream); ENVGS_CHECK_LAUNCH(cfg, stream); }
+        return (int)hipMemsetAsync(ranges, 0, sizeof(uint32_t) * 2 * (size_t)pl.ntiles, stream);
+    }
     if (bin_temp_bytes < sort_temp_bytes(N, cfg->width, cfg->height)) return ENVGS_ERR_TEMP_TOO_SMALL;
     uint32_t *hist = (uint32_t *)bin_temp;
     uint32_t *tile_count = hist + (size_t)BIN_ROWS_MAX * pl.ntiles;
@@ -482,7 +505,8 @@ int launch_bin(const envgs_raster_cfg *cfg, uint32_t N, const float *geom, const
     ENVGS_CHECK_LAUNCH(cfg, stream);
     hipLaunchKernelGGL(bin_column_scan, dim3((pl.ntiles + 15) / 16), dim3(256), 0, stream, pl.rows, pl.ntiles, hist, tile_count);
     ENVGS_CHECK_LAUNCH(cfg, stream);
-    hipLaunchKernelGGL(bin_tile_scan, dim3(1), dim3(1024), 0, stream, pl.ntiles, tile_count, tile_start, ranges, N, hdr);
+    hipLaunchKernelGGL(bin_tile_scan, dim3(1), dim3(1024), 0, stream, pl.ntiles, tile_count, tile_start, ranges, N, hdr,
+                       tile_queue ? tq.order6 : nullptr, tile_queue ? tq.heads6 : nullptr, tile_one_queue() ? 1 : 0);
     ENVGS_CHECK_LAUNCH(cfg, stream);
     hipLaunchKernelGGL(bin_pass<true>, dim3(pl.rows), dim3(256), lds, stream, cfg->P, cfg->width, cfg->height, pl.slice, pl.ntiles,
                        geom, radii, hist, tile_start, tile_pairs, N);
@@ -630,7 +654,7 @@ int launch_ray_sort(int R, const float *ray_o, const float *ray_d, const float4 
     hipLaunchKernelGGL(ray_bucket_pass<false>, dim3(rows), dim3(256), lds, stream, R, slice, nb, shift, ray_o, ray_d, (const float *)partial, rows, lead, keys, hist,
                        (const uint32_t *)nullptr, (uint64_t *)nullptr);
     hipLaunchKernelGGL(bin_column_scan, dim3((nb + 15) / 16), dim3(256), 0, stream, rows, nb, hist, count);
-    hipLaunchKernelGGL(bin_tile_scan, dim3(1), dim3(1024), 0, stream, nb, count, start, ranges, (uint32_t)R, hdr);
+    hipLaunchKernelGGL(bin_tile_scan, dim3(1), dim3(1024), 0, stream, nb, count, start, ranges, (uint32_t)R, hdr, (uint32_t *)nullptr, (uint32_t *)nullptr, 0);
     hipLaunchKernelGGL(ray_bucket_pass<true>, dim3(rows), dim3(256), lds, stream, R, slice, nb, shift, ray_o, ray_d, (const float *)partial, rows, lead, keys, hist, start, pairs);
     launch_bucket_sorts(R, nb, ranges, pairs, (uint64_t *)nullptr, order, hdr, long_list, 0, stream);
     return (int)hipGetLastError();
@@ -682,7 +706,7 @@ int launch_key_sort(int n, const uint64_t *keys_in, uint64_t *keys_out, int top_
     const size_t lds = sizeof(uint32_t) * (size_t)nb;
     hipLaunchKernelGGL(key_bucket_pass<false>, dim3(rows), dim3(256), lds, stream, n, slice, nb, shift, keys_in, hist, (const uint32_t *)nullptr, (uint64_t *)nullptr);
     hipLaunchKernelGGL(bin_column_scan, dim3((nb + 15) / 16), dim3(256), 0, stream, rows, nb, hist, count);
-    hipLaunchKernelGGL(bin_tile_scan, dim3(1), dim3(1024), 0, stream, nb, count, start, ranges, (uint32_t)n, hdr);
+    hipLaunchKernelGGL(bin_tile_scan, dim3(1), dim3(1024), 0, stream, nb, count, start, ranges, (uint32_t)n, hdr, (uint32_t *)nullptr, (uint32_t *)nullptr, 0);
     hipLaunchKernelGGL(key_bucket_pass<true>, dim3(rows), dim3(256), lds, stream, n, slice, nb, shift, keys_in, hist, start, keys_out);
     launch_bucket_sorts((uint64_t)n, nb, ranges, keys_out, keys_out, (uint32_t *)nullptr, hdr, long_list, 1, stream);      // in place
     return (int)hipGetLastError();

@@ -1,7 +1,12 @@
 // raster_render.hip -- R6 (front-to-back compositing) and R7 (its back-to-front gradient).
 //
-// CDNA4 mapping: one 256-lane workgroup per 16x16 tile (the reference's binning granularity, so tile /
-// sort indices stay bit-comparable); each of its 4 wavefronts owns one 8x8 pixel quadrant, so a
+// CDNA4 mapping: one 256-lane workgroup composites one 16x16 tile at a time (the reference's binning granularity, so tile /
+// sort indices stay bit-comparable).  Both kernels are PERSISTENT grids: as many workgroups as the device keeps resident (R6: 5 per CU, R7: 4),
+// each drawing tickets from the call's tile queue -- the tiles heaviest cost class first (common.h: build_tile_order; R6 by list length,
+// R7 by the exact pass count R6 leaves in tile_cost) -- until the queue is dry; no workgroup waits for another.  With ~2 tiles per resident
+// slot and the heaviest tile 2-3 times the mean, a fixed one-workgroup-per-tile order ended with whatever heavy tile started last.  Without a
+// queue block (the audit entry point, callers of the older C entry points) or under ENVGS_DBG_BALANCE value 2 the same kernels run one
+// workgroup per tile in xcd_tile() order.  Each of a workgroup's 4 wavefronts owns one 8x8 pixel quadrant, so a
 // wavefront's 64 lanes stay spatially compact: they agree on "this splat misses us" far more often than
 // a 16x4 strip would.  Per-tile splat lists are staged through LDS in batches of 256 records with
 // coalesced 16 B loads of the 64 B geom record; the inner loop reads each record as an LDS broadcast.
@@ -92,12 +97,44 @@ struct TileLds {
 // are resident per CU (160 KB LDS) instead of three with 256-splat batches (44 KB).
 constexpr int BWD_BATCH = 192;
 
-// XCD-aware tile order: consecutive workgroup ids land on different XCDs (b % 8), each with a private L2.  Give every
+// The fixed mapping (no tile queue): consecutive workgroup ids land on different XCDs (b % 8), each with a private L2.  Give every
 // XCD one contiguous run of tiles so neighbouring tiles -- which share most of their splats -- hit the same L2.
 __device__ __forceinline__ int xcd_tile(int b, int ntiles)
 {
     const int per = (ntiles + 7) >> 3;
     return (b & 7) * per + (b >> 3);
+}
+
+// The persistent grids' ticket (order / heads: common.h, tile queues).  nqueues = 0, the default: ONE queue over all tiles, thread 0 takes its
+// next entry.  nqueues = 8 (ENVGS_DBG_BALANCE value 4, the form measured against it): a queue per band; thread 0 takes the next entry of queue
+// `home` -- the XCD the workgroup really runs on, whose L2 holds that band's splats -- and, once a queue is dry, of home + 1, home + 2, ...
+// (mod 8).  `dry` counts the queues this workgroup has found dry (a dry queue stays dry: the heads only grow).  Returns the tile,
+// workgroup-uniform, or -1 when every queue is dry.  Two barriers: the first ends the previous tile's use of the LDS, the second publishes the
+// ticket.  No workgroup waits for another.
+__device__ __forceinline__ int take_tile(const uint32_t *__restrict__ order, uint32_t *__restrict__ heads, const int ntiles, const int home,
+                                         const int nqueues, int &dry, int *s_tile)
+{
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int per = nqueues ? (ntiles + 7) >> 3 : ntiles;
+        int t = -1;
+        while (dry < (nqueues ? nqueues : 1)) {
+            const int x = nqueues ? (home + dry) & 7 : 0;
+            const int cnt = min(per, ntiles - x * per);
+            if (cnt > 0) {
+                const uint32_t k = atomicAdd(heads + x * TQ_HEAD_STRIDE, 1u);
+                if (k < (uint32_t)cnt) {
+                    const uint32_t e = order[x * per + (int)k];
+                    t = e < (uint32_t)ntiles ? (int)e : -1;
+                    break;
+                }
+            }
+            dry++;
+        }
+        *s_tile = t;
+    }
+    __syncthreads();
+    return *s_tile;
 }
 
 // Exact wavefront-level culling.  A pixel composites a splat only if alpha = min(0.99, o*exp(-rho/2)) >= 1/255, i.e.
@@ -184,17 +221,26 @@ composite_fwd(int W, int H, int bg_len, const uint32_t *__restrict__ ranges, con
               const float *__restrict__ geom, const Feat colors, const float *__restrict__ bg,
               float *__restrict__ out_color, float *__restrict__ allmap, float *__restrict__ final_T,
               int32_t *__restrict__ n_contrib, float *__restrict__ weight, uint8_t *__restrict__ audit_contrib, int audit_lmax,
-              uint8_t *__restrict__ contrib_mask, const uint8_t *__restrict__ audit_skip)
+              uint8_t *__restrict__ contrib_mask, const uint8_t *__restrict__ audit_skip,
+              const uint32_t *__restrict__ order, uint32_t *__restrict__ heads, uint32_t *__restrict__ tile_cost, const int nqueues)
 {
     __shared__ TileLds<C> lds;
     __shared__ float wacc[256];            // per-splat weight summed over the 4 wavefronts before it leaves the CU
     __shared__ unsigned char cmk[256][4];  // per splat and quadrant: some pixel of the quadrant blended it (-> contrib_mask, what the backward walks);
                                            // each wavefront owns its byte: plain stores
-    const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
-    const int tile = xcd_tile(blockIdx.x, gx * gy);
-    if (tile >= gx * gy) return;
-    const int tx = tile % gx, ty = tile / gx;
+    __shared__ int s_tile;
+    __shared__ unsigned s_cost;            // (quadrant, splat) passes the backward will walk in this tile (-> tile_cost: R7's queue order)
+    const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE, ntiles = gx * gy;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    // order != nullptr: a persistent workgroup that composites tile after tile from the queues; else the fixed mapping, one tile per workgroup
+    const int home = order ? xcc_id() : 0;
+    int dry = 0;
+  for (bool first = true;; first = false) {
+    int tile;
+    if (order) tile = take_tile(order, heads, ntiles, home, nqueues, dry, &s_tile);
+    else tile = (first && xcd_tile(blockIdx.x, ntiles) < ntiles) ? xcd_tile(blockIdx.x, ntiles) : -1;
+    if (tile < 0) break;
+    const int tx = tile % gx, ty = tile / gx;
     const int pxi = tx * TILE + (wave & 1) * 8 + (lane & 7);
     const int pyi = ty * TILE + (wave >> 1) * 8 + (lane >> 3);
     const bool inside = pxi < W && pyi < H;
@@ -209,7 +255,8 @@ composite_fwd(int W, int H, int bg_len, const uint32_t *__restrict__ ranges, con
     int32_t last = 0, medc = -1;
 #pragma unroll
     for (int c = 0; c < C; c++) Cacc[c] = 0.f;
-    wacc[tid] = 0.f; reinterpret_cast<unsigned *>(&cmk[0][0])[tid] = 0u;
+    wacc[tid] = 0.f; reinterpret_cast<unsigned *>(&cmk[0][0])[tid] = 0u;          // per-tile LDS state (the ticket's barrier is behind us, the batch loop's ahead)
+    if (tid == 0) s_cost = 0u;
 
     for (uint32_t base = r0; base < r1; base += 256) {
         if (__syncthreads_and(done)) break;
@@ -270,16 +317,28 @@ composite_fwd(int W, int H, int bg_len, const uint32_t *__restrict__ ranges, con
           }
         }
         __syncthreads();
+        unsigned qmask = 0u;
         if (tid < count) {
             const float ws = wacc[tid];
             if (ws != 0.0f) { atomic_add_f32(weight + lds.id[tid], ws); wacc[tid] = 0.f; }
             if (contrib_mask) {
                 unsigned *cw = reinterpret_cast<unsigned *>(&cmk[0][0]) + tid;
                 const unsigned v = *cw;                            // 0x01 in byte q = quadrant q
-                contrib_mask[base + tid] = (uint8_t)((v & 1u) | ((v >> 7) & 2u) | ((v >> 14) & 4u) | ((v >> 21) & 8u));
+                qmask = (v & 1u) | ((v >> 7) & 2u) | ((v >> 14) & 4u) | ((v >> 21) & 8u);
+                contrib_mask[base + tid] = (uint8_t)qmask;
                 if (v) *cw = 0u;
             }
         }
+        if (tile_cost && contrib_mask) {
+            unsigned n = 0u;
+#pragma unroll
+            for (int q = 0; q < 4; q++) n += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64((qmask >> q) & 1u));
+            if (lane == 0 && n) atomicAdd(&s_cost, n);
+        }
+    }
+    if (tile_cost && contrib_mask) {
+        __syncthreads();
+        if (tid == 0) tile_cost[tile] = s_cost;
     }
 
     if (inside) {
@@ -294,6 +353,7 @@ composite_fwd(int W, int H, int bg_len, const uint32_t *__restrict__ ranges, con
         allmap[5 * HW + pid] = med;
         allmap[6 * HW + pid] = dist;
     }
+  }
 }
 
 // ------------------------------------------------------------------------------------------ R7 ---
@@ -470,7 +530,7 @@ composite_bwd(int W, int H, int bg_len, const uint32_t *__restrict__ ranges, con
               const float *__restrict__ geom, const Feat colors, const float *__restrict__ bg,
               const float *__restrict__ final_T, const int32_t *__restrict__ n_contrib,
               const float *__restrict__ dL_dcolor, const float *__restrict__ dL_dallmap, float *__restrict__ grad_rec,
-              const uint8_t *__restrict__ contrib_mask)
+              const uint8_t *__restrict__ contrib_mask, const uint32_t *__restrict__ order, uint32_t *__restrict__ heads, const int nqueues)
 {
     constexpr int V = 15 + C;
     __shared__ TileLds<C, BWD_BATCH> lds;
@@ -478,12 +538,20 @@ composite_bwd(int W, int H, int bg_len, const uint32_t *__restrict__ ranges, con
     // ONE global atomic per (splat, word).  The L2 atomic units retire roughly one dword per clock per channel
     // (~0.12 T dword-atomics/s measured), so the number of global atomic dwords -- not bytes -- is what R7 pays for.
     __shared__ float gacc[BWD_BATCH][V];
-    __shared__ int s_max_last, s_dist;
-    const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
-    const int tile = xcd_tile(blockIdx.x, gx * gy);
-    if (tile >= gx * gy) return;
-    const int tx = tile % gx, ty = tile / gx;
+    __shared__ int s_max_last, s_dist, s_tile;
+    const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE, ntiles = gx * gy;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    if (!order && xcd_tile(blockIdx.x, ntiles) >= ntiles) return;
+    for (int i = tid; i < BWD_BATCH * V; i += 256) (&gacc[0][0])[i] = 0.f;          // (every flush leaves it zero again)
+    // order != nullptr: a persistent workgroup that takes tile after tile from the queues; else the fixed mapping, one tile per workgroup
+    const int home = order ? xcc_id() : 0;
+    int dry = 0;
+  for (bool first = true;; first = false) {
+    int tile;
+    if (order) tile = take_tile(order, heads, ntiles, home, nqueues, dry, &s_tile);
+    else tile = first ? xcd_tile(blockIdx.x, ntiles) : -1;
+    if (tile < 0) break;
+    const int tx = tile % gx, ty = tile / gx;
     const int pxi = tx * TILE + (wave & 1) * 8 + (lane & 7);
     const int pyi = ty * TILE + (wave >> 1) * 8 + (lane >> 3);
     const bool inside = pxi < W && pyi < H;
@@ -493,7 +561,6 @@ composite_bwd(int W, int H, int bg_len, const uint32_t *__restrict__ ranges, con
 
     // Entries behind the deepest last-contributor of this tile were never blended by any pixel: skip them.
     if (tid == 0) { s_max_last = 0; s_dist = 0; }
-    for (int i = tid; i < BWD_BATCH * V; i += 256) (&gacc[0][0])[i] = 0.f;
     __syncthreads();
     {
         int m = last;
@@ -512,37 +579,77 @@ composite_bwd(int W, int H, int bg_len, const uint32_t *__restrict__ ranges, con
         composite_bwd_tile<C, true, EXACT>(lds, gacc, W, H, bg_len, point_list, geom, colors, bg, final_T, n_contrib, dL_dcolor, dL_dallmap, grad_rec, r0, tx, ty, max_last, contrib_mask);
     else
         composite_bwd_tile<C, false, EXACT>(lds, gacc, W, H, bg_len, point_list, geom, colors, bg, final_T, n_contrib, dL_dcolor, dL_dallmap, grad_rec, r0, tx, ty, max_last, contrib_mask);
+  }
 }
 
 // ------------------------------------------------------------------------------------ launchers ---
+// The grid of one compositing launch.  With a tile queue (tq.order != nullptr): as many workgroups as the device keeps resident (CUs x the
+// occupancy the runtime reports for this instantiation; R6: 5 per CU, R7: 4), never more than there are tiles -- each loops over tickets.
+// ENVGS_DBG_TILE_GRID > 0 sets the grid instead (tests: 1 or 3 workgroups take every tile; more workgroups than tiles).
+// Without one, or under ENVGS_DBG_BALANCE bit 2 (the A/B inside one build): one workgroup per tile in xcd_tile() order, as until round 9.
+struct TileDispatch {
+    const uint32_t *order;
+    uint32_t *heads;
+    int nqueues;          // take_tile: 0 = one queue over all tiles; 8 = a queue per band (ENVGS_DBG_BALANCE value 4)
+    unsigned grid;
+};
+
+template <typename Kernel>
+static TileDispatch tile_dispatch(Kernel kernel, int *slots /* per device, 0 = not asked yet */, int ntiles, const uint32_t *order, uint32_t *heads)
+{
+    const int sw = debug_switch(ENVGS_DBG_BALANCE);
+    TileDispatch d{order, heads, (sw & 4) ? 8 : 0, (unsigned)(8 * ((ntiles + 7) / 8))};
+    if (!order || (sw & 2)) { d.order = nullptr; d.heads = nullptr; return d; }
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
+    if (slots[dev] == 0) {
+        int cus = 0, per_cu = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 64;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) != hipSuccess || per_cu <= 0) per_cu = 1;
+        slots[dev] = cus * per_cu;
+    }
+    const int cap = debug_switch(ENVGS_DBG_TILE_GRID);
+    d.grid = (unsigned)(cap > 0 ? (cap < slots[dev] ? cap : slots[dev]) : (ntiles < slots[dev] ? ntiles : slots[dev]));
+    return d;
+}
+
+template <int C, bool AUDIT, bool EXACT>
+static void launch_fwd(const envgs_raster_cfg *cfg, const uint32_t *ranges, const uint32_t *point_list, const float *geom,
+                       const Feat colors, const float *bg, float *out_color, float *allmap, float *final_T,
+                       int32_t *n_contrib, float *weight, uint8_t *audit_contrib, int audit_lmax, hipStream_t stream, uint8_t *contrib_mask,
+                       const uint8_t *audit_skip, uint32_t *tile_queue)
+{
+    static int slots[16] = {};
+    const int ntiles = ((cfg->width + TILE - 1) / TILE) * ((cfg->height + TILE - 1) / TILE);
+    const TileQueue tq = tile_queue_of(tile_queue, ntiles);
+    const TileDispatch d = tile_dispatch(composite_fwd<C, AUDIT, EXACT>, slots, ntiles, tile_queue ? tq.order6 : nullptr, tile_queue ? tq.heads6 : nullptr);
+    hipLaunchKernelGGL((composite_fwd<C, AUDIT, EXACT>), dim3(d.grid), dim3(256), 0, stream, cfg->width, cfg->height, cfg->bg_len, ranges,
+                       point_list, geom, colors, bg, out_color, allmap, final_T, n_contrib, weight, audit_contrib, audit_lmax, contrib_mask, audit_skip,
+                       d.order, d.heads, tile_queue ? tq.tile_cost : nullptr, d.nqueues);
+}
+
 template <int C>
 static int run_fwd(const envgs_raster_cfg *cfg, const uint32_t *ranges, const uint32_t *point_list, const float *geom,
                    const float *colors, const float *bg, float *out_color, float *allmap, float *final_T,
                    int32_t *n_contrib, float *weight, uint8_t *audit_contrib, int audit_lmax, hipStream_t stream, int colors_f16, uint8_t *contrib_mask,
-                   const uint8_t *audit_skip)
+                   const uint8_t *audit_skip, uint32_t *tile_queue)
 {
-    const int gx = (cfg->width + TILE - 1) / TILE, gy = (cfg->height + TILE - 1) / TILE;
     ProfScope prof_(K_COMPOSITE_FWD, stream);
-    const dim3 grid(8 * ((gx * gy + 7) / 8)), block(256);
     const Feat colors_{colors, colors_f16 != 0};
 #ifdef ENVGS_DIAG
     if (debug_switch(ENVGS_DBG_RASTER_EXACT)) {       // diagnostic library only: IEEE divisions + library expf (the attribution run)
         if (audit_contrib)
-            hipLaunchKernelGGL((composite_fwd<C, true, true>), grid, block, 0, stream, cfg->width, cfg->height, cfg->bg_len, ranges,
-                               point_list, geom, colors_, bg, out_color, allmap, final_T, n_contrib, weight, audit_contrib, audit_lmax, contrib_mask, audit_skip);
+            launch_fwd<C, true, true>(cfg, ranges, point_list, geom, colors_, bg, out_color, allmap, final_T, n_contrib, weight, audit_contrib, audit_lmax, stream, contrib_mask, audit_skip, tile_queue);
         else
-            hipLaunchKernelGGL((composite_fwd<C, false, true>), grid, block, 0, stream, cfg->width, cfg->height, cfg->bg_len, ranges,
-                               point_list, geom, colors_, bg, out_color, allmap, final_T, n_contrib, weight, (uint8_t *)nullptr, 0, contrib_mask, (const uint8_t *)nullptr);
+            launch_fwd<C, false, true>(cfg, ranges, point_list, geom, colors_, bg, out_color, allmap, final_T, n_contrib, weight, nullptr, 0, stream, contrib_mask, nullptr, tile_queue);
         ENVGS_CHECK_LAUNCH(cfg, stream);
         return 0;
     }
 #endif
     if (audit_contrib)
-        hipLaunchKernelGGL((composite_fwd<C, true>), grid, block, 0, stream, cfg->width, cfg->height, cfg->bg_len, ranges,
-                           point_list, geom, colors_, bg, out_color, allmap, final_T, n_contrib, weight, audit_contrib, audit_lmax, contrib_mask, audit_skip);
+        launch_fwd<C, true, false>(cfg, ranges, point_list, geom, colors_, bg, out_color, allmap, final_T, n_contrib, weight, audit_contrib, audit_lmax, stream, contrib_mask, audit_skip, tile_queue);
     else
-        hipLaunchKernelGGL((composite_fwd<C, false>), grid, block, 0, stream, cfg->width, cfg->height, cfg->bg_len, ranges,
-                           point_list, geom, colors_, bg, out_color, allmap, final_T, n_contrib, weight, (uint8_t *)nullptr, 0, contrib_mask, (const uint8_t *)nullptr);
+        launch_fwd<C, false, false>(cfg, ranges, point_list, geom, colors_, bg, out_color, allmap, final_T, n_contrib, weight, nullptr, 0, stream, contrib_mask, nullptr, tile_queue);
     ENVGS_CHECK_LAUNCH(cfg, stream);
     return 0;
 }
@@ -550,52 +657,74 @@ static int run_fwd(const envgs_raster_cfg *cfg, const uint32_t *ranges, const ui
 int launch_render_fwd(const envgs_raster_cfg *cfg, const uint32_t *ranges, const uint32_t *point_list, const float *geom,
                       const float *colors, const float *bg, float *out_color, float *allmap, float *final_T,
                       int32_t *n_contrib, float *weight, hipStream_t stream, uint8_t *audit_contrib, int audit_lmax, int colors_f16, uint8_t *contrib_mask,
-                      const uint8_t *audit_skip)
+                      const uint8_t *audit_skip, uint32_t *tile_queue)
 {
     if (cfg->P > 0) {
         hipError_t e = hipMemsetAsync(weight, 0, sizeof(float) * (size_t)cfg->P, stream);
         if (e != hipSuccess) return (int)e;
     }
     switch (cfg->channels) {
-    case 3: return run_fwd<3>(cfg, ranges, point_list, geom, colors, bg, out_color, allmap, final_T, n_contrib, weight, audit_contrib, audit_lmax, stream, colors_f16, contrib_mask, audit_skip);
-    case 5: return run_fwd<5>(cfg, ranges, point_list, geom, colors, bg, out_color, allmap, final_T, n_contrib, weight, audit_contrib, audit_lmax, stream, colors_f16, contrib_mask, audit_skip);
-    case 7: return run_fwd<7>(cfg, ranges, point_list, geom, colors, bg, out_color, allmap, final_T, n_contrib, weight, audit_contrib, audit_lmax, stream, colors_f16, contrib_mask, audit_skip);
+    case 3: return run_fwd<3>(cfg, ranges, point_list, geom, colors, bg, out_color, allmap, final_T, n_contrib, weight, audit_contrib, audit_lmax, stream, colors_f16, contrib_mask, audit_skip, tile_queue);
+    case 5: return run_fwd<5>(cfg, ranges, point_list, geom, colors, bg, out_color, allmap, final_T, n_contrib, weight, audit_contrib, audit_lmax, stream, colors_f16, contrib_mask, audit_skip, tile_queue);
+    case 7: return run_fwd<7>(cfg, ranges, point_list, geom, colors, bg, out_color, allmap, final_T, n_contrib, weight, audit_contrib, audit_lmax, stream, colors_f16, contrib_mask, audit_skip, tile_queue);
     default: return ENVGS_ERR_BAD_ARG;
     }
+}
+
+template <int C, bool EXACT>
+static void launch_bwd(const envgs_raster_cfg *cfg, const uint32_t *ranges, const uint32_t *point_list, const float *geom,
+                       const Feat colors, const float *bg, const float *final_T, const int32_t *n_contrib,
+                       const float *dL_dcolor, const float *dL_dallmap, float *grad_rec, hipStream_t stream, const uint8_t *contrib_mask, uint32_t *tile_queue)
+{
+    static int slots[16] = {};
+    const int ntiles = ((cfg->width + TILE - 1) / TILE) * ((cfg->height + TILE - 1) / TILE);
+    const TileQueue tq = tile_queue_of(tile_queue, ntiles);
+    const TileDispatch d = tile_dispatch(composite_bwd<C, EXACT>, slots, ntiles, tile_queue ? tq.order7 : nullptr, tile_queue ? tq.heads7 : nullptr);
+    hipLaunchKernelGGL((composite_bwd<C, EXACT>), dim3(d.grid), dim3(256), 0, stream, cfg->width, cfg->height, cfg->bg_len, ranges,
+                       point_list, geom, colors, bg, final_T, n_contrib, dL_dcolor, dL_dallmap, grad_rec, contrib_mask, d.order, d.heads, d.nqueues);
 }
 
 template <int C>
 static int run_bwd(const envgs_raster_cfg *cfg, const uint32_t *ranges, const uint32_t *point_list, const float *geom,
                    const float *colors, const float *bg, const float *final_T, const int32_t *n_contrib,
-                   const float *dL_dcolor, const float *dL_dallmap, float *grad_rec, hipStream_t stream, int colors_f16, const uint8_t *contrib_mask)
+                   const float *dL_dcolor, const float *dL_dallmap, float *grad_rec, hipStream_t stream, int colors_f16, const uint8_t *contrib_mask,
+                   uint32_t *tile_queue)
 {
-    const int gx = (cfg->width + TILE - 1) / TILE, gy = (cfg->height + TILE - 1) / TILE;
     ProfScope prof_(K_COMPOSITE_BWD, stream);
+    const Feat colors_{colors, colors_f16 != 0};
 #ifdef ENVGS_DIAG
     if (debug_switch(ENVGS_DBG_RASTER_EXACT)) {
-        hipLaunchKernelGGL((composite_bwd<C, true>), dim3(8 * ((gx * gy + 7) / 8)), dim3(256), 0, stream, cfg->width, cfg->height, cfg->bg_len, ranges,
-                           point_list, geom, Feat{colors, colors_f16 != 0}, bg, final_T, n_contrib, dL_dcolor, dL_dallmap, grad_rec, contrib_mask);
+        launch_bwd<C, true>(cfg, ranges, point_list, geom, colors_, bg, final_T, n_contrib, dL_dcolor, dL_dallmap, grad_rec, stream, contrib_mask, tile_queue);
         ENVGS_CHECK_LAUNCH(cfg, stream);
         return 0;
     }
 #endif
-    hipLaunchKernelGGL((composite_bwd<C, false>), dim3(8 * ((gx * gy + 7) / 8)), dim3(256), 0, stream, cfg->width, cfg->height, cfg->bg_len, ranges,
-                       point_list, geom, Feat{colors, colors_f16 != 0}, bg, final_T, n_contrib, dL_dcolor, dL_dallmap, grad_rec, contrib_mask);
+    launch_bwd<C, false>(cfg, ranges, point_list, geom, colors_, bg, final_T, n_contrib, dL_dcolor, dL_dallmap, grad_rec, stream, contrib_mask, tile_queue);
     ENVGS_CHECK_LAUNCH(cfg, stream);
     return 0;
 }
 
 int launch_render_bwd(const envgs_raster_cfg *cfg, const uint32_t *ranges, const uint32_t *point_list, const float *geom,
                       const float *colors, const float *bg, const float *final_T, const int32_t *n_contrib,
-                      const float *dL_dcolor, const float *dL_dallmap, float *grad_rec, hipStream_t stream, int colors_f16, const uint8_t *contrib_mask)
+                      const float *dL_dcolor, const float *dL_dallmap, float *grad_rec, hipStream_t stream, int colors_f16, const uint8_t *contrib_mask,
+                      uint32_t *tile_queue)
 {
     if (cfg->P <= 0) return 0;
+    if (tile_queue) {
+        // R7's queues, in front of the grad_rec clear: heaviest first by the exact pass counts R6 left in tile_cost next to contrib_mask; without a
+        // contrib_mask by the list lengths, which is R6's order
+        const int ntiles = ((cfg->width + TILE - 1) / TILE) * ((cfg->height + TILE - 1) / TILE);
+        const TileQueue tq = tile_queue_of(tile_queue, ntiles);
+        if (contrib_mask) launch_tile_order(ntiles, tq.tile_cost, nullptr, 1, tq.order7, tq.heads7, stream);
+        else launch_tile_order(ntiles, ranges + 1, ranges, 2, tq.order7, tq.heads7, stream);
+        ENVGS_CHECK_LAUNCH(cfg, stream);
+    }
     hipError_t e = hipMemsetAsync(grad_rec, 0, sizeof(float) * GREC * (size_t)cfg->P, stream);
     if (e != hipSuccess) return (int)e;
     switch (cfg->channels) {
-    case 3: return run_bwd<3>(cfg, ranges, point_list, geom, colors, bg, final_T, n_contrib, dL_dcolor, dL_dallmap, grad_rec, stream, colors_f16, contrib_mask);
-    case 5: return run_bwd<5>(cfg, ranges, point_list, geom, colors, bg, final_T, n_contrib, dL_dcolor, dL_dallmap, grad_rec, stream, colors_f16, contrib_mask);
-    case 7: return run_bwd<7>(cfg, ranges, point_list, geom, colors, bg, final_T, n_contrib, dL_dcolor, dL_dallmap, grad_rec, stream, colors_f16, contrib_mask);
+    case 3: return run_bwd<3>(cfg, ranges, point_list, geom, colors, bg, final_T, n_contrib, dL_dcolor, dL_dallmap, grad_rec, stream, colors_f16, contrib_mask, tile_queue);
+    case 5: return run_bwd<5>(cfg, ranges, point_list, geom, colors, bg, final_T, n_contrib, dL_dcolor, dL_dallmap, grad_rec, stream, colors_f16, contrib_mask, tile_queue);
+    case 7: return run_bwd<7>(cfg, ranges, point_list, geom, colors, bg, final_T, n_contrib, dL_dcolor, dL_dallmap, grad_rec, stream, colors_f16, contrib_mask, tile_queue);
     default: return ENVGS_ERR_BAD_ARG;
     }
 }

@@ -574,13 +574,7 @@ __device__ __forceinline__ int ray_of(const TraceArgs &A, int slot) { return slo
 // workgroup b of a grid whose size is a multiple of 8: workgroups that share an XCD (b % 8) get one contiguous run of block slots
 __device__ __forceinline__ int xcd_block(int b, int nblocks) { return (b & 7) * (nblocks >> 3) + (b >> 3); }
 
-__device__ __forceinline__ int xcc_id()
-{
-    unsigned v;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
-    return (int)(v & 7u);
-}
-
+// (home = xcc_id(), common.h: the XCD the workgroup really runs on)
 __device__ __forceinline__ int fetch_batch(unsigned *ctr /*one per XCD: ENVGS_CTR_BATCH_FETCH_STRIDE words*/, int nbatch, int home, int lane)
 {
     const int per = (nbatch + 7) >> 3;

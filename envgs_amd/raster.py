@@ -112,6 +112,7 @@ def _store(t):
     return t
 
 
+TILE_QUEUE = {"on": True}     # R6 / R7 as persistent grids over per-call tile queues (include/envgs_raster.h: tile_queue); off = one workgroup per tile, fixed bands
 CONTRIB_MASK = {"on": True}   # forward records which pixel quadrants blended each tile instance; the backward walks exactly those (tests switch it off to cover the geometric fallback)
 
 
@@ -175,11 +176,13 @@ def rasterize_forward(C, means3D, shs, colors_precomp, opacities, scales, rotati
         bin_temp = torch.empty(max(bin_bytes, 1), dtype=torch.uint8, device=dev)
         # per tile instance: the pixel quadrants that blended it (the backward walks exactly those)
         cmask = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev) if CONTRIB_MASK["on"] else None
-        _lib.check(lib.envgs_raster_bin_and_render(cfg, cap, p(geom), p(radii), p(colors), p(bg), p(pairs), p(keys_s), p(point_list),
-                                                   p(bin_temp), bin_bytes, p(ranges), p(out_color), p(allmap), p(final_T),
-                                                   p(n_contrib), p(weight), p(cmask), stream),
-                   "envgs_raster_bin_and_render")
-        return pairs, keys_s, point_list, cmask
+        # this call's tile queues: R6's and R7's heads and orders and the per-tile pass counts, saved for the backward next to contrib_mask
+        tq = torch.empty(lib.envgs_raster_tile_queue_bytes(W, H) // 4, **i32) if TILE_QUEUE["on"] else None
+        _lib.check(lib.envgs_raster_bin_and_render_queued(cfg, cap, p(geom), p(radii), p(colors), p(bg), p(pairs), p(keys_s), p(point_list),
+                                                          p(bin_temp), bin_bytes, p(ranges), p(out_color), p(allmap), p(final_T),
+                                                          p(n_contrib), p(weight), p(cmask), p(tq), stream),
+                   "envgs_raster_bin_and_render_queued")
+        return pairs, keys_s, point_list, cmask, tq
 
     # The number of tile instances N sizes the binning buffers, and it is known only after the projection.  Waiting for it drains the
     # GPU's queue at the start of every step (and every launch after it is exposed until the host is ahead again: ~0.5 ms of idle GPU per
@@ -209,16 +212,23 @@ def rasterize_forward(C, means3D, shs, colors_precomp, opacities, scales, rotati
         if N > cap:
             LAST_STATS["n_guess_misses"] = LAST_STATS.get("n_guess_misses", 0) + 1
             bufs = bin_and_render(N)
-    pairs, keys_s, point_list, cmask = bufs
+    pairs, keys_s, point_list, cmask, tq = bufs
     # next capacity: 15 % above this count (64 k granularity), and not below 97 % of the previous capacity -- views alternate, scenes change slowly
     _N_GUESS[key] = max(((max(int(N * 1.15), N + 4096) + 65535) // 65536) * 65536, int(0.97 * (guess or 0)))
     LAST_STATS.update(N=N, P=P, H=H, W=W, C=C)
     saved = dict(cfg=cfg, N=N, geom=geom, colors=colors, bg=bg, point_list=point_list, ranges=ranges, final_T=final_T,
-                 n_contrib=n_contrib, contrib_mask=cmask, means3D=means3D, scales=scales, rotations=rotations, shs=shs, clamped=clamped,
+                 n_contrib=n_contrib, contrib_mask=cmask, tile_queue=tq, means3D=means3D, scales=scales, rotations=rotations, shs=shs, clamped=clamped,
                  cov3D_precomp=cov3D_precomp, radii=radii, view=view, proj=proj, campos=campos)
     if keep_binning:
         saved.update(tiles_touched=tiles, offsets=offsets, tile_pairs=pairs, keys_sorted=keys_s)
     return (out_color, radii, allmap, weight), saved
+
+
+def tile_queue_views(saved):
+    """The saved tile queue block by its parts (include/envgs_raster.h): heads6 / heads7 (8,), order6 / order7 and tile_cost (ntiles,)."""
+    tq = saved["tile_queue"]
+    n = (tq.numel() - 512) // 3
+    return dict(heads6=tq[0:256:32], heads7=tq[256:512:32], order6=tq[512:512 + n], order7=tq[512 + n:512 + 2 * n], tile_cost=tq[512 + 2 * n:512 + 3 * n])
 
 
 def render_audit(saved, lmax, skip_px=None, want_weight=False):
@@ -264,12 +274,12 @@ def rasterize_backward(saved, dL_dcolor, dL_dallmap):
     dshs = torch.empty(shs.shape, **f32) if shs is not None else None            # gradients are fp32 whatever the feature storage
     dcolors = torch.empty(P, C, **f32) if shs is None else None
     p = _lib.ptr
-    _lib.check(lib.envgs_raster_backward(cfg, saved["N"], p(saved["geom"]), p(saved["colors"]), p(saved["bg"]),
+    _lib.check(lib.envgs_raster_backward_queued(cfg, saved["N"], p(saved["geom"]), p(saved["colors"]), p(saved["bg"]),
                                          p(saved["point_list"]), p(saved["ranges"]), p(saved["final_T"]), p(saved["n_contrib"]),
                                          p(saved.get("contrib_mask")), p(dL_dcolor), p(dL_dallmap), p(saved["means3D"]), p(saved["scales"]), p(saved["rotations"]),
                                          p(shs), p(saved["clamped"]), p(cov), p(saved["radii"]), p(saved["view"]), p(saved["proj"]),
                                          p(saved["campos"]), p(grad_rec), p(dmeans3D), p(dmeans2D), p(dscales), p(drots), p(dshs),
-                                         p(dcolors), p(dopac), p(dcov), _stream(dev)), "envgs_raster_backward")
+                                         p(dcolors), p(dopac), p(dcov), p(saved.get("tile_queue")), _stream(dev)), "envgs_raster_backward_queued")
     return dict(means3D=dmeans3D, means2D=dmeans2D, shs=dshs, colors_precomp=dcolors, opacities=dopac, scales=dscales,
                 rotations=drots, cov3D_precomp=dcov, grad_rec=grad_rec)
 

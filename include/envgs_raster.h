@@ -116,6 +116,33 @@ ENVGS_API int envgs_raster_bin_and_render(const envgs_raster_cfg *cfg, uint32_t 
                                 float *weight, uint8_t *contrib_mask, void *stream);
 
 /*
+ * The same call with a TILE QUEUE block: R6 then runs as a persistent grid (as many workgroups as the device keeps resident, each taking
+ * tile after tile), and so does R7 in envgs_raster_backward_queued given the same block.  tile_queue: envgs_raster_tile_queue_bytes(width,
+ * height) bytes, 128 B aligned, owned by THIS call and its backward (not shared scratch: several forwards may be outstanding and their
+ * backwards may run in any order; one block serves one backward at a time).  In 32-bit words, with ntiles = the 16x16 tiles of the image and
+ * per = ceil(ntiles / 8):
+ *   [0, 256)  R6's eight queue heads, one per 128 B line      [256, 512)  R7's
+ *   [512, 512 + ntiles)  R6's order      [512 + ntiles, 512 + 2 ntiles)  R7's order      [512 + 2 ntiles, 512 + 3 ntiles)  tile_cost
+ * An order is ONE queue (head 0) of all tiles, heaviest cost class first (32 classes: class = cost * 32 / (largest cost + 1), costs
+ * saturating at 2^27 - 1), tile index ascending inside a class; every workgroup takes tickets from it until it is dry.  (ENVGS_DBG_BALANCE
+ * value 4: order[x * per ..] is queue x instead, the tiles of the x-th contiguous eighth of the image in the same order, and a workgroup takes
+ * from the queue of the XCD it runs on, then from the next ones.)  An image of more than 8192 tiles gets index order.  R6's cost is the tile's
+ * list length (built inside the binning, no launch of its own); R7's is tile_cost, the (quadrant, entry) passes R6 recorded in contrib_mask for
+ * the tile (built by one small launch in front of the backward) -- or the list length when there is no contrib_mask.  Which workgroup
+ * composites a tile changes no arithmetic: every per-pixel output is bit-identical to the call without a queue; `weight` and the gradients
+ * are float atomics across tiles.
+ * tile_queue == NULL is envgs_raster_bin_and_render (one workgroup per tile, fixed bands).
+ */
+ENVGS_API size_t envgs_raster_tile_queue_bytes(int32_t width, int32_t height);
+ENVGS_API int envgs_raster_bin_and_render_queued(const envgs_raster_cfg *cfg, uint32_t N,
+                                const float *geom, const int32_t *radii,
+                                const float *colors, const float *bg,
+                                uint64_t *tile_pairs, uint64_t *keys_sorted /* may be NULL */, uint32_t *point_list,
+                                void *bin_temp, size_t bin_temp_bytes, uint32_t *ranges,
+                                float *out_color, float *allmap, float *final_T, int32_t *n_contrib,
+                                float *weight, uint8_t *contrib_mask, uint32_t *tile_queue, void *stream);
+
+/*
  * Parity audit of stage R6 (tests only; no reference counterpart): the SAME compositing kernel, instantiated with one extra store --
  * contrib (H*W, lmax) uint8, contrib[pixel][k] = 1 when entry k of the pixel's tile list was blended into it -- so the per-pixel
  * contributor SETS can be compared bit-exactly with the oracle's.  Inputs are the outputs of _project / _bin_and_render; the image
@@ -150,6 +177,20 @@ ENVGS_API int envgs_raster_backward(const envgs_raster_cfg *cfg, uint32_t N,
                           float *dmeans3D, float *dmeans2D, float *dscales, float *drots,
                           float *dshs, float *dcolors, float *dopacities, float *dtransmat_precomp,
                           void *stream);
+/* The same with the tile queue block of the forward (envgs_raster_bin_and_render_queued; NULL = envgs_raster_backward). */
+ENVGS_API int envgs_raster_backward_queued(const envgs_raster_cfg *cfg, uint32_t N,
+                          const float *geom, const float *colors, const float *bg,
+                          const uint32_t *point_list, const uint32_t *ranges,
+                          const float *final_T, const int32_t *n_contrib, const uint8_t *contrib_mask /* may be NULL */,
+                          const float *dL_dcolor, const float *dL_dallmap,
+                          const float *means3D, const float *scales, const float *rotations,
+                          const float *shs, const uint8_t *clamped, const float *transmat_precomp,
+                          const int32_t *radii,
+                          const float *viewmatrix, const float *projmatrix, const float *campos,
+                          float *grad_rec,
+                          float *dmeans3D, float *dmeans2D, float *dscales, float *drots,
+                          float *dshs, float *dcolors, float *dopacities, float *dtransmat_precomp,
+                          uint32_t *tile_queue, void *stream);
 
 /*
  * Optional per-kernel timing with HIP events recorded on the launch stream (bench.py's roofline leg; the
@@ -186,8 +227,9 @@ ENVGS_API const char *envgs_prof_kernel_name(int kernel_id);
 #define ENVGS_DBG_RASTER_EXACT 3     /* libenvgs_hip_diag.so only: R6 / R7 with IEEE divisions and the library expf instead of v_rcp_f32 (+ Newton) / v_exp_f32 -- the attribution run of the parity tests; no effect in the product library */
 #define ENVGS_DBG_RAYKEY 4           /* ray coherence key (csrc/ray_key.h): value - 1 = direction-only rounds in front of the interleaved (direction, origin) rounds; 0 = default */
 #define ENVGS_DBG_SPARSE 5           /* sparse entries of the tracer's record backward (envgs_trace.h: sparse_hits): value - 1 = the largest hit count an entry may have to be filed per hit; 0 = default (4), 1 = off */
-#define ENVGS_DBG_BALANCE 6          /* how coarse work is handed out (round 7).  Bit 1: the tracer's record backward takes its batches in coherence order, grid-stride over at most 8192 workgroups (the order until round 7) instead of longest batch first, one workgroup per batch.  Bit 2: reserved (selected the fixed tile bands against round 7's tile queues of R6 / R7, which lost and were taken out: profiles/DEAD_ENDS.md); no effect.  Bits 8..: value >> 8 = classes K of the longest-first order (0 = default; 1 = coherence order through the new dispatch) -- the K sweep of profiles/r07_ab_balance.txt */
-#define ENVGS_DBG_COUNT 7
+#define ENVGS_DBG_BALANCE 6          /* how coarse work is handed out (round 7).  Bit 1: the tracer's record backward takes its batches in coherence order, grid-stride over at most 8192 workgroups (the order until round 7) instead of longest batch first, one workgroup per batch.  Bit 2 (value 2): R6 / R7 ignore the tile queue's order and run one workgroup per tile over the fixed bands, as without a queue (the A/B of round 9's persistent grids inside one build; the orders are still built).  Value 4: R6 / R7 take their tiles from a queue per XCD band with stealing instead of one queue over all tiles (the form measured against it: profiles/r09_ab_raster_persistent.txt).  Bits 8..: value >> 8 = classes K of the longest-first order (0 = default; 1 = coherence order through the new dispatch) -- the K sweep of profiles/r07_ab_balance.txt */
+#define ENVGS_DBG_TILE_GRID 7        /* workgroups of R6's / R7's persistent grids (0 = default: what the device keeps resident, at most one per tile); capped at the resident count.  Tests: 1 or 3 workgroups loop over every tile, or more workgroups than tiles */
+#define ENVGS_DBG_COUNT 8
 ENVGS_API void envgs_debug_set(int32_t which, int32_t value);
 ENVGS_API int32_t envgs_debug_get(int32_t which);
 
