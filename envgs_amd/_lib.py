@@ -130,6 +130,18 @@ class TsdfViews(ctypes.Structure):
     _fields_ = [("count", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("v", TsdfView * 8)]
 
 
+class CullView(ctypes.Structure):
+    """struct envgs_cull_view (include/envgs_mesh.h)."""
+    _fields_ = [("mask", ctypes.c_void_p), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("R", ctypes.c_float * 9), ("T", ctypes.c_float * 3)]
+
+
+class CullViews(ctypes.Structure):
+    """struct envgs_cull_views (include/envgs_mesh.h)."""
+    _fields_ = [("count", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("v", CullView * 8)]
+
+
 # every symbol include/*.h declares: name -> (restype, argtypes)
 _P = c_void_p
 SYMBOLS = {
@@ -206,6 +218,13 @@ SYMBOLS = {
     "envgs_points_grid_temp_bytes": (c_size_t, [c_uint32] + [ctypes.c_int32] * 3),
     "envgs_points_grid_build": (c_int, [c_uint32, _P] + [ctypes.c_float] * 4 + [ctypes.c_int32] * 3 + [_P, c_size_t, _P, _P, _P]),
     "envgs_points_nearest": (c_int, [c_uint32, _P] + [ctypes.c_float] * 5 + [ctypes.c_int32] * 3 + [_P] * 4 + [_P]),
+    "envgs_points_thin_temp_bytes": (c_size_t, [c_uint32]),
+    "envgs_points_thin_begin": (c_int, [c_uint32, _P, _P, c_size_t, _P, _P]),
+    "envgs_points_thin_round": (c_int, [c_uint32, _P, ctypes.c_float, ctypes.c_int32, c_uint32] + [ctypes.c_float] * 4 + [ctypes.c_int32] * 4
+                                + [_P, _P, _P, c_size_t] + [c_uint32] * 3 + [_P, _P]),
+    "envgs_points_thin_keep": (c_int, [c_uint32, _P, c_size_t, _P, _P]),
+    "envgs_mesh_cull_vertices": (c_int, [c_uint32, _P, ctypes.POINTER(CullViews), ctypes.c_int32, _P, _P]),
+    "envgs_mesh_cull_faces": (c_int, [c_uint32, c_uint32, _P, _P, _P, _P]),
     "envgs_l1_ssim_partial_count": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "envgs_l1_ssim_forward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P]),
     "envgs_l1_ssim_backward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, ctypes.c_float, ctypes.c_float, _P, _P]),

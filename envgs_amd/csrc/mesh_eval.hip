@@ -18,6 +18,13 @@
 //                  The slot order inside a cell depends on scheduling; the search result is a lexicographic minimum and does not.
 //   pg_nearest     a lane per query: Chebyshev shells around the query's cell.  A run of x-adjacent cells is one contiguous run of records, so a
 //                  shell is walked row by row: full rows on its four faces in j / k, the two end cells of the rows in between.
+// Thinning (header: "thinning"; over the same grid)
+//   th_begin       a lane per point: its state (UNDECIDED, or DROPPED if not finite) and the first worklist of the undecided
+//   th_round       a lane per undecided point: the cell rows of shells 0 .. R around it; a kept neighbour of lower key drops it, an undecided one
+//                  blocks it, else it is kept; the blocked go to the other worklist, one atomic per wavefront.  No lane waits for another.
+//   th_keep        a lane per point: the state as a byte
+// Culling (header: "culling")
+//   cull_vertices  a lane per vertex: up to 8 views by the pixel rule of tsdf_integrate;  cull_faces  a lane per face: all three corners kept
 #include "common.h"
 #include "mesh_rng.h"
 
@@ -229,6 +236,126 @@ pg_nearest(const uint32_t Q, const float *__restrict__ queries, const float max_
     index[q] = (int32_t)best.index;
 }
 
+// ---- thinning (header: "thinning") ----------------------------------------------------------------------------------------------------------------
+constexpr uint32_t TH_UNDECIDED = 0u, TH_KEPT = 1u, TH_DROPPED = 2u;
+// the counters at the end of the scratch: three worklist lengths used in rotation (round t reads TH_LEN + t % 3, appends to TH_LEN + (t + 1) % 3 and
+// clears TH_LEN + (t + 2) % 3 for round t + 1 to append to), and the number of rounds that found work
+constexpr uint32_t TH_LEN = 0u, TH_ROUNDS = 3u, TH_COUNTERS = 4u;
+
+// One atomic per wavefront: the lanes that want a slot are counted by a ballot, the first of them reserves the run, every one takes its rank in it.
+// Every lane of the wavefront must arrive here.  A slot at or beyond cap is never written (there are at most cap appenders by construction).
+__device__ __forceinline__ void th_append(const bool want, const uint32_t value, uint32_t *__restrict__ list, uint32_t *__restrict__ len, const uint32_t cap)
+{
+    const unsigned long long m = __ballot(want);
+    if (!m) return;                                               // the same in every lane of the wavefront
+    const int lane = lane_id(), leader = __ffsll((long long)m) - 1;
+    uint32_t base = 0;
+    if (lane == leader) base = atomicAdd(len, (uint32_t)__popcll(m));
+    base = (uint32_t)__shfl((int)base, leader);
+    if (want) {
+        const uint32_t slot = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (slot < cap) list[slot] = value;
+    }
+}
+
+// a lane per point: the state, and the first worklist; counters[TH_LEN + 0] was cleared by the host call
+__global__ void __launch_bounds__(256)
+th_begin(const uint32_t N, const float *__restrict__ points, uint32_t *__restrict__ state, uint32_t *__restrict__ list, uint32_t *__restrict__ counters)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    bool fin = false;
+    if (i < N) {
+        fin = ev_finite(points[3 * (size_t)i]) && ev_finite(points[3 * (size_t)i + 1]) && ev_finite(points[3 * (size_t)i + 2]);
+        state[i] = fin ? TH_UNDECIDED : TH_DROPPED;
+    }
+    th_append(fin, i, list, counters + TH_LEN, N);
+}
+
+// One round: a lane per undecided point.  It never waits for another lane: it reads whatever state its lower-keyed neighbours have at that moment,
+// and a neighbour that is still undecided only postpones it to the next launch (header: why a stale state is harmless).
+template <bool HASH>
+__global__ void __launch_bounds__(256)
+th_round(const uint32_t N, const float *__restrict__ points, const float r2, const uint32_t seed, const Grid g, const int32_t shells,
+         const uint32_t *__restrict__ cell_end, const float4 *__restrict__ records, uint32_t *state, const uint32_t *__restrict__ list_in,
+         uint32_t *__restrict__ list_out, uint32_t *__restrict__ counters, const uint32_t in, const uint32_t out, const uint32_t clear)
+{
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t m = min(counters[TH_LEN + in], N);
+    if (t == 0) {
+        counters[TH_LEN + clear] = 0u;
+        if (m) counters[TH_ROUNDS] += 1u;                         // one lane of one launch, and the launches are in order
+    }
+    uint32_t i = 0;
+    bool blocked = false;
+    if (t < m && (i = list_in[t]) < N) {
+        const float qx = points[3 * (size_t)i], qy = points[3 * (size_t)i + 1], qz = points[3 * (size_t)i + 2];
+        const uint32_t key = HASH ? rng_hash(seed, i, RNG_THIN_STREAM) : i;
+        const int32_t nx = g.n[0], ny = g.n[1], nz = g.n[2];
+        const int32_t ci = pg_axis(qx, g.o[0], g.cell, nx), cj = pg_axis(qy, g.o[1], g.cell, ny), ck = pg_axis(qz, g.o[2], g.cell, nz);
+        const int32_t k0 = max(ck - shells, 0), k1 = min(ck + shells, nz - 1), j0 = max(cj - shells, 0), j1 = min(cj + shells, ny - 1);
+        const int32_t i0 = max(ci - shells, 0), i1 = min(ci + shells, nx - 1);
+        bool dropped = false;
+        for (int32_t k = k0; k <= k1 && !dropped; k++) {
+            for (int32_t j = j0; j <= j1 && !dropped; j++) {
+                const uint32_t row = (uint32_t)nx * ((uint32_t)j + (uint32_t)ny * (uint32_t)k);      // x-adjacent cells are one run of records
+                const uint32_t c0 = row + (uint32_t)i0, first = c0 ? cell_end[c0 - 1] : 0u, last = min(cell_end[row + (uint32_t)i1], N);
+                for (uint32_t s = first; s < last; s++) {
+                    const float4 p = records[s];
+                    const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
+                    const float d2 = ((dx * dx) + (dy * dy)) + (dz * dz);
+                    const uint32_t o = __float_as_uint(p.w);
+                    if (!(d2 <= r2) || o == i || o >= N) continue;
+                    if ((HASH ? rng_hash(seed, o, RNG_THIN_STREAM) : o) > key) continue;
+                    const uint32_t st = __hip_atomic_load(state + o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (st == TH_KEPT) { dropped = true; break; }
+                    blocked = blocked || st == TH_UNDECIDED;
+                }
+            }
+        }
+        if (dropped) blocked = false;
+        if (!blocked) __hip_atomic_store(state + i, dropped ? TH_DROPPED : TH_KEPT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    th_append(blocked, i, list_out, counters + TH_LEN + out, N);
+}
+
+__global__ void __launch_bounds__(256)
+th_keep(const uint32_t N, const uint32_t *__restrict__ state, uint8_t *__restrict__ keep)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < N) keep[i] = state[i] == TH_KEPT ? 1 : 0;
+}
+
+// ---- culling to masks (header: "culling") ----------------------------------------------------------------------------------------------------------
+// a lane per vertex; the projection is that of tsdf_integrate (csrc/mesh.hip), operation for operation
+__global__ void __launch_bounds__(256)
+cull_vertices(const uint32_t V, const float *__restrict__ vertices, const envgs_cull_views views, const int accumulate, uint8_t *__restrict__ keep)
+{
+    const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+    if (v >= V) return;
+    const float x = vertices[3 * (size_t)v], y = vertices[3 * (size_t)v + 1], z = vertices[3 * (size_t)v + 2];
+    bool ok = ev_finite(x) && ev_finite(y) && ev_finite(z) && (!accumulate || keep[v] != 0);
+    for (int vi = 0; vi < views.count && ok; vi++) {
+        const envgs_cull_view &C = views.v[vi];
+        const float zc = C.R[6] * x + C.R[7] * y + C.R[8] * z + C.T[2];
+        if (!(zc > 0.f)) continue;
+        const float xc = C.R[0] * x + C.R[1] * y + C.R[2] * z + C.T[0];
+        const float yc = C.R[3] * x + C.R[4] * y + C.R[5] * z + C.T[1];
+        const float fu = floorf(C.fx * (xc / zc) + C.cx), fv = floorf(C.fy * (yc / zc) + C.cy);
+        if (!(fu >= 0.f && fu < (float)C.W && fv >= 0.f && fv < (float)C.H)) continue;
+        ok = C.mask[(size_t)(int)fv * (size_t)C.W + (size_t)(int)fu] != 0;
+    }
+    keep[v] = ok ? 1 : 0;
+}
+
+__global__ void __launch_bounds__(256)
+cull_faces(const uint32_t V, const uint32_t F, const int32_t *__restrict__ faces, const uint8_t *__restrict__ vertex_keep, uint8_t *__restrict__ face_keep)
+{
+    const uint32_t f = blockIdx.x * 256u + threadIdx.x;
+    if (f >= F) return;
+    uint32_t idx[3];
+    face_keep[f] = ms_indices(faces, f, V, idx) && vertex_keep[idx[0]] && vertex_keep[idx[1]] && vertex_keep[idx[2]] ? 1 : 0;
+}
+
 bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 uint32_t blocks_of(uint32_t n) { return (n + 255u) / 256u; }
@@ -271,6 +398,20 @@ GridTemp grid_temp(uint32_t N, uint32_t cells)
     t.scan = t.tot + up256(4 * (size_t)t.nbc);
     t.scan_bytes = scan_temp_bytes((int)t.nbc);
     t.total = t.scan + up256(t.scan_bytes);
+    return t;
+}
+
+// state (N) | worklist 0 (N) | worklist 1 (N) | counters
+struct ThinTemp { size_t state, list[2], counters, total; };
+ThinTemp thin_temp(uint32_t N)
+{
+    ThinTemp t;
+    const size_t part = up256(4 * (size_t)N);
+    t.state = 0;
+    t.list[0] = part;
+    t.list[1] = 2 * part;
+    t.counters = 3 * part;
+    t.total = t.counters + up256(4 * TH_COUNTERS);
     return t;
 }
 
@@ -363,6 +504,88 @@ int envgs_points_nearest(uint32_t Q, const float *queries, float max_distance, f
     const Grid g = {{ox, oy, oz}, cell, {nx, ny, nz}};
     hipLaunchKernelGGL(pg_nearest, dim3(blocks_of(Q)), dim3(256), 0, (hipStream_t)stream, Q, queries, max_distance, g, cell_end, (const float4 *)records, dist2,
                        index);
+    return (int)hipGetLastError();
+}
+
+size_t envgs_points_thin_temp_bytes(uint32_t N)
+{
+    return N >= COUNT_LIMIT ? 0 : thin_temp(N).total;
+}
+
+// count[0] = the length of worklist `slot`, count[1] = the rounds that found work
+static int thin_report(const uint32_t *counters, uint32_t slot, uint32_t *count, hipStream_t stream)
+{
+    hipError_t e;
+    if ((e = hipMemcpyAsync(count, counters + TH_LEN + slot, 4, hipMemcpyDeviceToDevice, stream)) != hipSuccess) return (int)e;
+    if ((e = hipMemcpyAsync(count + 1, counters + TH_ROUNDS, 4, hipMemcpyDeviceToDevice, stream)) != hipSuccess) return (int)e;
+    return (int)hipGetLastError();
+}
+
+int envgs_points_thin_begin(uint32_t N, const float *points, void *temp, size_t temp_bytes, uint32_t *count, void *stream_)
+{
+    if (N >= COUNT_LIMIT || !temp || !aligned16(temp) || !count || (N && !points)) return ENVGS_ERR_BAD_ARG;
+    const ThinTemp T = thin_temp(N);
+    if (temp_bytes < T.total) return ENVGS_ERR_TEMP_TOO_SMALL;
+    hipStream_t stream = (hipStream_t)stream_;
+    char *base = (char *)temp;
+    uint32_t *counters = (uint32_t *)(base + T.counters);
+    hipError_t e;
+    if ((e = hipMemsetAsync(counters, 0, 4 * TH_COUNTERS, stream)) != hipSuccess) return (int)e;
+    if (N) hipLaunchKernelGGL(th_begin, dim3(blocks_of(N)), dim3(256), 0, stream, N, points, (uint32_t *)(base + T.state), (uint32_t *)(base + T.list[0]), counters);
+    return thin_report(counters, 0, count, stream);
+}
+
+int envgs_points_thin_round(uint32_t N, const float *points, float radius, int32_t hashed, uint32_t seed, float ox, float oy, float oz, float cell, int32_t nx,
+                            int32_t ny, int32_t nz, int32_t shells, const uint32_t *cell_end, const float *records, void *temp, size_t temp_bytes,
+                            uint32_t first_round, uint32_t rounds, uint32_t undecided, uint32_t *count, void *stream_)
+{
+    const uint32_t cells = grid_cells(nx, ny, nz);
+    if (N >= COUNT_LIMIT || !cells || !grid_ok(ox, oy, oz, cell) || !cell_end || !aligned16(records) || !temp || !aligned16(temp) || !count) return ENVGS_ERR_BAD_ARG;
+    if (!(radius >= 0.0f) || !std::isfinite(radius) || shells < 0 || shells >= ENVGS_POINTS_MAX_DIM || (N && (!points || !records))) return ENVGS_ERR_BAD_ARG;
+    const ThinTemp T = thin_temp(N);
+    if (temp_bytes < T.total) return ENVGS_ERR_TEMP_TOO_SMALL;
+    hipStream_t stream = (hipStream_t)stream_;
+    char *base = (char *)temp;
+    uint32_t *counters = (uint32_t *)(base + T.counters), *state = (uint32_t *)(base + T.state);
+    const Grid g = {{ox, oy, oz}, cell, {nx, ny, nz}};
+    const float r2 = radius * radius;
+    const uint32_t lanes = undecided < N ? undecided : N;
+    uint32_t t = first_round;
+    for (uint32_t r = 0; r < rounds && lanes; r++, t++) {
+        uint32_t *in = (uint32_t *)(base + T.list[t & 1u]), *out = (uint32_t *)(base + T.list[(t + 1u) & 1u]);
+        const uint32_t a = t % 3u, b = (t % 3u + 1u) % 3u, c = (t % 3u + 2u) % 3u;
+        if (hashed)
+            hipLaunchKernelGGL(th_round<true>, dim3(blocks_of(lanes)), dim3(256), 0, stream, N, points, r2, seed, g, shells, cell_end, (const float4 *)records,
+                               state, (const uint32_t *)in, out, counters, a, b, c);
+        else
+            hipLaunchKernelGGL(th_round<false>, dim3(blocks_of(lanes)), dim3(256), 0, stream, N, points, r2, seed, g, shells, cell_end, (const float4 *)records,
+                               state, (const uint32_t *)in, out, counters, a, b, c);
+    }
+    return thin_report(counters, t % 3u, count, stream);
+}
+
+int envgs_points_thin_keep(uint32_t N, const void *temp, size_t temp_bytes, uint8_t *keep, void *stream)
+{
+    if (N >= COUNT_LIMIT || !temp || !aligned16(temp) || (N && !keep)) return ENVGS_ERR_BAD_ARG;
+    const ThinTemp T = thin_temp(N);
+    if (temp_bytes < T.total) return ENVGS_ERR_TEMP_TOO_SMALL;
+    if (N) hipLaunchKernelGGL(th_keep, dim3(blocks_of(N)), dim3(256), 0, (hipStream_t)stream, N, (const uint32_t *)((const char *)temp + T.state), keep);
+    return (int)hipGetLastError();
+}
+
+int envgs_mesh_cull_vertices(uint32_t V, const float *vertices, const envgs_cull_views *views, int32_t accumulate, uint8_t *keep, void *stream)
+{
+    if (V >= COUNT_LIMIT || !views || views->count < 0 || views->count > ENVGS_TSDF_MAX_VIEWS || (V && (!vertices || !keep))) return ENVGS_ERR_BAD_ARG;
+    for (int i = 0; i < views->count; i++)
+        if (!views->v[i].mask || views->v[i].H < 1 || views->v[i].W < 1) return ENVGS_ERR_BAD_ARG;
+    if (V) hipLaunchKernelGGL(cull_vertices, dim3(blocks_of(V)), dim3(256), 0, (hipStream_t)stream, V, vertices, *views, (int)accumulate, keep);
+    return (int)hipGetLastError();
+}
+
+int envgs_mesh_cull_faces(uint32_t V, uint32_t F, const int32_t *faces, const uint8_t *vertex_keep, uint8_t *face_keep, void *stream)
+{
+    if (V >= COUNT_LIMIT || F >= COUNT_LIMIT || (F && (!faces || !face_keep)) || (F && V && !vertex_keep)) return ENVGS_ERR_BAD_ARG;
+    if (F) hipLaunchKernelGGL(cull_faces, dim3(blocks_of(F)), dim3(256), 0, (hipStream_t)stream, V, F, faces, vertex_keep, face_keep);
     return (int)hipGetLastError();
 }
 

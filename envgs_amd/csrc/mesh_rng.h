@@ -17,6 +17,10 @@
 namespace envgs {
 
 constexpr uint32_t RNG_COUNT_STREAM = 0xffffffffu;               // the counter of a face's rounding draw; samples use 2k and 2k + 1
+// The counter of a point's thinning key, key(i) = rng_hash(seed, i, RNG_THIN_STREAM).  rng_mix is a bijection of uint32 (xor-shifts and odd
+// multipliers are invertible) and so is xor with a constant, so for a fixed seed i -> key(i) is a permutation of uint32: the keys of distinct
+// points are distinct and the order by key is strict without a tie-break.
+constexpr uint32_t RNG_THIN_STREAM = 0xfffffffeu;
 
 ENVGS_RNG_FN uint32_t rng_mix(uint32_t x)
 {

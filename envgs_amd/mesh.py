@@ -13,6 +13,8 @@ tests/mesh_oracle.py restates them independently.  There is no CPU path: CPU ten
     mesh = simplify(clean(vol.extract()), 2 * voxel_size, origin=vol.origin)      # csrc/mesh_simplify.hip: vertex clustering on a uniform grid
     ckpt.save_mesh_ply("scene.ply", mesh.vertices, mesh.faces, mesh.colors)
     score = evaluate(mesh, scan_points, max_distance=0.2, threshold=0.01, density=1e4)      # csrc/mesh_eval.hip: .chamfer, .fscore, ...
+    dtu = evaluate_dtu(cull_to_masks(mesh, cameras, masks), scan_points, radius=0.2, max_distance=20.0, density=25.0,
+                       observed=(obs_mask, origin, voxel), box=(lo, hi), plane=plane)       # the DTU protocol: thin_points() and the filters
 """
 import math
 from types import SimpleNamespace
@@ -448,7 +450,8 @@ class PointGrid:
     limits raises ValueError, naming the smallest admissible value.  The result of nearest() does not depend on cell_size.
     One host sync: the read-back of the extrema (a second one when some point is not finite).  `points` itself is not kept."""
 
-    def __init__(self, points, max_distance, cell_size=None):
+    def __init__(self, points, max_distance, cell_size=None, _default_cell=None):
+        """_default_cell: the first guess thin_points() puts in place of the heuristic when cell_size is None; raised by the same rule."""
         points = _points_tensor(points, "PointGrid")
         max_distance = float(max_distance)
         if not (max_distance >= 0.0 and math.isfinite(max_distance) and math.isfinite(_f32(max_distance))):
@@ -464,7 +467,7 @@ class PointGrid:
         if cell_size is None:
             spans = [e for e in extent if e > 0.0]
             per_point = (math.prod(spans) / (4.0 * max(N, 1))) ** (1.0 / len(spans)) if spans else 0.0
-            cell_size = max(max_distance / 16.0, per_point)
+            cell_size = max(max_distance / 16.0, per_point) if _default_cell is None else float(_default_cell)
             if not (cell_size > 0.0 and math.isfinite(cell_size) and _f32(cell_size) > 0.0):
                 cell_size = 1.0
             while not admissible(cell_size):
@@ -562,3 +565,204 @@ def evaluate(mesh_or_points, reference_points, max_distance, threshold, density=
 def compare_meshes(a, b, max_distance, threshold, density, seed=0):
     """evaluate() of the surface samples of mesh `a` against those of mesh `b`, both at `density` with `seed`: what simplify() or clean() cost."""
     return evaluate(a, sample_surface(b, density, seed)[0], max_distance, threshold, density=density, seed=seed)
+
+
+# ---- the DTU protocol (csrc/mesh_eval.hip: thinning and culling; the filters are torch) -----------------------------------------------------------------
+THIN_GROUP = 4                # rounds per read-back of the undecided count (DESIGN.md, "DTU protocol")
+
+
+def _thin_shells(radius, cell_size, dims):
+    """R of include/envgs_mesh.h ("thinning"): the smallest integer with ((float)R * cell) * (1 - 2^-10) >= radius in fp32, clipped to the grid."""
+    radius, cell, last = _f32(radius), _f32(cell_size), max(dims) - 1
+    reach = lambda r: _f32(_f32(float(r) * cell) * 0.9990234375) >= radius       # a product of two fp32 numbers in double, rounded once, is the fp32 product
+    R = min(last, max(0, int(radius / cell) - 2))
+    while R < last and not reach(R):
+        R += 1
+    return R
+
+
+def _thin(points, radius, seed, cell_size, group, history):
+    points = _points_tensor(points, "thin_points")
+    radius = float(radius)
+    if not (radius >= 0.0 and math.isfinite(radius) and math.isfinite(_f32(radius))):
+        raise ValueError("thin_points: radius must be finite and not negative")
+    if seed is not None:
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 32:
+            raise ValueError("thin_points: seed must be in 0 .. 2^32 - 1, or None for the given order")
+    grid = PointGrid(points, radius, cell_size, _default_cell=radius * 1.002 if radius > 0.0 else None)
+    lib = _lib.load()
+    dev, N = points.device, points.shape[0]
+    (ox, oy, oz), (nx, ny, nz) = grid.origin, grid.dims
+    shells = _thin_shells(radius, grid.cell_size, grid.dims)
+    tb = lib.envgs_points_thin_temp_bytes(N)
+    temp = torch.empty(tb, dtype=torch.uint8, device=dev)
+    count = torch.empty(2, dtype=torch.int32, device=dev)
+    keep = torch.empty(N, dtype=torch.bool, device=dev)
+    p, s = _lib.ptr, _stream(dev)
+    _lib.check(lib.envgs_points_thin_begin(N, p(points), p(temp), tb, p(count), s), "envgs_points_thin_begin")
+    undecided, rounds, launched = N, 0, 0                         # N: the bound that needs no read-back
+    while undecided and launched < N + group:                     # every round decides a point: N rounds suffice, whatever the floats are
+        _lib.check(lib.envgs_points_thin_round(N, p(points), radius, int(seed is not None), seed or 0, ox, oy, oz, grid.cell_size, nx, ny, nz, shells,
+                                               p(grid.cell_end), p(grid.records), p(temp), tb, launched, group, undecided, p(count), s),
+                   "envgs_points_thin_round")
+        launched += group
+        undecided, rounds = count.tolist()
+        if history is not None:
+            history.append(undecided)
+    if undecided:
+        raise RuntimeError("thin_points: %d points undecided after %d rounds" % (undecided, launched))
+    _lib.check(lib.envgs_points_thin_keep(N, p(temp), tb, p(keep), s), "envgs_points_thin_keep")
+    return keep, rounds
+
+
+def thin_points(points, radius, seed=0, cell_size=None, return_rounds=False):
+    """The thinning step of the DTU evaluation (include/envgs_mesh.h, "thinning"): keep (N,) bool such that no two kept points are within `radius`
+    of each other (d2 <= radius^2 in fp32, inclusive) and every dropped finite point has a kept one within it -- exactly the set the DTU loop keeps
+    when it visits the points by ascending key: key(i) = hash(seed, i) for seed in 0 .. 2^32-1 (a strict order, the stand-in for the script's
+    shuffle), or the given order with seed=None.  Rows that are not finite are never kept.  radius: finite, >= 0 (0 removes exact duplicates); N
+    below 2^31.  points[keep] keeps the ascending original index: the canonical order.
+    The result depends on the points, the radius and the seed alone, never on cell_size (None: just above the radius, so that one shell of cells
+    around a point holds its neighbours; raised as PointGrid raises its own until the grid limits hold; an explicit value outside the limits raises
+    PointGrid's ValueError) and never on scheduling: two runs give identical bytes.
+    The device decides in rounds; a point waits for its lower-keyed neighbours.  The hash order needs about log N rounds.  Index order on spatially
+    sorted input (a scan line, a lattice) can need up to N rounds, one launch each: shuffle such input or give a seed.
+    -> keep, or (keep, rounds: the rounds that found work) with return_rounds.  Host syncs: the extrema read-back of the grid, plus one count
+    read-back per group of THIN_GROUP = 4 rounds."""
+    keep, rounds = _thin(points, radius, seed, cell_size, THIN_GROUP, None)
+    return (keep, rounds) if return_rounds else keep
+
+
+def cull_to_masks(mesh, cameras, masks, return_index=False):
+    """The cull_scan step of the 2DGS DTU evaluation: drops every vertex that some camera sees outside its object mask, and the faces that lose a
+    corner.  cameras: namespaces with K (3,3), R (3,3) world -> camera and T (3,) (synth.make_camera); masks: (n,H,W) bool or uint8 device tensor,
+    0 = outside.  A vertex is projected by the pixel rule of TSDFVolume.integrate, verbatim (include/envgs_mesh.h, "culling"); it passes a view iff
+    it is behind the camera (zc <= 0), or its pixel is outside the image, or the mask is set there; a vertex that is not finite fails.  The faces
+    whose three corners pass every view go through select_faces(), so the order is preserved and the vertices are compacted as clean() does.
+    To dilate the masks first, as the 2DGS script does: torch.nn.functional.max_pool2d(masks[:, None].float(), 2 * k + 1, 1, k)[:, 0] > 0.
+    -> Mesh, or (Mesh, vertex_index) with return_index.  Views go to the device 8 per launch.  One host sync: that of select_faces()."""
+    v, f, _ = _mesh_tensors(mesh, "cull_to_masks")
+    _need_gpu(masks, "cull_to_masks")
+    cameras = list(cameras)
+    if masks.dtype == torch.bool:
+        masks = masks.contiguous().view(torch.uint8)
+    if masks.dtype != torch.uint8 or masks.dim() != 3 or masks.shape[0] != len(cameras) or masks.device != v.device or (len(cameras) and masks[0].numel() == 0):
+        raise ValueError("cull_to_masks: masks must be a (n,H,W) bool or uint8 tensor on the mesh's device, one per camera")
+    masks = masks.contiguous()
+    lib = _lib.load()
+    dev, V, F = v.device, v.shape[0], f.shape[0]
+    vertex_keep = torch.empty(V, dtype=torch.uint8, device=dev)
+    face_keep = torch.empty(F, dtype=torch.uint8, device=dev)
+    p = _lib.ptr
+    for b0 in range(0, max(len(cameras), 1), MAX_VIEWS):
+        views = _lib.CullViews()
+        views.count = min(MAX_VIEWS, len(cameras) - b0)
+        for q in range(views.count):
+            cam, c = cameras[b0 + q], views.v[q]
+            k, r, t = _host(cam.K, (3, 3)), _host(cam.R, (3, 3)), _host(cam.T, (3,))
+            c.mask = masks[b0 + q].data_ptr()
+            c.H, c.W = masks.shape[1], masks.shape[2]
+            c.fx, c.fy, c.cx, c.cy = float(k[0, 0]), float(k[1, 1]), float(k[0, 2]), float(k[1, 2])
+            c.R = (_lib.ctypes.c_float * 9)(*[float(x) for x in r.reshape(-1)])
+            c.T = (_lib.ctypes.c_float * 3)(*[float(x) for x in t])
+        _lib.check(lib.envgs_mesh_cull_vertices(V, p(v), views, int(b0 > 0), p(vertex_keep), _stream(dev)), "envgs_mesh_cull_vertices")
+    _lib.check(lib.envgs_mesh_cull_faces(V, F, p(f), p(vertex_keep), p(face_keep), _stream(dev)), "envgs_mesh_cull_faces")
+    return select_faces(mesh, face_keep, return_index=return_index)
+
+
+def _triple(x, what):
+    x = [_f32(v) for v in x]
+    if len(x) != 3:
+        raise ValueError("%s: three numbers are required" % what)
+    return x
+
+
+def in_box(points, lo, hi):
+    """(N,) bool: lo <= p < hi on every axis (fp32 compares; a row that is not finite is False)."""
+    points = _points_tensor(points, "in_box")
+    lo = torch.tensor(_triple(lo, "in_box"), dtype=torch.float32, device=points.device)
+    hi = torch.tensor(_triple(hi, "in_box"), dtype=torch.float32, device=points.device)
+    return ((points >= lo) & (points < hi) & torch.isfinite(points)).all(dim=1)
+
+
+def in_volume(points, volume, origin, voxel_size):
+    """(N,) bool: the DTU observation mask.  volume: (nx,ny,nz) bool or uint8 device tensor indexed [gx, gy, gz]; g = rint((p - origin) / voxel_size)
+    per axis in fp32, ties to even (what np.around and torch.round both do); inside iff 0 <= g < dims on every axis and volume[g] != 0.  A row
+    that is not finite is False."""
+    points = _points_tensor(points, "in_volume")
+    _need_gpu(volume, "in_volume")
+    if volume.dim() != 3 or volume.dtype not in (torch.bool, torch.uint8) or volume.device != points.device:
+        raise ValueError("in_volume: volume must be a (nx,ny,nz) bool or uint8 tensor on the points' device")
+    voxel = _f32(voxel_size)
+    if not (voxel > 0.0 and math.isfinite(voxel)):
+        raise ValueError("in_volume: voxel_size must be positive and finite")
+    o = torch.tensor(_triple(origin, "in_volume"), dtype=torch.float32, device=points.device)
+    dims = torch.tensor(list(volume.shape), dtype=torch.float32, device=points.device)
+    # the divisor is a device tensor: torch turns a division by a host scalar into a product with its reciprocal, which rounds differently
+    g = torch.round((points - o) / torch.full((1,), voxel, dtype=torch.float32, device=points.device))
+    ok = ((g >= 0) & (g < dims) & torch.isfinite(points)).all(dim=1)          # decided on the floats, before any conversion
+    gi = torch.where(ok[:, None], g, torch.zeros((), dtype=torch.float32, device=points.device)).long()
+    return ok & (volume[gi[:, 0], gi[:, 1], gi[:, 2]] != 0)
+
+
+def above_plane(points, plane):
+    """(N,) bool: ((a x + b y) + c z) + d > 0 for plane = (a, b, c, d), every product and sum a separate fp32 operation.  A row that is not finite
+    is False."""
+    points = _points_tensor(points, "above_plane")
+    plane = [_f32(v) for v in plane]
+    if len(plane) != 4:
+        raise ValueError("above_plane: plane must be (a, b, c, d)")
+    a, b, c, d = plane
+    s = points[:, 0] * a
+    s = s + points[:, 1] * b
+    s = s + points[:, 2] * c
+    s = s + d
+    return (s > 0) & torch.isfinite(points).all(dim=1)
+
+
+def evaluate_dtu(mesh_or_points, scan_points, radius, max_distance, density=None, seed=0, observed=None, box=None, plane=None, threshold=None):
+    """The DTU evaluation protocol on the device.  The prediction -- a Mesh sampled at `density`, or a (N,3) point tensor -- is thinned at `radius`
+    with `seed` (thin_points), then filtered:
+      data_in   the thinned points inside box = (lo, hi) (in_box);   data_obs  those of data_in inside observed = (volume, origin, voxel_size) (in_volume)
+      accuracy      mean nearest distance from data_obs to ALL scan points, over the points found within max_distance
+      completeness  the same from the scan points above plane = (a, b, c, d) (above_plane) to data_in;   chamfer  the mean of the two
+    A filter that is None is skipped.  Also returned: the counts n_samples (before thinning), n_thinned, n_in, n_pred (data_obs), n_scan, n_ref (scan
+    above the plane), found_pred, found_ref, thin_rounds, and the distances d_pred (n_pred,), d_ref (n_ref,) as evaluate() gives them.  With
+    `threshold` (<= max_distance): within_pred, within_ref, precision, recall and fscore over the same two sets, by evaluate()'s rules.
+    seed=None thins in the given order (a mesh is then sampled with seed 0).
+    Stated deviations from the DTU script: random area-proportional surface samples in place of its per-triangle lattice plus the vertices;
+    d <= max_distance where the script has <; a hash order in place of NumPy's shuffle.  The scan is taken as given (the DTU scans are thinned
+    already); thin it with thin_points() if it is not."""
+    max_distance = float(max_distance)
+    if threshold is not None:
+        threshold = float(threshold)
+        if not 0.0 <= threshold <= max_distance:
+            raise ValueError("evaluate_dtu: 0 <= threshold <= max_distance is required")
+    pred = _eval_points(mesh_or_points, density, 0 if seed is None else seed, "evaluate_dtu")
+    scan = _points_tensor(scan_points, "evaluate_dtu")
+    if pred.device != scan.device:
+        raise ValueError("evaluate_dtu: the prediction and the scan must be on one device")
+    keep, rounds = _thin(pred, radius, seed, None, THIN_GROUP, None)
+    thinned = pred[keep]
+    data_in = thinned if box is None else thinned[in_box(thinned, box[0], box[1])]
+    data_obs = data_in if observed is None else data_in[in_volume(data_in, observed[0], observed[1], observed[2])]
+    ref = scan if plane is None else scan[above_plane(scan, plane)]
+    d_pred = torch.sqrt(PointGrid(scan, max_distance).nearest(data_obs.contiguous())[0].double())
+    d_ref = torch.sqrt(PointGrid(data_in.contiguous(), max_distance).nearest(ref.contiguous())[0].double())
+    rows = []
+    for d in (d_pred, d_ref):
+        found = torch.isfinite(d)
+        rows += [torch.where(found, d, torch.zeros((), dtype=torch.float64, device=d.device)).sum(), found.sum().double(),
+                 (d <= (max_distance if threshold is None else threshold)).sum().double()]
+    sum_p, found_p, within_p, sum_r, found_r, within_r = torch.stack(rows).tolist()
+    accuracy = sum_p / found_p if found_p else float("nan")
+    completeness = sum_r / found_r if found_r else float("nan")
+    out = SimpleNamespace(accuracy=accuracy, completeness=completeness, chamfer=0.5 * (accuracy + completeness), n_samples=pred.shape[0],
+                          n_thinned=thinned.shape[0], n_in=data_in.shape[0], n_pred=data_obs.shape[0], n_scan=scan.shape[0], n_ref=ref.shape[0],
+                          found_pred=int(found_p), found_ref=int(found_r), thin_rounds=rounds, d_pred=d_pred, d_ref=d_ref)
+    if threshold is not None:
+        out.precision = within_p / out.n_pred if out.n_pred else 0.0
+        out.recall = within_r / out.n_ref if out.n_ref else 0.0
+        out.fscore = 2.0 * out.precision * out.recall / (out.precision + out.recall) if out.precision + out.recall > 0.0 else 0.0
+        out.within_pred, out.within_ref = int(within_p), int(within_r)
+    return out

@@ -241,6 +241,86 @@ ENVGS_API int envgs_points_grid_build(uint32_t N, const float *points, float ox,
 ENVGS_API int envgs_points_nearest(uint32_t Q, const float *queries, float max_distance, float ox, float oy, float oz, float cell, int32_t nx, int32_t ny,
                                    int32_t nz, const uint32_t *cell_end, const float *records, float *dist2, int32_t *index, void *stream);
 
+/* ---- thinning: no two kept points within a radius, by the sequential rule of the DTU evaluation (csrc/mesh_eval.hip) -------------------------------
+ * PARITY UNPINNED.  tests/mesh_thin_oracle.py restates what follows in NumPy.  fp32, left to right, no FMA.
+ *
+ * For the points p_0 .. p_{N-1} (N below 2^31) and a finite radius >= 0:
+ *      d2(i, j) = ((dx*dx) + (dy*dy)) + (dz*dz), d = p_i - p_j;   r2 = radius * radius
+ *    i and j are NEIGHBOURS iff the coordinates of both are finite, i != j and d2 <= r2.  The bound is inclusive; duplicates are neighbours, and
+ *    radius = 0 removes exact duplicates only (a d2 of 0 between different positions can arise only where a product underflows, at differences
+ *    below 2^-74; the shell bound below, like that of the nearest-point search, supposes no such underflow).
+ *      hashed:      key(i) = h(seed, i, 0xFFFFFFFE)   (the counter hash above).  mix is a bijection of uint32 and so is xor with a constant, so for a
+ *                   fixed seed i -> key(i) is a permutation: the keys are distinct and their order is strict without a tie-break
+ *      not hashed:  key(i) = i, the given order
+ *    The points are visited by ascending key.  A finite point is KEPT iff no kept neighbour has a smaller key; a point that is not finite is never
+ *    kept and is nobody's neighbour.  That is the loop of the DTU script ("a point that is still alive is kept and kills everything within the
+ *    radius") on the array permuted by key: the lexicographically first maximal independent set of the neighbour graph.  `keep` is a function of
+ *    the points, the radius and the keys alone: it depends on no cell size, no scheduling and no number of rounds.
+ *
+ * Device form.  One uint32 state per point: UNDECIDED, KEPT or DROPPED; the points that are not finite start DROPPED.  A round gives a lane to
+ * every undecided point i.  The lane walks the cells of shells 0 .. R around i's cell (the grid and the cell rule of the nearest-point search) and
+ * considers every record j with d2 <= r2, j != i and key(j) < key(i), the key recomputed from the index in the record: a KEPT j makes i DROPPED
+ * and ends the walk; an UNDECIDED j makes i blocked; a lane that is neither becomes KEPT.  The blocked points form the next round's worklist
+ * (two buffers in turn, one integer atomic per wavefront; its order is free, since no result depends on it).
+ *
+ * Why a lane may read states that other lanes write in the same launch.  A state only ever moves from UNDECIDED to a final value, and a final
+ * value is correct at the moment it is written: i is DROPPED only on seeing a lower-keyed neighbour KEPT, which stays so; i is KEPT only after seeing
+ * every lower-keyed neighbour DROPPED, which stays so.  Whatever a lane reads is therefore either final and true, or UNDECIDED -- possibly stale --
+ * which blocks it and costs a round, never a result.  Every round decides at least the undecided point of smallest key (all its lower-keyed
+ * neighbours are final), so N rounds always suffice: the host loop is bounded by that integer and compares no float.  No lane waits inside a
+ * kernel for another lane or workgroup; progress comes only from launching the next round.
+ *
+ * R, computed once by the caller in fp32, is the smallest integer with ((float)R * cell) * (1 - 2^-10) >= radius, clipped to the last shell that
+ * can hold a cell of the grid (max(nx, ny, nz) - 1).  The expression is the b of the nearest-point search, whose proof gives: every point outside
+ * shells 0 .. R has d2 > b*b >= r2, so it is no neighbour.  (radius = 0 gives R = 0: equal positions share a cell.)
+ *
+ * Scratch: state (N u32) | worklist (N u32) | worklist (N u32) | 4 counters, each part rounded up to 256 B.  `count` (2 u32, on the device):
+ * count[0] = the undecided points left, count[1] = the rounds so far that found an undecided point. */
+
+/* Scratch bytes of the three calls below (0 if N is 2^31 or more). */
+ENVGS_API size_t envgs_points_thin_temp_bytes(uint32_t N);
+
+/* Builds the states and the first worklist (the finite points) in `temp`, which carries them to the calls below, and reports into `count`. */
+ENVGS_API int envgs_points_thin_begin(uint32_t N, const float *points, void *temp, size_t temp_bytes, uint32_t *count, void *stream);
+
+/* Runs rounds first_round .. first_round + rounds - 1 (first_round counts every round launched since envgs_points_thin_begin, from 0) over a grid
+ * built by envgs_points_grid_build on the same points, and reports into `count`.  `undecided` sizes the launches: the caller's latest read-back of
+ * count[0] (or N before any); with 0 nothing is launched.  hashed != 0: the hash keys of `seed`; 0: index order.  `shells` is R above, 0 .. 1023.
+ * Bad arguments as for envgs_points_nearest, plus a `temp` that is NULL or not 16-byte aligned. */
+ENVGS_API int envgs_points_thin_round(uint32_t N, const float *points, float radius, int32_t hashed, uint32_t seed, float ox, float oy, float oz, float cell,
+                                      int32_t nx, int32_t ny, int32_t nz, int32_t shells, const uint32_t *cell_end, const float *records, void *temp,
+                                      size_t temp_bytes, uint32_t first_round, uint32_t rounds, uint32_t undecided, uint32_t *count, void *stream);
+
+/* keep (N) uint8: 1 = kept.  To be called once count[0] is 0; a point still undecided is written as 0. */
+ENVGS_API int envgs_points_thin_keep(uint32_t N, const void *temp, size_t temp_bytes, uint8_t *keep, void *stream);
+
+/* ---- culling: the vertices some camera sees outside its mask (csrc/mesh_eval.hip) -------------------------------------------------------------------
+ * A vertex is projected into a view BY THE PIXEL RULE OF envgs_tsdf_integrate (fp32, left to right, no FMA, IEEE division):
+ *      xc = R00 x + R01 y + R02 z + T0 (yc, zc likewise);   u = fx (xc / zc) + cx,  v = fy (yc / zc) + cy;   px = floor(u),  py = floor(v)
+ * It PASSES the view iff zc <= 0, or the pixel is outside the image, or mask[py][px] != 0.  A vertex is kept iff its three coordinates are finite
+ * and it passes every view; a face is kept iff its three indices are in range and its three corners are kept.  So a mesh fused under masks and
+ * culled under the same masks is treated by one rule. */
+typedef struct envgs_cull_view {
+    const uint8_t *mask;                      /* (H,W); 0 = outside the object */
+    int32_t H, W;
+    float fx, fy, cx, cy;
+    float R[9];                               /* world -> camera, row major */
+    float T[3];
+} envgs_cull_view;
+
+typedef struct envgs_cull_views {
+    int32_t count;                            /* 0 .. ENVGS_TSDF_MAX_VIEWS */
+    int32_t reserved0;
+    envgs_cull_view v[ENVGS_TSDF_MAX_VIEWS];
+} envgs_cull_views;
+
+/* keep (V) uint8.  accumulate = 0: keep[v] = finite and passes every view given; != 0: the same AND the keep[v] already there, so that more than
+ * ENVGS_TSDF_MAX_VIEWS views take several calls.  V at or above 2^31, a count outside 0 .. 8, a NULL mask or an empty image: ENVGS_ERR_BAD_ARG. */
+ENVGS_API int envgs_mesh_cull_vertices(uint32_t V, const float *vertices, const envgs_cull_views *views, int32_t accumulate, uint8_t *keep, void *stream);
+
+/* face_keep (F) uint8 from vertex_keep (V): the input of envgs_mesh_select_count / _emit.  An index outside [0, V) is never dereferenced. */
+ENVGS_API int envgs_mesh_cull_faces(uint32_t V, uint32_t F, const int32_t *faces, const uint8_t *vertex_keep, uint8_t *face_keep, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
