@@ -38,6 +38,28 @@ __device__ __forceinline__ V3 unit_adjoint(V3 x, float r, float inv, V3 gy)
     return V3{gy.x * inv - x.x * k, gy.y * inv - x.y * k, gy.z * inv - x.z * k};
 }
 
+// d norm_loss / d norm_map on a pixel with norm_map == 0, in double.  There a = 0, so sign(a - g) = -sign(g) and d cos / d a = gn / eps, and both
+// unit() adjoints at 0 are gy / eps: the row is (R^T (-sign(g) - gn / eps)) * k / eps^2, about 1e24 k.  Float operands carry their half ulp each
+// into the three-term sum R^T gb, and where its terms cancel (a gradient nearly orthogonal to a world axis) the element keeps few digits; with the
+// chain in double the result is the float64 statement rounded once.  k = scale * weight / N.
+__device__ __forceinline__ V3 zero_normal_adjoint(V3 p, const float *R, double k)
+{
+    constexpr double eps = 1e-8, inv = 1e8;       // 1 / (0 + eps) and 1 / max(0, eps)
+    const double t[3] = {2.0 * (double)p.x - 1.0, 2.0 * (double)p.y - 1.0, 2.0 * (double)p.z - 1.0};
+    const double it = 1.0 / (sqrt(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]) + eps);
+    const double g[3] = {t[0] * it, t[1] * it, t[2] * it};
+    const double ing = 1.0 / fmax(sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]), eps);
+    double gb[3];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const double sg = g[c] > 0. ? 1. : (g[c] < 0. ? -1. : 0.);
+        gb[c] = (-sg - g[c] * ing * inv) * k * inv;
+    }
+    return V3{(float)(((double)R[0] * gb[0] + (double)R[3] * gb[1] + (double)R[6] * gb[2]) * inv),
+              (float)(((double)R[1] * gb[0] + (double)R[4] * gb[1] + (double)R[7] * gb[2]) * inv),
+              (float)(((double)R[2] * gb[0] + (double)R[5] * gb[1] + (double)R[8] * gb[2]) * inv)};
+}
+
 __global__ void __launch_bounds__(SUP_THREADS)
 supervisor_fwd(const envgs_supervisor_args A, const int pixel_blocks)
 {
@@ -73,7 +95,15 @@ supervisor_fwd(const envgs_supervisor_args A, const int pixel_blocks)
                 const float agn = dot3(a, gn), c = agn * ina;
                 const float s = sd_select(F, ENVGS_SUP_F_NORM_ACC, ENVGS_SUP_F_NORM_DPT, acc, sd);
                 v[ENVGS_SUP_NORM] = s * (fabsf(a.x - g.x) + fabsf(a.y - g.y) + fabsf(a.z - g.z) + 1.0f - c);
-                if (A.g_norm_map) {
+                if (A.g_norm_map && r0 == 0.f) {
+                    // background: the 1e24-fold amplified row, its scale included, in double
+                    double sc = (F & ENVGS_SUP_F_NORM_ACC) ? (double)acc : 1.0;
+                    if (F & ENVGS_SUP_F_NORM_DPT) {
+                        const double near = (double)A.near_far[0], far = (double)A.near_far[1];
+                        sc *= fmin(fmax(1.0 - ((double)A.dpt_map[i * A.dpt_map_row] - near) / (far - near), 0.0), 1.0);
+                    }
+                    gx = zero_normal_adjoint(p, R, sc * (double)A.weight[ENVGS_SUP_NORM] / (double)A.N);
+                } else if (A.g_norm_map) {
                     // d cos / d a = gn / na - a/|a| * <a, gn> / na^2 (the clamp in na = max(|a|, eps) is a constant)
                     const float k = s * A.weight[ENVGS_SUP_NORM] * inv_n, q = ra > 0.f ? agn * ina * ina / ra : 0.f;
                     const V3 ga{(sign_of(a.x - g.x) - (gn.x * ina - a.x * q)) * k, (sign_of(a.y - g.y) - (gn.y * ina - a.y * q)) * k,

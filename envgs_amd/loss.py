@@ -149,7 +149,11 @@ class EnvGSGeometryLoss:
     (3,H,W) planes are read in place.  A term whose keys are missing, whose weight is 0 or whose [start_iter, until_iter) window does not hold
     `iter` is skipped, as in the reference.  Returns the weighted sum as a device scalar and a dict of device scalars named like the reference's
     scalar_stats.  Gradients flow to norm_map, surf_norm_map, dist_map, env_opacity and (from msk_loss only) acc_map; dpt_map and acc_map as
-    scales are constants.  One view per call; no host synchronisation anywhere."""
+    scales are constants.  One view per call; no host synchronisation anywhere.
+
+    One deliberate deviation from the reference: when the two depth percentiles coincide (more than 99 % of dpt_map holds one value, far == near)
+    the reference's normalize_depth divides 0 by 0 and its loss is NaN.  Here the depth scale is then 0 where d == near, 0 where d > near and 1
+    where d < near, and the loss and every gradient stay finite (tests/test_supervisor_shapes_gpu.py pins it)."""
 
     def __init__(self, norm_loss_weight=0.0, norm_loss_start_iter=7000, norm_loss_until_iter=None, use_acc_scale_norm_loss=False,
                  use_dpt_scale_norm_loss=False, gs_norm_loss_weight=0.0, gs_dist_loss_weight=0.0, gs_norm_loss_start_iter=7000,

@@ -11,6 +11,9 @@
  * s is 1, acc, the depth scale, or their product (per term, by flag); both are constants for the gradient.  The depth scale is
  * clip(1 - (d - near) / (far - near), 0, 1) with near / far the n-th smallest / largest depth, n = int(0.01 N) (depth_utils.py:65-71): exact
  * order statistics, found on the device by a radix select and read from a device buffer, so that nothing returns to the host.
+ * When the two percentiles coincide (far == near: more than 99 % of the depths hold one value) the formula is 0 / 0 at every pixel with
+ * d == near, and the reference's loss is NaN.  Here, deliberately, the scale is then 0 where d == near, 0 where d > near and 1 where d < near
+ * (the clip is fminf(fmaxf(x, 0), 1), which returns its other operand for a NaN), and every output stays finite.
  *
  * Every tensor is addressed as base + row * row_stride (+ channel * channel_stride), strides in ELEMENTS, so channel-last maps and (3, H, W)
  * planes are both read in place.  Outputs are contiguous.

@@ -6,7 +6,7 @@ compute_loss is called UNBOUND on a types.SimpleNamespace that carries the optio
 config; compute_loss reads nothing but those fields).  The imports need the stand-ins tests/golden/make_sampler_golden.py installs, plus
 torchvision.models / torchvision.models.vgg (the perceptual loss of loss_utils, never called here).
 
-One set of inputs (H x W = 48 x 64 pixels, n = int(0.01 N) = 30, P = 1000 environment opacities), four option sets:
+One set of inputs (by default H x W = 48 x 64 pixels, n = int(0.01 N) = 30, P = 1000 environment opacities), four option sets:
   a  configs/models/envgs.yaml       : norm_loss 0.01 + gs_norm_loss 0.04, both scaled by the normalised depth, windows open from iteration 0
   b  configs/models/envgs_synth.yaml : the same two terms scaled by acc_map, windows open from iteration 4000
   c  all five terms, both scales on both normal terms, 'l1' environment opacity
@@ -17,7 +17,9 @@ depth percentiles.  Per case the file holds the five scalar_stats, the loss, the
 norm_map == 0, where two `x / (|x| + 1e-8)` and one cosine clamp amplify the gradient by 1e8 each -- the elementwise relative error of the
 reference's own FLOAT32 run against its float64 run (the noise floor the GPU test scales its bound from).
 Adaptation: loss_utils.mse casts its operands with .float(); during the float64 run Tensor.float casts to float64 instead, so that msk_loss is float64 too.
-The fixture is DATA.  Re-run: python tests/golden/make_supervisor_golden.py"""
+The fixture is DATA.  Re-run: python tests/golden/make_supervisor_golden.py
+A second fixture at a size that is no multiple of the kernel's workgroup (11 x 29 = 319 pixels, n = 3, P = 257, cases a and c; the planted blocks
+keep their share of the pixels):  python tests/golden/make_supervisor_golden.py 11 29 257 supervisor_golden_ragged.npz a,c"""
 import os
 import sys
 import types
@@ -32,7 +34,6 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 
 H, W, P = 48, 64, 1000
-N = H * W
 
 # every option field compute_loss reads, at the constructor's defaults
 DEFAULTS = dict(
@@ -60,25 +61,28 @@ GRAD_KEYS = ("norm_map", "surf_norm_map", "acc_map", "dist_map", "env_opacity")
 STAT_KEYS = ("env_opacity_loss", "norm_loss", "gs_norm_loss", "msk_loss", "gs_dist_loss")
 
 
-def make_inputs():
+def make_inputs(H=H, W=W, P=P):
+    """The planted blocks are stated for the default N = 3072 and keep their share of the pixels at any other N (at = the identity at 3072)."""
+    N = H * W
+    at = lambda i: i * N // 3072
     g = torch.Generator().manual_seed(20240607)
     r = lambda *s: torch.rand(*s, generator=g, dtype=torch.float32)
     rn = lambda *s: torch.randn(*s, generator=g, dtype=torch.float32)
     unit = lambda v: v / v.norm(dim=-1, keepdim=True)
     norm_map = unit(rn(N, 3)) * (0.3 + 0.7 * r(N, 1))                    # rendered normals: alpha-weighted, so shorter than 1
-    norm_map[0:200] = 0.0                                                # background: no contributing surfel
+    norm_map[at(0):at(200)] = 0.0                                       # background: no contributing surfel
     surf_norm_map = unit(rn(N, 3)) * (0.3 + 0.7 * r(N, 1))
-    surf_norm_map[100:260] = 0.0
+    surf_norm_map[at(100):at(260)] = 0.0
     prior = unit(rn(N, 3)) * 0.5 + 0.5                                   # how normals are stored on disk
-    prior[150:350] = 0.5                                                 # a zero prior
-    prior[350:380] = 0.5 + 0.1 * rn(30, 3)                               # short priors
-    prior[380:420] = 0.1 * r(40, 3)                                      # |batch.norm| below the mask's 0.25
+    prior[at(150):at(350)] = 0.5                                        # a zero prior
+    prior[at(350):at(380)] = 0.5 + 0.1 * rn(at(380) - at(350), 3)       # short priors
+    prior[at(380):at(420)] = 0.1 * r(at(420) - at(380), 3)              # |batch.norm| below the mask's 0.25
     acc = r(N, 1)
-    acc[0:100] = 0.0                                                     # half of the background block; the other half keeps the acc-scaled terms alive there
+    acc[at(0):at(100)] = 0.0                                            # half of the background block; the other half keeps the acc-scaled terms alive there
     msk = (r(N, 1) > 0.3).float()
-    msk[500:520] = 0.5                                                   # not > 0.5
+    msk[at(500):at(520)] = 0.5                                          # not > 0.5
     dpt = 1.0 + 5.0 * r(N, 1)
-    dpt[300:320] = 0.0                                                   # 20 zeros: fewer than n, so the low percentile is a positive depth
+    dpt[at(300):at(320)] = 0.0                                          # 20 zeros: fewer than n, so the low percentile is a positive depth
     n = int(N * 0.01)
     order = torch.argsort(dpt[:, 0])
     dpt[order[n - 3:n + 3], 0] = dpt[order[n - 1], 0].clone()            # ties straddling the n-th smallest ...
@@ -128,7 +132,7 @@ def run_reference(compute_loss, dotdict, inputs, opts, it, dtype):
     return loss.detach(), {k: v.detach() for k, v in stats.items()}, grads
 
 
-def main():
+def main(H=H, W=W, P=P, name="supervisor_golden.npz", tags=tuple(CASES)):
     _install_mocks()
     sys.path.insert(0, "/root/reference")
     sys.argv = ["evc"]
@@ -137,11 +141,12 @@ def main():
     from easyvolcap.models.supervisors.envgs_supervisor import EnvGSSupervisor
     compute_loss = EnvGSSupervisor.compute_loss
 
-    inputs = make_inputs()
+    inputs = make_inputs(H, W, P)
     out = {"in_" + k: v.numpy() for k, v in inputs.items()}
     out["H"], out["W"], out["P"] = np.int64(H), np.int64(W), np.int64(P)
     zero = (inputs["norm_map"][0] == 0).all(dim=-1).numpy()
-    for tag, (opts, it) in CASES.items():
+    for tag in tags:
+        opts, it = CASES[tag]
         loss, stats, grads = run_reference(compute_loss, dotdict, inputs, opts, it, torch.float64)
         loss32, _, grads32 = run_reference(compute_loss, dotdict, inputs, opts, it, torch.float32)
         out["iter_" + tag] = np.int64(it)
@@ -169,10 +174,13 @@ def main():
         out["f32_noise_zero_normal_" + tag] = np.float64(noise)
         print("case %s iter %d: loss %.12g (float32 run: %.9g)  stats %s  gradients %s" % (
             tag, it, float(loss), float(loss32), {k: float(v) for k, v in stats.items()}, [k for k in GRAD_KEYS if grads[k] is not None]))
-    path = os.path.join(HERE, "supervisor_golden.npz")
+    path = os.path.join(HERE, name)
     np.savez_compressed(path, **out)
     print("fixture bytes:", os.path.getsize(path))
 
 
 if __name__ == "__main__":
-    main()
+    if len(sys.argv) > 1:
+        main(int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3]), sys.argv[4], tuple(sys.argv[5].split(",")) if len(sys.argv) > 5 else tuple(CASES))
+    else:
+        main()

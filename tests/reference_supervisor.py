@@ -35,10 +35,10 @@ def percentiles(d, p=0.01):
     return s[n - 1], s[d.size - n]
 
 
-def depth_scale(d, near=None, far=None):
+def depth_scale(d, near=None, far=None, dtype=np.float64):
     if near is None:
         near, far = percentiles(d)
-    d = np.asarray(d, np.float64)
+    d = np.asarray(d, dtype)
     return np.clip(1.0 - (d - float(near)) / (float(far) - float(near)), 0.0, 1.0)
 
 
@@ -58,10 +58,13 @@ def _window(it, start, until):
     return it >= start and (until is None or it < until)
 
 
-def geometry_loss(inp, opts, it):
-    """-> (loss, stats: dict name -> float, grads: dict input name -> array), everything float64."""
+def geometry_loss(inp, opts, it, dtype=np.float64, dpt_scale=None):
+    """-> (loss, stats: dict name -> float, grads: dict input name -> array), everything in `dtype` (float64: the checker; float32: the same
+    statement at the device's precision, which measures how much of a bound the arithmetic itself uses up).  The decisions (order statistics, the
+    pass-through interval of the opacity clamp against its double bounds) are taken on the values as given, whatever `dtype` is.
+    dpt_scale: (N,) values used IN PLACE of the depth scale (the case far == near, where the formula is 0 / 0)."""
     o = dict(DEFAULTS, **opts)
-    f = lambda k: None if inp.get(k) is None else np.asarray(inp[k], np.float64)
+    f = lambda k: None if inp.get(k) is None else np.asarray(inp[k], dtype)
     nm, sn, acc, dpt, dist, env, prior, msk, R = (f(k) for k in ("norm_map", "surf_norm_map", "acc_map", "dpt_map", "dist_map", "env_opacity", "norm", "msk", "R"))
     loss, stats, grads = 0.0, {}, {}
 
@@ -69,11 +72,12 @@ def geometry_loss(inp, opts, it):
         grads[name] = grads.get(name, 0.0) + g
 
     def scale(use_acc, use_dpt):
-        s = np.ones(nm.shape[0])
+        s = np.ones(nm.shape[0], dtype)
         if use_acc:
             s = s * acc
         if use_dpt:
-            s = s * depth_scale(dpt, *percentiles(inp["dpt_map"]))            # order statistics of the values as given (their own dtype)
+            # order statistics of the values as given (their own dtype)
+            s = s * (depth_scale(dpt, *percentiles(inp["dpt_map"]), dtype=dtype) if dpt_scale is None else np.asarray(dpt_scale, dtype))
         return s
 
     if env is not None and o["env_opacity_loss_weight"] > 0 and it >= o["env_opacity_loss_start_iter"]:
@@ -82,7 +86,8 @@ def geometry_loss(inp, opts, it):
             lo, hi = 1e-3, 1 - 1e-3
             v = np.clip(env, lo, hi)
             stats["env_opacity_loss"] = (np.log(v) + np.log(1 - v)).mean()
-            add("env_opacity", w * np.where((env >= lo) & (env <= hi), 1 / v - 1 / (1 - v), 0.0))
+            given = np.asarray(inp["env_opacity"], np.float64)             # (float32(0.999) lies above 0.999, float32(0.001) above 0.001)
+            add("env_opacity", w * np.where((given >= lo) & (given <= hi), 1 / v - 1 / (1 - v), 0.0))
         elif o["env_opacity_loss_type"] == "l1":
             stats["env_opacity_loss"] = np.abs(1 - env).mean()
             add("env_opacity", -w * np.sign(1 - env))
@@ -119,7 +124,7 @@ def geometry_loss(inp, opts, it):
         add("surf_norm_map", -w * nm)
 
     if acc is not None and o["msk_loss_weight"] > 0 and _window(it, o["msk_loss_start_iter"], o["msk_loss_until_iter"]):
-        m = ((msk > 0.5) & (np.sqrt((prior * prior).sum(-1)) > 0.25)).astype(np.float64)
+        m = ((msk > 0.5) & (np.sqrt((prior * prior).sum(-1)) > 0.25)).astype(dtype)
         stats["msk_loss"] = ((acc - m) ** 2).mean()
         loss += o["msk_loss_weight"] * stats["msk_loss"]
         add("acc_map", 2 * (acc - m) * o["msk_loss_weight"] / acc.size)
@@ -127,6 +132,6 @@ def geometry_loss(inp, opts, it):
     if dist is not None and o["gs_dist_loss_weight"] > 0 and _window(it, o["gs_dist_loss_start_iter"], o["gs_dist_loss_until_iter"]):
         stats["gs_dist_loss"] = dist.mean()
         loss += o["gs_dist_loss_weight"] * stats["gs_dist_loss"]
-        add("dist_map", np.full(dist.shape, o["gs_dist_loss_weight"] / dist.size))
+        add("dist_map", np.full(dist.shape, o["gs_dist_loss_weight"] / dist.size, dtype))
 
     return loss, stats, grads

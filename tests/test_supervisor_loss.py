@@ -1,7 +1,8 @@
 """Geometry regularisers of the EnvGS supervisor (include/envgs_supervisor.h, envgs_amd.loss.EnvGSGeometryLoss).
 
-CPU: the float64 twin (tests/reference_supervisor.py) against the reference's own outputs (tests/golden/supervisor_golden.npz, written by
-tests/golden/make_supervisor_golden.py), its percentile routine against np.partition, argument rejection of the C-ABI and of the front-end.
+CPU: the float64 twin (tests/reference_supervisor.py) against the reference's own outputs (tests/golden/supervisor_golden.npz and, at a pixel
+count that is no multiple of the kernel's workgroup, supervisor_golden_ragged.npz; both written by tests/golden/make_supervisor_golden.py), its
+percentile routine against np.partition, argument rejection of the C-ABI and of the front-end.
 GPU: exact percentiles, the fixture cases, full-size option combinations and layouts against the twin, composition with the image loss
 through the base pass, and the absence of host synchronisation.
 
@@ -22,13 +23,16 @@ import torch
 from tests import reference_supervisor as twin
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "supervisor_golden.npz")
+RAGGED = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "supervisor_golden_ragged.npz")     # 11 x 29 pixels (n = 3), P = 257
+# (fixture, case): the 48 x 64 fixture keeps its test ids
+FIXTURE_CASES = [pytest.param(GOLD, t, id=t) for t in "abcd"] + [pytest.param(RAGGED, t, id="ragged-" + t) for t in "ac"]
 GRAD_KEYS = ("norm_map", "surf_norm_map", "acc_map", "dist_map", "env_opacity")
 ENVGS_YAML = dict(gs_norm_loss_weight=0.04, gs_norm_loss_start_iter=0, use_dpt_scale_gs_norm_loss=True, norm_loss_weight=0.01, norm_loss_start_iter=0,
                   use_dpt_scale_norm_loss=True)
 
 
-def _fixture():
-    z = np.load(GOLD)
+def _fixture(path=GOLD):
+    z = np.load(path)
     inp = {k[3:]: z[k] for k in z.files if k.startswith("in_")}
     return z, inp
 
@@ -52,9 +56,9 @@ def _case(z, tag):
 
 
 # ---------------------------------------------------------------- CPU ----------------------------------------------------------------------
-@pytest.mark.parametrize("tag", ["a", "b", "c", "d"])
-def test_twin_matches_reference_golden(tag):
-    z, inp = _fixture()
+@pytest.mark.parametrize("path,tag", FIXTURE_CASES)
+def test_twin_matches_reference_golden(path, tag):
+    z, inp = _fixture(path)
     opts, it = _case(z, tag)
     loss, stats, grads = twin.geometry_loss(_flat(inp), opts, it)
     assert abs(loss - float(z["loss_" + tag])) < 1e-12
@@ -188,7 +192,9 @@ def _to_dev(inp, dev, grad=True):
 
 
 def _check_grads(got, ref, zero, noise=None, tol=1e-4, what=""):
-    """got / ref: dict name -> (N,C) or (N,) arrays; zero: (N,) bool, the pixels with norm_map == 0."""
+    """got / ref: dict name -> (N,C) or (N,) arrays; zero: (N,) bool, the pixels with norm_map == 0.  Every comparison is measured and printed
+    before the first one beyond its bound fails the test."""
+    beyond = []
     for k, r in ref.items():
         g = got[k]
         assert g is not None, k
@@ -210,9 +216,11 @@ def _check_grads(got, ref, zero, noise=None, tol=1e-4, what=""):
                 el = (np.abs(gg[nz] - rr[nz]) / np.abs(rr[nz])).max()
                 print("%s d %-14s %-14s elementwise rel %.3e (reference float32 noise %.3e)" % (what, k, name, el, noise))
                 assert (gg[~nz] == 0).all()
-                assert el <= 4.0 * noise, (k, name, el, noise)
-            else:
-                assert err < tol, (k, name, err)
+                if not el <= 4.0 * noise:
+                    beyond.append((k, name, el, noise))
+            elif not err < tol:
+                beyond.append((k, name, err))
+    assert not beyond, beyond
 
 
 @pytest.mark.gpu
@@ -238,10 +246,14 @@ def test_device_percentiles_are_bit_exact(N):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("tag", ["a", "b", "c", "d"])
-def test_fused_geometry_loss_matches_golden(tag):
+@pytest.mark.parametrize("path,tag", FIXTURE_CASES)
+def test_fused_geometry_loss_matches_golden(path, tag):
+    """The fixture cases on the device.  On the pixels with norm_map == 0 the bound is 4 x the reference's own float32 deviation, elementwise; on
+    the 11 x 29 fixture (45 non-zero elements there) that is 4 x 1.259e-06 for case a, and the element at row 1, x (-6.0e16 in a row of magnitude
+    2.9e19: R^T gb cancels 480-fold) comes out 1.148e-05 off under plain float32 arithmetic, the float32 twin's included.  The kernel evaluates
+    those rows in double (supervisor.hip:zero_normal_adjoint) and meets the bound."""
     from envgs_amd.loss import EnvGSGeometryLoss
-    z, inp = _fixture()
+    z, inp = _fixture(path)
     opts, it = _case(z, tag)
     dev = torch.device("cuda", 0)
     out, batch = _to_dev(inp, dev)
