@@ -225,6 +225,15 @@ SYMBOLS = {
     "envgs_points_thin_keep": (c_int, [c_uint32, _P, c_size_t, _P, _P]),
     "envgs_mesh_cull_vertices": (c_int, [c_uint32, _P, ctypes.POINTER(CullViews), ctypes.c_int32, _P, _P]),
     "envgs_mesh_cull_faces": (c_int, [c_uint32, c_uint32, _P, _P, _P, _P]),
+    "envgs_points_transform": (c_int, [c_uint32, _P, ctypes.POINTER(ctypes.c_float), _P, _P]),
+    "envgs_points_register_temp_bytes": (c_size_t, [c_uint32]),
+    "envgs_points_register_sums": (c_int, [c_uint32, _P, ctypes.POINTER(ctypes.c_float)] + [ctypes.c_float] * 5 + [ctypes.c_int32] * 3
+                                   + [_P, _P, ctypes.POINTER(ctypes.c_double), _P, c_size_t] + [_P] * 4 + [_P]),
+    "envgs_points_voxel_keys": (c_int, [c_uint32, _P] + [ctypes.c_float] * 4 + [ctypes.c_int32] * 3 + [_P, _P]),
+    "envgs_points_voxel_temp_bytes": (c_size_t, [c_uint32]),
+    "envgs_points_voxel_cluster": (c_int, [c_uint32, _P] + [ctypes.c_float] * 4 + [ctypes.c_int32] * 3 + [_P, _P, _P, c_size_t, _P, _P, _P]),
+    "envgs_points_voxel_finish": (c_int, [c_uint32, _P] + [ctypes.c_float] * 4 + [ctypes.c_int32] * 3 + [_P, c_size_t, c_uint32, _P, _P]),
+    "envgs_points_in_polygon": (c_int, [c_uint32, _P, ctypes.c_int32, ctypes.c_double, ctypes.c_double, c_uint32, _P, _P, _P]),
     "envgs_l1_ssim_partial_count": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "envgs_l1_ssim_forward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P]),
     "envgs_l1_ssim_backward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, ctypes.c_float, ctypes.c_float, _P, _P]),

@@ -29,9 +29,12 @@ COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++20", "-fPIC", "-munsafe-fp-a
 # mesh.hip: the TSDF integration follows the NumPy oracle's fp32 sequence (multiply, add, IEEE divide, floor) decision for decision
 # mesh_simplify.hip: likewise the cell and the fixed-point offset of a vertex (subtract, IEEE divide, floor, multiply, add)
 # mesh_eval.hip: likewise the face area (products, differences, IEEE sqrt), the samples, the cell of a point and the squared distances
+# mesh_register.hip: the same cell and squared distance (csrc/mesh_points.h is one text for both files), the fp32 transformation, the double
+# products of the registration sums and the crossing test of the crop volume
 _NO_SLP = ["-fno-slp-vectorize"]
 EXTRA = {"raster_project.hip": ["-ffp-contract=off"], "raster_project_bwd.hip": ["-ffp-contract=off"], "densify_device.hip": ["-ffp-contract=off"],
          "mesh.hip": ["-ffp-contract=off"], "mesh_simplify.hip": ["-ffp-contract=off"], "mesh_eval.hip": ["-ffp-contract=off"],
+         "mesh_register.hip": ["-ffp-contract=off"],
          "trace_kbuffer.hip": _NO_SLP, "trace_collect.hip": _NO_SLP, "trace_lists.hip": _NO_SLP,
          "trace_surfel_bwd.hip": _NO_SLP, "trace_api.hip": _NO_SLP}
 

@@ -16,8 +16,7 @@
 //   pg_scatter     a lane per point: slot = atomic increment of its cell's word; the 16 B record (x, y, z, index bits) goes there.  Afterwards
 //                  the word of a cell holds the END of the cell, and the end of cell c - 1 is the start of cell c: one array serves both.
 //                  The slot order inside a cell depends on scheduling; the search result is a lexicographic minimum and does not.
-//   pg_nearest     a lane per query: Chebyshev shells around the query's cell.  A run of x-adjacent cells is one contiguous run of records, so a
-//                  shell is walked row by row: full rows on its four faces in j / k, the two end cells of the rows in between.
+//   pg_nearest     a lane per query: pg_walk of mesh_points.h, the Chebyshev shells around the query's cell (the registration calls the same walk)
 // Thinning (header: "thinning"; over the same grid)
 //   th_begin       a lane per point: its state (UNDECIDED, or DROPPED if not finite) and the first worklist of the undecided
 //   th_round       a lane per undecided point: the cell rows of shells 0 .. R around it; a kept neighbour of lower key drops it, an undecided one
@@ -26,6 +25,7 @@
 // Culling (header: "culling")
 //   cull_vertices  a lane per vertex: up to 8 views by the pixel rule of tsdf_integrate;  cull_faces  a lane per face: all three corners kept
 #include "common.h"
+#include "mesh_points.h"
 #include "mesh_rng.h"
 
 #include "../../include/envgs_mesh.h"
@@ -36,10 +36,6 @@ namespace {
 constexpr uint32_t COUNT_LIMIT = 1u << 31;
 constexpr float FACE_LIMIT = 16777216.0f;                         // 2^24 samples of one face
 constexpr uint32_t NO_CELL = 0xffffffffu;
-
-struct Grid { float o[3]; float cell; int32_t n[3]; };
-
-__device__ __forceinline__ bool ev_finite(const float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 
 // ---- sampling ---------------------------------------------------------------------------------------------------------------------------------------
 // the three corners of a face whose indices are in range; false otherwise (no index out of range is dereferenced)
@@ -130,13 +126,7 @@ ms_emit(const uint32_t F, const uint32_t nb, const uint32_t S, const float *__re
 }
 
 // ---- the point grid -----------------------------------------------------------------------------------------------------------------------------------
-// rule 1 of the simplification on one axis; the caller has checked that x is finite
-__device__ __forceinline__ int32_t pg_axis(const float x, const float o, const float cell, const int32_t n)
-{
-    const float fl = floorf((x - o) / cell);
-    return !(fl >= 1.0f) ? 0 : (fl >= 2147483648.0f ? n - 1 : min((int32_t)fl, n - 1));
-}
-
+// the cell of a point (pg_axis), the shell walk (pg_walk) and their types: mesh_points.h, shared with mesh_register.hip
 __global__ void __launch_bounds__(256)
 pg_count(const uint32_t N, const float *__restrict__ points, const Grid g, uint32_t *__restrict__ cell_of, uint32_t *__restrict__ hist)
 {
@@ -183,22 +173,6 @@ pg_scatter(const uint32_t N, const float *__restrict__ points, const uint32_t *_
     records[slot] = make_float4(points[3 * (size_t)i], points[3 * (size_t)i + 1], points[3 * (size_t)i + 2], __uint_as_float(i));
 }
 
-struct Best { float d2; uint32_t index; };
-
-// the records of the cells c0 .. c1 of one row
-__device__ __forceinline__ void pg_scan_cells(const uint32_t c0, const uint32_t c1, const uint32_t *__restrict__ cell_end, const float4 *__restrict__ records,
-                                              const float qx, const float qy, const float qz, const float r2, Best &best)
-{
-    const uint32_t first = c0 ? cell_end[c0 - 1] : 0u, last = cell_end[c1];
-    for (uint32_t s = first; s < last; s++) {
-        const float4 p = records[s];
-        const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
-        const float d2 = ((dx * dx) + (dy * dy)) + (dz * dz);
-        const uint32_t i = __float_as_uint(p.w);
-        if (d2 <= r2 && (d2 < best.d2 || (d2 == best.d2 && i < best.index))) { best.d2 = d2; best.index = i; }
-    }
-}
-
 __global__ void __launch_bounds__(256)
 pg_nearest(const uint32_t Q, const float *__restrict__ queries, const float max_distance, const Grid g, const uint32_t *__restrict__ cell_end,
            const float4 *__restrict__ records, float *__restrict__ dist2, int32_t *__restrict__ index)
@@ -206,32 +180,7 @@ pg_nearest(const uint32_t Q, const float *__restrict__ queries, const float max_
     const uint32_t q = blockIdx.x * 256u + threadIdx.x;
     if (q >= Q) return;
     const float qx = queries[3 * (size_t)q], qy = queries[3 * (size_t)q + 1], qz = queries[3 * (size_t)q + 2];
-    Best best = {__uint_as_float(0x7f800000u), 0xffffffffu};
-    if (ev_finite(qx) && ev_finite(qy) && ev_finite(qz)) {
-        const int32_t nx = g.n[0], ny = g.n[1], nz = g.n[2];
-        const int32_t ci = pg_axis(qx, g.o[0], g.cell, nx), cj = pg_axis(qy, g.o[1], g.cell, ny), ck = pg_axis(qz, g.o[2], g.cell, nz);
-        const float r2 = max_distance * max_distance;
-        // the last shell that holds a cell of the grid: an integer, so the loop ends whatever the floats are
-        const int32_t rmax = max(max(max(ci, nx - 1 - ci), max(cj, ny - 1 - cj)), max(ck, nz - 1 - ck));
-        for (int32_t r = 0; r <= rmax; r++) {
-            const int32_t k0 = max(ck - r, 0), k1 = min(ck + r, nz - 1), j0 = max(cj - r, 0), j1 = min(cj + r, ny - 1);
-            const int32_t i0 = max(ci - r, 0), i1 = min(ci + r, nx - 1);
-            for (int32_t k = k0; k <= k1; k++) {
-                const bool kface = k == ck - r || k == ck + r;
-                for (int32_t j = j0; j <= j1; j++) {
-                    const uint32_t row = (uint32_t)nx * ((uint32_t)j + (uint32_t)ny * (uint32_t)k);
-                    if (kface || j == cj - r || j == cj + r) {
-                        pg_scan_cells(row + (uint32_t)i0, row + (uint32_t)i1, cell_end, records, qx, qy, qz, r2, best);
-                    } else {                                        // r >= 1 here: the two ends of the row, where they are inside the grid
-                        if (ci - r >= 0) pg_scan_cells(row + (uint32_t)(ci - r), row + (uint32_t)(ci - r), cell_end, records, qx, qy, qz, r2, best);
-                        if (ci + r < nx) pg_scan_cells(row + (uint32_t)(ci + r), row + (uint32_t)(ci + r), cell_end, records, qx, qy, qz, r2, best);
-                    }
-                }
-            }
-            const float b = ((float)r * g.cell) * 0.9990234375f;    // 1 - 2^-10: every point outside shell r is farther than b (header: the proof)
-            if (best.d2 <= b * b || b > max_distance) break;
-        }
-    }
+    const Best best = pg_walk(qx, qy, qz, max_distance, g, cell_end, records);
     dist2[q] = best.d2;
     index[q] = (int32_t)best.index;
 }

@@ -19,6 +19,7 @@
 // The compaction is envgs_mesh_select_count / _emit of mesh_clean.hip, called by the host on the clustered mesh.
 #include "common.h"
 #include "mesh_facehash.h"
+#include "mesh_points.h"
 
 #include "../../include/envgs_mesh.h"
 
@@ -36,22 +37,9 @@ struct DeviceAtomics {
     static __host__ __device__ __forceinline__ void min(cell *p, uint32_t v) { (void)__hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 };
 
-struct Grid { float o[3]; float cell; int32_t n[3]; };
-
-constexpr float POS_ONE = 1048576.0f, POS_STEP = 1.0f / 1048576.0f;      // 2^20
+// Grid, POS_ONE / POS_STEP and sc_locate (rule 1 and the offset of rule 3): mesh_points.h, shared with the sparse voxel mean of mesh_register.hip
 constexpr float COL_ONE = 65536.0f, COL_STEP = 1.0f / 65536.0f;          // 2^16
 constexpr uint32_t NO_CLUSTER = 0xffffffffu;
-
-// rule 1 and the offset of rule 3 on one axis; the caller has checked that x is finite
-__device__ __forceinline__ void sc_locate(const float x, const float o, const float cell, const int32_t n, int32_t &i, uint32_t &q)
-{
-    const float u = (x - o) / cell;
-    const float fl = floorf(u);
-    i = !(fl >= 1.0f) ? 0 : (fl >= 2147483648.0f ? n - 1 : min((int32_t)fl, n - 1));
-    float f = u - (float)i;
-    f = !(f > 0.0f) ? 0.0f : (f > 1.0f ? 1.0f : f);
-    q = (uint32_t)floorf(f * POS_ONE + 0.5f);
-}
 
 __device__ __forceinline__ uint32_t sc_colour(float c)
 {

@@ -1,7 +1,7 @@
 """Mesh extraction (include/envgs_mesh.h, csrc/mesh.hip, csrc/mesh_clean.hip, csrc/mesh_simplify.hip, csrc/mesh_eval.hip): TSDF fusion of rendered
 depth into a dense volume, marching tetrahedra over it, the clean-up of the mesh (connected components, order-preserving face selection, removal
 of small components), its simplification by vertex clustering, and its evaluation against a ground-truth cloud (surface samples, exact nearest
-points, Chamfer and F-score).
+points, Chamfer and F-score; the DTU protocol; rigid registration and the Tanks-and-Temples protocol: csrc/mesh_register.hip).
 
 PARITY UNPINNED: the reference ships a fuser (easyvolcap/utils/tsdf_utils.py, fusion_utils.py, runners/visualizers/geometry_visualizer.py) that
 cannot run as it stands and leaves the marching step to libraries outside it, so the semantics are this project's ("Mesh extraction");
@@ -15,10 +15,13 @@ tests/mesh_oracle.py restates them independently.  There is no CPU path: CPU ten
     score = evaluate(mesh, scan_points, max_distance=0.2, threshold=0.01, density=1e4)      # csrc/mesh_eval.hip: .chamfer, .fscore, ...
     dtu = evaluate_dtu(cull_to_masks(mesh, cameras, masks), scan_points, radius=0.2, max_distance=20.0, density=25.0,
                        observed=(obs_mask, origin, voxel), box=(lo, hi), plane=plane)       # the DTU protocol: thin_points() and the filters
+    tnt = evaluate_tnt(mesh, scan_points, tau=0.003, init=T_colmap_to_scan, crop=load_crop_volume("Barn.json"), density=4e5)
+                                                                                            # Tanks and Temples: register(), voxel_downsample(), the crop
 """
 import math
 from types import SimpleNamespace
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -487,6 +490,7 @@ class PointGrid:
                                  "cell_size here is %r" % (cell_size, _grid_dims(extent, cell_size), good))
         self.origin, self.dims = tuple(lo), tuple(_grid_dims(extent, cell_size))
         self.cell_size, self.max_distance, self.count, self.device = cell_size, max_distance, N, points.device
+        self.center = tuple(0.5 * (l + h) for l, h in zip(lo, hi))      # of the box of the finite points, in double: the c of register_sums()
         lib = _lib.load()
         nx, ny, nz = self.dims
         tb = lib.envgs_points_grid_temp_bytes(N, nx, ny, nz)
@@ -765,4 +769,293 @@ def evaluate_dtu(mesh_or_points, scan_points, radius, max_distance, density=None
         out.recall = within_r / out.n_ref if out.n_ref else 0.0
         out.fscore = 2.0 * out.precision * out.recall / (out.precision + out.recall) if out.precision + out.recall > 0.0 else 0.0
         out.within_pred, out.within_ref = int(within_p), int(within_r)
+    return out
+
+
+# ---- registration and the Tanks-and-Temples protocol (csrc/mesh_register.hip; include/envgs_mesh.h, "registration") ------------------------------------
+REGISTER_SUMS, VOXEL_MAX_DIM, POLYGON_MAX = 18, 2 ** 21, 256     # ENVGS_REGISTER_SUMS, ENVGS_VOXEL_MAX_DIM, ENVGS_POLYGON_MAX
+
+
+def _transformation(T, what):
+    """-> (4,4) float64 NumPy copy of a 4x4 or 3x4 transformation (the last row of a 3x4 is 0 0 0 1), checked finite."""
+    if isinstance(T, torch.Tensor):
+        T = T.detach().cpu().numpy()
+    T = np.array(T, dtype=np.float64)
+    if T.shape == (3, 4):
+        T = np.vstack([T, [0.0, 0.0, 0.0, 1.0]])
+    if T.shape != (4, 4) or not np.isfinite(T).all():
+        raise ValueError("%s: the transformation must be a finite 4x4 or 3x4 matrix" % what)
+    return T
+
+
+def _rigid_rows(T):
+    """The upper 3x4 of T, each entry rounded once to fp32, as the host array the C-ABI takes (and the owner that keeps it alive)."""
+    with np.errstate(over="ignore"):
+        m = np.ascontiguousarray(T[:3, :4], dtype=np.float32).reshape(12)
+    if not np.isfinite(m).all():
+        raise ValueError("the transformation does not fit fp32")
+    return m.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_float)), m
+
+
+def transform_points(points, T):
+    """(N,3) f32: x' = ((M00 x + M01 y) + M02 z) + M03 and likewise y', z' in fp32 without FMA, M the upper 3x4 of T (4x4 or 3x4, float64, on the
+    host) with each entry rounded once to fp32.  A row that is not finite stays not finite.  The device function is the one register() calls.
+    No host sync."""
+    points = _points_tensor(points, "transform_points")
+    m, owner = _rigid_rows(_transformation(T, "transform_points"))
+    out = torch.empty(points.shape[0], 3, dtype=torch.float32, device=points.device)
+    _lib.check(_lib.load().envgs_points_transform(points.shape[0], _lib.ptr(points), m, _lib.ptr(out), _stream(points.device)), "envgs_points_transform")
+    del owner
+    return out
+
+
+def rigid_from_sums(sums, with_scale=False, center=None):
+    """The least-squares rigid (or, with_scale, similarity) transformation of the matched pairs behind the 18 sums of one registration iteration
+    (include/envgs_mesh.h, "registration", rules 2 and 3): n, sum d2, sum ah (3), sum bh (3), sum ah bh^T (9, row major), sum |ah|^2, with ah, bh
+    the moved source point and its match less `center`.  A pure float64 function of its arguments: no GPU, no library.
+      am = sum ah / n, bm = sum bh / n;   H = sum ah bh^T - n am bm^T;   U S V^T = svd(H)
+      R = V diag(1, 1, d) U^T with d = +1 or -1, the sign of det(V U^T) (never a reflection);   s = tr(S diag(1, 1, d)) / (sum |ah|^2 - n |am|^2)
+      or 1;   t = bm - s R am;   the result maps x to s R x + (c + t - s R c), c = center (None: the origin).
+    -> (4,4) float64.  Raises ValueError for n < 3, for sums that are not finite, and with_scale for a denominator that is not positive.  A planar or
+    collinear cloud is no error: the rotation is then the proper one of least angle among the minimisers the SVD offers."""
+    s = np.asarray(sums, dtype=np.float64).reshape(-1)
+    if s.shape[0] != REGISTER_SUMS:
+        raise ValueError("rigid_from_sums: 18 sums are required")
+    if not np.isfinite(s).all():
+        raise ValueError("rigid_from_sums: the sums are not finite")
+    n = s[0]
+    if not n >= 3:
+        raise ValueError("rigid_from_sums: fewer than 3 pairs")
+    c = np.zeros(3) if center is None else np.asarray(center, dtype=np.float64).reshape(3)
+    am, bm = s[2:5] / n, s[5:8] / n
+    H = s[8:17].reshape(3, 3) - n * np.outer(am, bm)
+    U, S, Vt = np.linalg.svd(H)
+    V = Vt.T
+    d = 1.0 if np.linalg.det(V @ U.T) >= 0.0 else -1.0
+    R = V @ np.diag([1.0, 1.0, d]) @ U.T
+    scale = 1.0
+    if with_scale:
+        den = s[17] - n * float(am @ am)
+        if not den > 0.0:
+            raise ValueError("rigid_from_sums: the source pairs have no extent, the scale is undefined")
+        scale = (S[0] + S[1] + d * S[2]) / den
+    sR = scale * R
+    out = np.eye(4)
+    out[:3, :3] = sR
+    out[:3, 3] = c + (bm - sR @ am) - sR @ c
+    return out
+
+
+def register_sums(source, grid, T, return_rows=False):
+    """One evaluation of a transformation T (4x4 or 3x4, float64, host) against a PointGrid: every source row is moved by transform_points' rule, its
+    nearest target point within grid.max_distance found by PointGrid.nearest's rule, and the 18 sums of rigid_from_sums reduced in a fixed order
+    (include/envgs_mesh.h), with c = grid.center, the centre of the box of the finite target points.  -> sums (18,) float64 NumPy, on the host: the
+    one sync; with return_rows also (moved (Q,3) f32, dist2 (Q,) f32, index (Q,) i32) on the device -- what transform_points and
+    grid.nearest(moved) give."""
+    source = _points_tensor(source, "register_sums")
+    if source.device != grid.device:
+        raise ValueError("register_sums: the source must be on the grid's device")
+    m, owner = _rigid_rows(_transformation(T, "register_sums"))
+    lib = _lib.load()
+    dev, Q = grid.device, source.shape[0]
+    tb = lib.envgs_points_register_temp_bytes(Q)
+    temp = torch.empty(tb, dtype=torch.uint8, device=dev)
+    sums = torch.empty(REGISTER_SUMS, dtype=torch.float64, device=dev)
+    moved = torch.empty(Q, 3, dtype=torch.float32, device=dev) if return_rows else None
+    dist2 = torch.empty(Q, dtype=torch.float32, device=dev) if return_rows else None
+    index = torch.empty(Q, dtype=torch.int32, device=dev) if return_rows else None
+    nx, ny, nz = grid.dims
+    p = _lib.ptr
+    center = (_lib.ctypes.c_double * 3)(*grid.center)
+    _lib.check(lib.envgs_points_register_sums(Q, p(source), m, grid.max_distance, grid.origin[0], grid.origin[1], grid.origin[2], grid.cell_size, nx, ny, nz,
+                                              p(grid.cell_end), p(grid.records), center, p(temp), tb, p(sums), p(moved), p(dist2), p(index), _stream(dev)),
+               "envgs_points_register_sums")
+    del owner
+    host = sums.cpu().numpy()
+    return (host, moved, dist2, index) if return_rows else host
+
+
+def register(source, target_or_grid, max_distance, init=None, with_scale=False, max_iterations=20, rel_fitness=1e-6, rel_rmse=1e-6, cell_size=None):
+    """Point-to-point ICP of source (N,3) onto a target -- a (M,3) point tensor, or a PointGrid built over one with this max_distance, so that several
+    calls can share it.  T_0 = init (4x4 or 3x4; None: the identity).  Iteration k evaluates T_k (register_sums: ONE kernel over the source plus a
+    fixed-order reduction, then one read-back of 18 doubles -- one host sync per iteration): fitness_k = n / N over ALL source rows, inlier_rmse_k =
+    sqrt(sum d2 / n).  It stops as CONVERGED when |fitness_k - fitness_{k-1}| < rel_fitness and |rmse_k - rmse_{k-1}| < rel_rmse; as not converged
+    when n < 3, when with_scale the source pairs have no extent, or after max_iterations updates; otherwise T_{k+1} = rigid_from_sums(sums_k) T_k in
+    float64.  The source is always moved from its original coordinates by the total transformation, never incrementally.
+    The search is exact and the sums are reduced in an order that depends on N alone, so the same inputs give the same transformation to the bit, from
+    run to run and at every cell_size (None: PointGrid's default).
+    -> namespace(transformation (4,4) float64 NumPy: the last T_k evaluated, fitness, inlier_rmse, iterations: the updates applied, converged,
+    center: the c of the sums, history: [namespace(transformation T_k, sums (18,), fitness, inlier_rmse)] one per evaluation)."""
+    source = _points_tensor(source, "register")
+    if isinstance(target_or_grid, PointGrid):
+        grid = target_or_grid
+        if _f32(grid.max_distance) != _f32(max_distance):
+            raise ValueError("register: the grid was built for max_distance %r, not %r" % (grid.max_distance, max_distance))
+    else:
+        grid = PointGrid(target_or_grid, max_distance, cell_size)
+    T = np.eye(4) if init is None else _transformation(init, "register")
+    max_iterations = int(max_iterations)
+    N = source.shape[0]
+    center = np.array(grid.center, dtype=np.float64)
+    history, converged, updates = [], False, 0
+    while True:
+        sums = register_sums(source, grid, T)
+        n = int(sums[0])
+        fitness = n / N if N else 0.0
+        rmse = math.sqrt(sums[1] / n) if n else 0.0
+        history.append(SimpleNamespace(transformation=T.copy(), sums=sums, fitness=fitness, inlier_rmse=rmse))
+        if len(history) > 1 and abs(fitness - history[-2].fitness) < rel_fitness and abs(rmse - history[-2].inlier_rmse) < rel_rmse:
+            converged = True
+            break
+        if n < 3 or updates >= max_iterations:
+            break
+        try:
+            delta = rigid_from_sums(sums, with_scale, center)
+        except ValueError:
+            break
+        T = delta @ T
+        updates += 1
+    return SimpleNamespace(transformation=T, fitness=fitness, inlier_rmse=rmse, iterations=updates, converged=converged, center=center, history=history)
+
+
+def voxel_grid(points, voxel_size, origin=None):
+    """The grid voxel_downsample() uses: -> (origin, dims), as simplify_grid sizes its own (origin None: the per-axis minimum of the finite rows;
+    dims[a] = floor(extent[a] / voxel_size) + 1), with up to 2^21 cells per axis and no bound on their product.  Raises ValueError beyond that,
+    naming the smallest admissible voxel_size.  One host sync: the extrema (a second one when some row is not finite)."""
+    points = _points_tensor(points, "voxel_downsample")
+    voxel_size = float(voxel_size)
+    if not (voxel_size > 0.0 and math.isfinite(voxel_size)) or not 0.0 < _f32(voxel_size) < float("inf"):
+        raise ValueError("voxel_downsample: voxel_size must be positive and finite")
+    lo, hi = _finite_extent(points)
+    if origin is not None:
+        lo = [float(o) for o in origin]
+        if len(lo) != 3 or not all(math.isfinite(o) for o in lo):
+            raise ValueError("voxel_downsample: origin must be three finite numbers")
+    extent = [h - l for l, h in zip(lo, hi)]
+    admissible = lambda c: max(_grid_dims(extent, c)) <= VOXEL_MAX_DIM
+    if not admissible(voxel_size):
+        bad, good = voxel_size, 2.0 * voxel_size
+        while not admissible(good):
+            bad, good = good, 2.0 * good
+        for _ in range(60):
+            mid = 0.5 * (bad + good)
+            bad, good = (bad, mid) if admissible(mid) else (mid, good)
+        raise ValueError("voxel_downsample: voxel_size %g gives %s cells, beyond 2^21 per axis; the smallest admissible voxel_size here is %r"
+                         % (voxel_size, _grid_dims(extent, voxel_size), good))
+    return tuple(lo), tuple(_grid_dims(extent, voxel_size))
+
+
+def voxel_downsample(points, voxel_size, origin=None, return_index=False):
+    """One point per occupied voxel: the sparse form of simplify()'s clustering (include/envgs_mesh.h, "registration", rule 4), for grids far beyond
+    2^31 cells.  The cell of a point is rule 1 of the simplification on the grid of voxel_grid(); the clusters are the occupied cells by ascending key
+    i | j << 21 | k << 42 (the simplification's own order, x fastest); the representative is its rule 3, word for word: a single member keeps its
+    bits, otherwise the rounded mean of 64-bit integer sums in steps of 2^-20 of a cell.  The result depends on no order: two runs and two
+    permutations of the input give identical bytes.  Rows that are not finite belong to no cluster.
+    -> (C,3) f32, with return_index also cluster (N,) i32 (-1 = none).  The keys are sorted by torch.sort; everything else is HIP.  Host syncs: those
+    of voxel_grid, and the read-back of C."""
+    points = _points_tensor(points, "voxel_downsample")
+    (ox, oy, oz), (nx, ny, nz) = voxel_grid(points, voxel_size, origin)
+    lib = _lib.load()
+    dev, N = points.device, points.shape[0]
+    cell = float(voxel_size)
+    p, s = _lib.ptr, _stream(dev)
+    keys = torch.empty(N, dtype=torch.int64, device=dev)
+    _lib.check(lib.envgs_points_voxel_keys(N, p(points), ox, oy, oz, cell, nx, ny, nz, p(keys), s), "envgs_points_voxel_keys")
+    sorted_keys, order = torch.sort(keys)
+    tb = lib.envgs_points_voxel_temp_bytes(N)
+    temp = torch.empty(tb, dtype=torch.uint8, device=dev)
+    cluster = torch.empty(N, dtype=torch.int32, device=dev) if return_index else None
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    _lib.check(lib.envgs_points_voxel_cluster(N, p(points), ox, oy, oz, cell, nx, ny, nz, p(sorted_keys), p(order), p(temp), tb, p(cluster), p(count), s),
+               "envgs_points_voxel_cluster")
+    C = int(count.item())
+    out = torch.empty(C, 3, dtype=torch.float32, device=dev)
+    _lib.check(lib.envgs_points_voxel_finish(N, p(points), ox, oy, oz, cell, nx, ny, nz, p(temp), tb, C, p(out), s), "envgs_points_voxel_finish")
+    return (out, cluster) if return_index else out
+
+
+_AXES = {"X": 0, "Y": 1, "Z": 2}
+
+
+def in_polygon_volume(points, axis, axis_min, axis_max, polygon):
+    """(N,) bool: the crop volume of the Tanks-and-Temples toolbox, Open3D's SelectionPolygonVolume.  axis "X", "Y" or "Z" is the orthogonal axis w;
+    (u, v) = (1, 2), (0, 2), (0, 1); polygon (M,3), 3 <= M <= 256.  A finite point is inside iff axis_min <= p[w] <= axis_max and the number of
+    edges (j, j+1 mod M) with (v_j > p_v) != (v_k > p_v) and p_u < (u_k - u_j) * (p_v - v_j) / (v_k - v_j) + u_j is odd, evaluated in double as
+    written on the fp32 point and the float64 polygon.  A row that is not finite is False.  No host sync."""
+    points = _points_tensor(points, "in_polygon_volume")
+    if axis not in _AXES:
+        raise ValueError("in_polygon_volume: axis must be 'X', 'Y' or 'Z'")
+    poly = np.asarray(polygon.detach().cpu().numpy() if isinstance(polygon, torch.Tensor) else polygon, dtype=np.float64)
+    if poly.ndim != 2 or poly.shape[1] != 3 or not 3 <= poly.shape[0] <= POLYGON_MAX or not np.isfinite(poly).all():
+        raise ValueError("in_polygon_volume: polygon must be a finite (M,3) array, 3 <= M <= 256")
+    axis_min, axis_max = float(axis_min), float(axis_max)
+    if math.isnan(axis_min) or math.isnan(axis_max):
+        raise ValueError("in_polygon_volume: axis_min and axis_max must be numbers")
+    dev = points.device
+    poly_dev = torch.from_numpy(np.ascontiguousarray(poly)).to(dev)
+    inside = torch.empty(points.shape[0], dtype=torch.bool, device=dev)
+    _lib.check(_lib.load().envgs_points_in_polygon(points.shape[0], _lib.ptr(points), _AXES[axis], axis_min, axis_max, poly.shape[0], _lib.ptr(poly_dev),
+                                                   _lib.ptr(inside), _stream(dev)), "envgs_points_in_polygon")
+    return inside
+
+
+def load_crop_volume(path):
+    """Reads an Open3D SelectionPolygonVolume JSON (the crop files of Tanks and Temples): -> namespace(axis "X" / "Y" / "Z", axis_min, axis_max,
+    polygon (M,3) float64 NumPy), the arguments of in_polygon_volume()."""
+    import json
+    with open(path) as f:
+        d = json.load(f)
+    polygon = np.asarray(d["bounding_polygon"], dtype=np.float64).reshape(-1, 3)
+    axis = str(d["orthogonal_axis"]).upper()
+    if axis not in _AXES:
+        raise ValueError("load_crop_volume: orthogonal_axis %r is not X, Y or Z" % d["orthogonal_axis"])
+    return SimpleNamespace(axis=axis, axis_min=float(d["axis_min"]), axis_max=float(d["axis_max"]), polygon=polygon)
+
+
+def _crop(points, crop):
+    if crop is None:
+        return points
+    return points[in_polygon_volume(points, crop.axis, crop.axis_min, crop.axis_max, crop.polygon)].contiguous()
+
+
+def evaluate_tnt(mesh_or_points, scan_points, tau, init=None, crop=None, density=None, seed=0, max_points=4_000_000):
+    """The Tanks-and-Temples evaluation on the device, by the schedule of the toolbox's run.py.  The prediction -- a Mesh sampled at `density` with
+    `seed`, or a (N,3) point tensor -- is brought into the scan's frame by `init` (4x4; None: the identity) and three ICP refinements, then scored at
+    the distance tau.  crop: a namespace as load_crop_volume() gives (axis, axis_min, axis_max, polygon), or None for no crop.  With T = init:
+      1. the prediction moved by T and cropped, the scan cropped, both down-sampled at voxel tau (voxel_downsample);  register() with
+         max_distance 80 tau and 20 iterations from the identity gives D;  T = D T
+      2. the same at voxel tau / 2 with max_distance 20 tau
+      3. every k-th row of each cloud, k the smallest that leaves at most max_points rows, the prediction moved by T, both cropped;
+         max_distance 2 tau
+      4. the prediction moved by the final T and cropped, it and the cropped scan down-sampled at voxel tau / 2;
+         evaluate(prediction, scan, max_distance=tau, threshold=tau)
+    -> the namespace of evaluate() (precision, recall, fscore at tau; accuracy, completeness, ...) plus transformation (4,4) float64, the total T, and
+    registrations: the three register() results.  Every step is deterministic, so two runs give identical numbers.
+    Stated deviations from the toolbox: d <= tau and d <= max_distance where it has <; the canonical voxel means of voxel_downsample() in place of
+    Open3D's hash-ordered float means; no RANSAC / trajectory alignment -- the caller supplies `init`; no histogram plots."""
+    tau = float(tau)
+    if not (tau > 0.0 and math.isfinite(tau)):
+        raise ValueError("evaluate_tnt: tau must be positive and finite")
+    max_points = int(max_points)
+    if max_points < 1:
+        raise ValueError("evaluate_tnt: max_points must be at least 1")
+    pred = _eval_points(mesh_or_points, density, seed, "evaluate_tnt")
+    scan = _points_tensor(scan_points, "evaluate_tnt")
+    if pred.device != scan.device:
+        raise ValueError("evaluate_tnt: the prediction and the scan must be on one device")
+    T = np.eye(4) if init is None else _transformation(init, "evaluate_tnt")
+    scan_cropped = _crop(scan, crop)
+    registrations = []
+    for voxel, reach in ((tau, 80.0 * tau), (0.5 * tau, 20.0 * tau)):
+        source = voxel_downsample(_crop(transform_points(pred, T), crop), voxel)
+        target = voxel_downsample(scan_cropped, voxel)
+        registrations.append(register(source, target, reach, max_iterations=20))
+        T = registrations[-1].transformation @ T
+    every = lambda t: t[::max(1, -(-t.shape[0] // max_points))].contiguous()
+    source = _crop(transform_points(every(pred), T), crop)
+    registrations.append(register(source, _crop(every(scan), crop), 2.0 * tau, max_iterations=20))
+    T = registrations[-1].transformation @ T
+    moved = voxel_downsample(_crop(transform_points(pred, T), crop), 0.5 * tau)
+    out = evaluate(moved, voxel_downsample(scan_cropped, 0.5 * tau), max_distance=tau, threshold=tau)
+    out.transformation, out.registrations = T, registrations
     return out

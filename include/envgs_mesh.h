@@ -321,6 +321,98 @@ ENVGS_API int envgs_mesh_cull_vertices(uint32_t V, const float *vertices, const 
 /* face_keep (F) uint8 from vertex_keep (V): the input of envgs_mesh_select_count / _emit.  An index outside [0, V) is never dereferenced. */
 ENVGS_API int envgs_mesh_cull_faces(uint32_t V, uint32_t F, const int32_t *faces, const uint8_t *vertex_keep, uint8_t *face_keep, void *stream);
 
+/* ---- registration and the Tanks-and-Temples protocol (csrc/mesh_register.hip, csrc/mesh_points.h) ---------------------------------------------------
+ * PARITY UNPINNED: the reference has no registration.  The rules are this project's own, modelled on Open3D's point-to-point ICP, voxel
+ * down-sampling and SelectionPolygonVolume and on the Tanks-and-Temples toolbox; tests/mesh_register_oracle.py restates them in NumPy.  All fp32
+ * arithmetic is left to right, no FMA, IEEE division; the double arithmetic named below is never contracted either.
+ *
+ * 1. Transformation.  M (12 floats on the HOST, row major) is the upper 3 x 4 of a transformation, each entry already rounded to fp32:
+ *      x' = ((M00 x + M01 y) + M02 z) + M03      y' = ((M10 x + M11 y) + M12 z) + M13      z' = ((M20 x + M21 y) + M22 z) + M23
+ *    A row with a coordinate that is not finite gives a row of which no coordinate is finite.  envgs_points_transform and the registration call
+ *    one device function (pt_transform), so the two cannot drift.
+ *
+ * 2. The sums of one ICP iteration.  For every source row p:  a = M p by rule 1;  b = the nearest target point within max_distance by the rule of
+ *    envgs_points_nearest applied to a (the same candidates, the same tie-break by lowest index, the same result at every cell size; the walk is
+ *    one device function, pg_walk, that both kernels call), its coordinates taken from the grid's record;  d2 = the fp32 d2 of that search.
+ *    A row without a match (none within max_distance, or a or p not finite) adds nothing.  With c = `center`, three finite doubles on the HOST --
+ *    the centre of the box of the finite target points, (lo + hi) / 2 per axis in double, which is a property of the points and not of the cell
+ *    size -- and  ah = (double)a - c,  bh = (double)b - c  (exact for all practical inputs), a matched row adds, all in double:
+ *      sums[0]      1                                   n, the number of matches (below 2^31, so exact)
+ *      sums[1]      (double)d2
+ *      sums[2..4]   ah          sums[5..7]   bh
+ *      sums[8+3r+c] ah[r] * bh[c]                        row major: sum of ah bh^T
+ *      sums[17]     ((ah0 ah0) + (ah1 ah1)) + (ah2 ah2)
+ *    The order of the additions is a function of Q alone.  Source row q belongs to lane q mod 64 of wavefront (q / 64) mod 4 of workgroup
+ *    q / 256; rows at or beyond Q and rows without a match contribute +0.
+ *      lane -> wavefront:  lane l adds the value of lane l + 32, then of l + 16, 8, 4, 2, 1 (a lane whose partner is beyond 63 adds its own value
+ *                          and feeds nobody); lane 0 ends with the balanced binary tree over the 64 lanes
+ *      -> workgroup row:   ((w0 + w1) + w2) + w3 over its four wavefronts: one row of 18 doubles, 144 B, per workgroup
+ *      -> the result:      ONE workgroup of 256 threads: thread t adds the rows t, t + 256, t + 512 .. in ascending order, starting from +0; the 256
+ *                          thread sums are then added exactly as the 256 lane values of a row above
+ *    No atomic is issued, float or integer: the 18 numbers are identical from run to run, and -- the match being a lexicographic minimum over a
+ *    set -- at every cell size of the grid.
+ *
+ * 3. The solve is on the host in float64 (envgs_amd.mesh.rigid_from_sums):  am = sum ah / n, bm = sum bh / n;  H = sum ah bh^T - n am bm^T;
+ *    U S V^T = svd(H);  D = diag(1, 1, det(V U^T));  R = V D U^T;  s = tr(S D) / (sum |ah|^2 - n |am|^2) with scale, else 1;
+ *    t = bm - s R am, and the transformation in world coordinates is x -> s R x + (c + t - s R c).
+ *
+ * 4. Voxel mean: the sparse form of the simplification's clustering, for grids far beyond 2^31 cells.  The cell of a point is rule 1 of the
+ *    simplification per axis, 1 <= n* <= ENVGS_VOXEL_MAX_DIM = 2^21; its key is i | j << 21 | k << 42, which orders the cells as the linear index
+ *    of the simplification does (x fastest); a point that is not finite has the key 2^63 - 1 and no cluster (-1).  The clusters are the occupied
+ *    keys in ascending order.  The representative is rule 3 of the simplification, word for word (one device function, sc_locate): a single
+ *    member keeps its bits, otherwise 64-bit integer sums of the offsets in steps of 2^-20 of a cell and the rounded mean.  Integer sums depend on
+ *    no order: two runs and two permutations of the input give identical bytes, and wherever the dense grid of envgs_mesh_simplify_cluster
+ *    exists its rows 0 .. C-1 of cl_vertices are the same bytes.  The sort of the keys between envgs_points_voxel_keys and
+ *    envgs_points_voxel_cluster is the caller's (any sort; only the grouping of equal keys and their ascending order are used).
+ *
+ * 5. Crop volume (Open3D's SelectionPolygonVolume).  axis 0 / 1 / 2 = X / Y / Z is the orthogonal axis w; (u, v) = (1, 2), (0, 2), (0, 1).  A
+ *    point whose coordinates are finite is INSIDE iff axis_min <= p[w] <= axis_max and the number of edges (j, k = j + 1 mod M) with
+ *      (v_j > p_v) != (v_k > p_v)   and   p_u < (u_k - u_j) * (p_v - v_j) / (v_k - v_j) + u_j
+ *    is odd -- evaluated in double as written (product, quotient, sum), on the fp32 point converted to double and the double polygon. */
+#define ENVGS_REGISTER_SUMS 18
+#define ENVGS_VOXEL_MAX_DIM (1 << 21)
+#define ENVGS_POLYGON_MAX 256
+
+/* out (N,3) = rule 1 applied to points (N,3); the two must not overlap.  N = 0 is valid.  A NULL or non-finite M, a count at or above 2^31 and a NULL
+ * array of rows return ENVGS_ERR_BAD_ARG before any GPU work. */
+ENVGS_API int envgs_points_transform(uint32_t N, const float *points, const float *M, float *out, void *stream);
+
+/* Scratch bytes of envgs_points_register_sums: 144 B per workgroup of 256 source rows (0 if Q is 2^31 or more). */
+ENVGS_API size_t envgs_points_register_temp_bytes(uint32_t Q);
+
+/* Rule 2 over source (Q,3) against a grid built by envgs_points_grid_build with the same origin, cell and dimensions: two launches (the rows, the
+ * final workgroup), sums (18 doubles) left on the device.  Optional per-row outputs, NULL = not wanted: moved (Q,3) the transformed rows,
+ * dist2 (Q) and index (Q) as envgs_points_nearest would give them for `moved`.  Q = 0 is valid: the sums are zero.  Bad arguments as for
+ * envgs_points_nearest, plus a NULL or non-finite M or center, a NULL `sums` and a `temp` that is NULL or not 16-byte aligned: ENVGS_ERR_BAD_ARG before
+ * any GPU work; a short `temp` ENVGS_ERR_TEMP_TOO_SMALL. */
+ENVGS_API int envgs_points_register_sums(uint32_t Q, const float *source, const float *M, float max_distance, float ox, float oy, float oz, float cell,
+                                         int32_t nx, int32_t ny, int32_t nz, const uint32_t *cell_end, const float *records, const double *center, void *temp,
+                                         size_t temp_bytes, double *sums, float *moved, float *dist2, int32_t *index, void *stream);
+
+/* keys (N) int64 of rule 4.  N = 0 is valid.  A dimension outside 1 .. 2^21, a cell that is not positive and finite, an origin that is not finite,
+ * a count at or above 2^31: ENVGS_ERR_BAD_ARG before any GPU work. */
+ENVGS_API int envgs_points_voxel_keys(uint32_t N, const float *points, float ox, float oy, float oz, float cell, int32_t nx, int32_t ny, int32_t nz,
+                                      int64_t *keys, void *stream);
+
+/* Scratch bytes of envgs_points_voxel_cluster / _finish: 48 B per point plus the scan's scratch (0 if N is 2^31 or more). */
+ENVGS_API size_t envgs_points_voxel_temp_bytes(uint32_t N);
+
+/* sorted_keys (N): the keys in ascending order; order (N) int64: the point of each sorted slot (an entry outside [0, N) is never dereferenced).
+ * Marks the first slot of every key, scans, and accumulates; leaves count = C on the device and, if wanted, cluster (N) int32 per POINT (-1 = none).
+ * `temp` carries the sums to envgs_points_voxel_finish.  The caller reads C back (the one host sync) and sizes the output. */
+ENVGS_API int envgs_points_voxel_cluster(uint32_t N, const float *points, float ox, float oy, float oz, float cell, int32_t nx, int32_t ny, int32_t nz,
+                                         const int64_t *sorted_keys, const int64_t *order, void *temp, size_t temp_bytes, int32_t *cluster,
+                                         uint32_t *count, void *stream);
+
+/* out (C,3): the representatives, C <= N the count read back; a row at or beyond the counted clusters is left alone. */
+ENVGS_API int envgs_points_voxel_finish(uint32_t N, const float *points, float ox, float oy, float oz, float cell, int32_t nx, int32_t ny, int32_t nz,
+                                        void *temp, size_t temp_bytes, uint32_t C, float *out, void *stream);
+
+/* inside (N) uint8 by rule 5.  polygon: (M,3) doubles ON THE DEVICE, 3 <= M <= ENVGS_POLYGON_MAX.  N = 0 is valid.  An axis outside 0 .. 2, an M out
+ * of range, a NULL polygon, a bound that is NaN: ENVGS_ERR_BAD_ARG before any GPU work. */
+ENVGS_API int envgs_points_in_polygon(uint32_t N, const float *points, int32_t axis, double axis_min, double axis_max, uint32_t M, const double *polygon,
+                                      uint8_t *inside, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
