@@ -22,6 +22,52 @@ def _stream(dev):
     return _lib.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
+# ---- argument checks of the entries that hand raw pointers to a one-lane-per-element kernel (reflect, blend, the bounce trio, surfel_quads).
+# Shapes, index dtypes and devices first (ValueError), then the device kind (RuntimeError: no CPU path); all of it before the library is touched.
+# The VALUES of sel / idx (unique, inside [0, R)) are not checked: that would read them back to the host.  They stay the caller's promise.
+def _need_gpu(t):
+    if t.device.type != "cuda":
+        raise RuntimeError("envgs_amd.fused needs tensors on the GPU; there is no CPU path")
+
+
+def _check_devices(fn, first, **others):
+    for name, t in others.items():
+        if t.device != first.device:
+            raise ValueError("%s: %s is on %s, the call is on %s" % (fn, name, t.device, first.device))
+
+
+def _check_image(fn, name, t, channels):
+    if t.dim() != 3 or t.shape[0] not in channels or t.shape[1] < 1 or t.shape[2] < 1:
+        raise ValueError("%s: %s must be (%s,H,W), got %s" % (fn, name, "|".join(str(c) for c in channels), tuple(t.shape)))
+    return int(t.shape[1]), int(t.shape[2])
+
+
+def _check_numel(fn, n, what, **ts):
+    for name, t in ts.items():
+        if t.numel() != n:
+            raise ValueError("%s: %s must hold %s = %d elements, got %s" % (fn, name, what, n, tuple(t.shape)))
+
+
+def _check_rows(fn, widths, **ts):
+    """Per-ray tensors (R, width): 2-D, the stated widths, one row count.  -> R"""
+    R = None
+    for (name, t), w in zip(ts.items(), widths):
+        if t.dim() != 2 or t.shape[1] != w:
+            raise ValueError("%s: %s must be (R,%d), got %s" % (fn, name, w, tuple(t.shape)))
+        if R is None:
+            R = int(t.shape[0])
+        elif t.shape[0] != R:
+            raise ValueError("%s: %s has %d rows, %s has %d" % (fn, name, t.shape[0], next(iter(ts)), R))
+    return R
+
+
+def _check_index(fn, name, t, dev):
+    if t.dtype != torch.int64 or t.dim() != 1:
+        raise ValueError("%s: %s must be a 1-D int64 tensor of row indices, got %s %s" % (fn, name, t.dtype, tuple(t.shape)))
+    if t.device != dev:
+        raise ValueError("%s: %s is on %s, the call is on %s" % (fn, name, t.device, dev))
+
+
 class _ShColors(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, shs, campos, deg, specular, roughness):
@@ -95,6 +141,17 @@ class _Reflect(torch.autograd.Function):
 
 
 def reflect(allmap, ray_o, ray_d, viewmatrix, depth_ratio=0.0):
+    """normal_world (3,H,W), depth (1,H,W), ref_o (H,W,3), ref_d (H,W,3) from allmap (7,H,W), rays of 3 H W elements each and the (4,4) view
+    matrix; one launch each way.  Inputs of another dtype or layout are converted to contiguous float32; gradients come back in the input's dtype
+    and shape.  Non-finite depths: a NaN, +inf or -inf expected depth (allmap[0] / allmap[1]) or median (allmap[5]) becomes 0 and passes no
+    gradient.  The reference's nan_to_num(x, 0, 0) sends -inf to the lowest finite float (-3.4e38) instead; the rasterizer cannot produce one
+    (depths are >= 0.2), so that value is not reproduced (the same rule as surface_normal; include/envgs_glue.h).
+    ValueError: allmap not (7,H,W), a ray tensor not of 3 H W elements, a view matrix not of 16, tensors on different devices."""
+    H, W = _check_image("reflect", "allmap", allmap, (7,))
+    _check_numel("reflect", 3 * H * W, "3 H W", ray_o=ray_o, ray_d=ray_d)
+    _check_numel("reflect", 16, "4 x 4", viewmatrix=viewmatrix)
+    _check_devices("reflect", allmap, ray_o=ray_o, ray_d=ray_d, viewmatrix=viewmatrix)
+    _need_gpu(allmap)
     return _Reflect.apply(allmap, ray_o, ray_d, viewmatrix, depth_ratio)
 
 
@@ -145,22 +202,25 @@ _FACES = {}
 
 def surfel_quads(means3D, scales, rotations):
     """get_disks (optix_utils.py:39-69) in one launch: v (4P,3) f32, f (2P,3) i32.  No gradient flows through the quads (they only seed the
-    acceleration structure); the face table depends on P alone and is cached."""
+    acceleration structure); the face table depends on P alone and is cached (the last 8 sizes; a table a caller still holds stays valid).
+    ValueError: means3D / scales / rotations not (P,3) / (P,2) / (P,4) with one P, or on different devices."""
+    P = _check_rows("surfel_quads", (3, 2, 4), means3D=means3D, scales=scales, rotations=rotations)
+    _check_devices("surfel_quads", means3D, scales=scales, rotations=rotations)
+    _need_gpu(means3D)
     lib = _lib.load()
     dev = means3D.device
-    if dev.type != "cuda":
-        raise RuntimeError("envgs_amd.fused needs tensors on the GPU; there is no CPU path")
-    P = means3D.shape[0]
     m, s, q = _f32c(means3D.detach()), _f32c(scales.detach()), _f32c(rotations.detach())
     v = torch.empty(4 * P, 3, dtype=torch.float32, device=dev)
     f = _FACES.get((dev.index, P))
     fresh = f is None
     if fresh:
-        f = _FACES[(dev.index, P)] = torch.empty(2 * P, 3, dtype=torch.int32, device=dev)
-        if len(_FACES) > 8:
-            _FACES.pop(next(iter(_FACES)))
+        f = torch.empty(2 * P, 3, dtype=torch.int32, device=dev)
     p = _lib.ptr
     _lib.check(lib.envgs_surfel_quads(P, p(m), p(s), p(q), p(v), p(f) if fresh else None, _stream(dev)), "envgs_surfel_quads")
+    if fresh:                                             # (cached only once its launch was accepted: a refused call leaves no unwritten table behind)
+        _FACES[(dev.index, P)] = f
+        if len(_FACES) > 8:
+            _FACES.pop(next(iter(_FACES)))
     return v, f
 
 
@@ -193,7 +253,12 @@ class _Blend(torch.autograd.Function):
 
 def blend(img, rgb_env):
     """(1 - s) * img[:3] + s * rgb_env  (H,W,3) from the -ch05 / -ch07 rasterizer output img (C,H,W) = [rgb | specular C-4 | roughness] and the
-    traced colour rgb_env (H,W,3): envgs_sampler.py:474, one launch each way instead of ~20 (include/envgs_glue.h)."""
+    traced colour rgb_env (H,W,3): envgs_sampler.py:474, one launch each way instead of ~20 (include/envgs_glue.h).
+    ValueError: img not (5|7,H,W), rgb_env not of 3 H W elements (any shape of that size, e.g. (1,HW,3), is taken row-major), different devices."""
+    H, W = _check_image("blend", "img", img, (5, 7))
+    _check_numel("blend", 3 * H * W, "3 H W", rgb_env=rgb_env)
+    _check_devices("blend", img, rgb_env=rgb_env)
+    _need_gpu(img)
     return _Blend.apply(img, rgb_env)
 
 
@@ -361,7 +426,10 @@ class _BounceRays(torch.autograd.Function):
         need = ctx.needs_input_grad
         outs = [torch.zeros_like(t) if need[i] else None for i, t in enumerate((ray_o, ray_d, dpt, acc, norm))]
         p = _lib.ptr
-        _lib.check(lib.envgs_bounce_rays_backward(n, p(sel), p(ray_o), p(ray_d), p(dpt), p(acc), p(norm), p(_f32c(g_o2)), p(_f32c(g_d2)),
+        # held in names: a converted copy made inside the call is freed as soon as its address is taken, and the second copy then takes the
+        # first one's block -- both upstream pointers would show g_d2 (any upstream that is not contiguous float32, e.g. the expanded scalar of a sum)
+        g_o2, g_d2 = _f32c(g_o2), _f32c(g_d2)
+        _lib.check(lib.envgs_bounce_rays_backward(n, p(sel), p(ray_o), p(ray_d), p(dpt), p(acc), p(norm), p(g_o2), p(g_d2),
                                                   *[p(t) for t in outs], _stream(ray_o.device)), "envgs_bounce_rays_backward")
         return (*outs, None)
 
@@ -369,7 +437,13 @@ class _BounceRays(torch.autograd.Function):
 def bounce_rays(ray_o, ray_d, dpt, acc, norm, sel):
     """Rays of the next bounce stage from the rows `sel` (unique int64 indices) of a stage's rays (R,3) and outputs dpt / acc (R,1), norm (R,3):
     o2 = o + d dpt/acc, d2 = d - 2 (d.n) n with n = norm/|norm| -- (n,3) each; differentiable in everything but `sel`; one launch each way
-    (include/envgs_glue.h: envgs_bounce_rays_forward)."""
+    (include/envgs_glue.h: envgs_bounce_rays_forward).  The VALUES of `sel` (unique, inside [0, R)) are the caller's promise: checking them
+    would read them back to the host.  ValueError: per-ray tensors that are not (R,3) (R,3) (R,1) (R,1) (R,3) with one R; a `sel` that is not a
+    1-D int64 tensor on the same device."""
+    _check_rows("bounce_rays", (3, 3, 1, 1, 3), ray_o=ray_o, ray_d=ray_d, dpt=dpt, acc=acc, norm=norm)
+    _check_devices("bounce_rays", ray_o, ray_d=ray_d, dpt=dpt, acc=acc, norm=norm)
+    _check_index("bounce_rays", "sel", sel, ray_o.device)
+    _need_gpu(ray_o)
     return _BounceRays.apply(ray_o, ray_d, dpt, acc, norm, sel)
 
 
@@ -377,6 +451,8 @@ class _BounceBlend(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rgb, aux, col_next, sel):
         lib = _lib.load()
+        if rgb.device.type != "cuda":
+            raise RuntimeError("envgs_amd.fused needs tensors on the GPU; there is no CPU path")
         rgb, aux, col_next = _f32c(rgb), _f32c(aux), _f32c(col_next)
         sel = sel.contiguous()
         col = rgb.clone()
@@ -403,14 +479,41 @@ class _BounceBlend(torch.autograd.Function):
 
 def bounce_blend(rgb, aux, col_next, sel):
     """A stage's colour with the next stage blended in at the rows that bounced: rgb (R,3) with rows sel replaced by
-    (1 - s) rgb[sel] + s col_next, s = aux[sel, 0]; differentiable in rgb, aux, col_next (include/envgs_glue.h: envgs_bounce_blend_forward)."""
+    (1 - s) rgb[sel] + s col_next, s = aux[sel, 0]; differentiable in rgb, aux, col_next (include/envgs_glue.h: envgs_bounce_blend_forward).
+    The VALUES of `sel` (unique, inside [0, R)) are the caller's promise, as for bounce_rays.  ValueError: rgb / aux not (R,3) / (R,2) with one
+    R; col_next not (sel.numel(), 3); a `sel` that is not a 1-D int64 tensor on the same device."""
+    _check_rows("bounce_blend", (3, 2), rgb=rgb, aux=aux)
+    _check_index("bounce_blend", "sel", sel, rgb.device)
+    if col_next.dim() != 2 or tuple(col_next.shape) != (sel.numel(), 3):
+        raise ValueError("bounce_blend: col_next must be (%d,3), one row per index of sel, got %s" % (sel.numel(), tuple(col_next.shape)))
+    _check_devices("bounce_blend", rgb, aux=aux, col_next=col_next)
+    _need_gpu(rgb)
     return _BounceBlend.apply(rgb, aux, col_next, sel)
 
 
 def bounce_pack_mid(mid, k, stages, idx, ray_o, ray_d, dpt, acc, norm, aux, rgb):
-    """Write stage k's 16 `mid` channels [o | d | dpt | acc | norm | aux | rgb] into mid (R, 16 * stages) at rows idx (None: row i).  No gradient."""
+    """Write stage k's 16 `mid` channels [o | d | dpt | acc | norm | aux | rgb] into mid (R, 16 * stages) at rows idx (None: row i).  No gradient.
+    The kernel stores 16-byte vectors through mid + idx[i] * 16 stages + 16 k, so `mid` must be the float32 contiguous (R, 16 stages) tensor itself
+    (16-byte aligned), not a column slice or a copy; the VALUES of idx (unique, inside [0, R)) are the caller's promise.  ValueError: such a
+    `mid`; k outside [0, stages); stage tensors that are not (n,3) (n,3) (n,1) (n,1) (n,3) (n,2) (n,3) with one n; an idx that is not a 1-D
+    int64 tensor of n indices on the same device; idx = None with n > R."""
+    stages, k = int(stages), int(k)
+    if stages < 1 or not 0 <= k < stages:
+        raise ValueError("bounce_pack_mid: stage k = %d outside [0, stages = %d)" % (k, stages))
+    if mid.dtype != torch.float32 or mid.dim() != 2 or mid.shape[1] != 16 * stages or not mid.is_contiguous() or mid.data_ptr() % 16:
+        raise ValueError("bounce_pack_mid: mid must be a contiguous, 16-byte aligned float32 (R,%d) tensor, got %s %s with strides %s"
+                         % (16 * stages, mid.dtype, tuple(mid.shape), tuple(mid.stride())))
+    n = _check_rows("bounce_pack_mid", (3, 3, 1, 1, 3, 2, 3), ray_o=ray_o, ray_d=ray_d, dpt=dpt, acc=acc, norm=norm, aux=aux, rgb=rgb)
+    _check_devices("bounce_pack_mid", mid, ray_o=ray_o, ray_d=ray_d, dpt=dpt, acc=acc, norm=norm, aux=aux, rgb=rgb)
+    if idx is not None:
+        _check_index("bounce_pack_mid", "idx", idx, mid.device)
+        if idx.numel() != n:
+            raise ValueError("bounce_pack_mid: idx holds %d indices for %d rows" % (idx.numel(), n))
+    elif n > mid.shape[0]:
+        raise ValueError("bounce_pack_mid: %d rows do not fit a mid of %d" % (n, mid.shape[0]))
+    _need_gpu(mid)
     lib = _lib.load()
     p = _lib.ptr
     ts = [_f32c(t.detach()) for t in (ray_o, ray_d, dpt, acc, norm, aux, rgb)]
-    _lib.check(lib.envgs_bounce_pack_mid(int(ts[0].shape[0]), p(idx.contiguous()) if idx is not None else None, int(stages), int(k), *[p(t) for t in ts],
-                                         p(mid), _stream(mid.device)), "envgs_bounce_pack_mid")
+    idx = None if idx is None else idx.contiguous()       # (held in a name: a copy made inside the call would be freed before the launch)
+    _lib.check(lib.envgs_bounce_pack_mid(n, p(idx), stages, k, *[p(t) for t in ts], p(mid), _stream(mid.device)), "envgs_bounce_pack_mid")

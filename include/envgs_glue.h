@@ -38,6 +38,10 @@ ENVGS_API int envgs_sh_colors_backward(int32_t P, int32_t sh_degree, int32_t sh_
 /*
  * Per pixel, from allmap (7,H,W) [0 depth*alpha, 1 alpha, 2-4 view normal, 5 median depth], rays (H,W,3) and the view matrix
  * (4,4, row-vector convention as everywhere): normal_world (3,H,W), depth (1,H,W), ref_o (H,W,3), ref_d (H,W,3).
+ * Non-finite depths, as for envgs_surface_normal_* below: a NaN, +inf AND -inf expected depth (allmap[0] / allmap[1]) or median depth
+ * (allmap[5]) becomes 0 and passes no gradient (dallmap[0], [1] resp. [5] are exactly 0 there).  The reference's nan_to_num(x, 0, 0) sends -inf
+ * to the lowest finite float instead; the rasterizer cannot produce one (depths are >= 0.2), so that value is not reproduced.
+ * The backward's dnormal_world, ddepth, dref_o, dref_d may each be NULL (that output did not reach the loss).
  */
 ENVGS_API int envgs_reflect_forward(int32_t H, int32_t W, float depth_ratio, const float *allmap, const float *ray_o,
                                     const float *ray_d, const float *viewmatrix, float *normal_world, float *depth,
@@ -126,6 +130,10 @@ ENVGS_API int envgs_blend_filtered_backward(int32_t H, int32_t W, int32_t channe
  * Backwards: g_ray_o / g_ray_d / g_dpt / g_acc / g_norm / g_aux are (R_k, .) buffers the caller has ZEROED (rows outside sel receive nothing);
  * g_rgb is the caller's COPY of g_col (rows outside sel pass through).  Any gradient pointer may be NULL.  One launch each.
  * envgs_bounce_pack_mid: the 16 `mid` channels [o 3 | d 3 | dpt | acc | norm 3 | aux 2 | rgb 3] of stage k (of `stages`) at rows idx (NULL: row i).
+ *   mid is the contiguous (R, 16 * stages) float buffer, 16-byte aligned: the rows are stored as four 16-byte vectors at mid + idx[i] * 16 * stages + 16 * k.
+ * The VALUES of sel / idx are the caller's promise -- unique and inside [0, R_k): no entry reads them back to check (that would synchronise
+ * with the host), and the kernels index the (R_k, .) buffers with them as they are.  The Python front end (envgs_amd/fused.py) checks what
+ * it can see without the device: shapes, the int64 dtype, the device, the layout of mid.
  */
 ENVGS_API int envgs_bounce_rays_forward(int32_t n, const int64_t *sel, const float *ray_o, const float *ray_d, const float *dpt, const float *acc,
                                         const float *norm, float *o2, float *d2, void *stream);
