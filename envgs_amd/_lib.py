@@ -142,6 +142,16 @@ class CullViews(ctypes.Structure):
     _fields_ = [("count", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("v", CullView * 8)]
 
 
+class FuseSource(ctypes.Structure):
+    """struct envgs_fuse_source (include/envgs_mesh.h)."""
+    _fields_ = [("depth", ctypes.c_void_p), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("fwd", ctypes.c_float * 12), ("back", ctypes.c_float * 12)]
+
+
+class FuseSources(ctypes.Structure):
+    """struct envgs_fuse_sources (include/envgs_mesh.h)."""
+    _fields_ = [("count", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("v", FuseSource * 8)]
+
+
 # every symbol include/*.h declares: name -> (restype, argtypes)
 _P = c_void_p
 SYMBOLS = {
@@ -234,6 +244,11 @@ SYMBOLS = {
     "envgs_points_voxel_cluster": (c_int, [c_uint32, _P] + [ctypes.c_float] * 4 + [ctypes.c_int32] * 3 + [_P, _P, _P, c_size_t, _P, _P, _P]),
     "envgs_points_voxel_finish": (c_int, [c_uint32, _P] + [ctypes.c_float] * 4 + [ctypes.c_int32] * 3 + [_P, c_size_t, c_uint32, _P, _P]),
     "envgs_points_in_polygon": (c_int, [c_uint32, _P, ctypes.c_int32, ctypes.c_double, ctypes.c_double, c_uint32, _P, _P, _P]),
+    "envgs_fuse_consistency": (c_int, [ctypes.c_int32, ctypes.c_int32, _P, ctypes.POINTER(FuseSources), ctypes.c_float, ctypes.c_float, ctypes.c_int32,
+                                       _P, _P, _P]),
+    "envgs_fuse_temp_bytes": (c_size_t, [ctypes.c_int32] * 3),
+    "envgs_fuse_count": (c_int, [ctypes.c_int32] * 3 + [_P, _P, _P, c_uint32, ctypes.c_float, _P, _P, _P, c_size_t, _P, _P]),
+    "envgs_fuse_emit": (c_int, [ctypes.c_int32] * 3 + [_P, _P, _P, c_size_t, _P, _P, _P, c_uint32] + [_P] * 4 + [_P]),
     "envgs_l1_ssim_partial_count": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "envgs_l1_ssim_forward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P]),
     "envgs_l1_ssim_backward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, ctypes.c_float, ctypes.c_float, _P, _P]),

@@ -31,6 +31,8 @@ COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++20", "-fPIC", "-munsafe-fp-a
 # mesh_eval.hip: likewise the face area (products, differences, IEEE sqrt), the samples, the cell of a point and the squared distances
 # mesh_register.hip: the same cell and squared distance (csrc/mesh_points.h is one text for both files), the fp32 transformation, the double
 # products of the registration sums and the crossing test of the crop volume
+# mesh_fuse.hip is NOT in the table: it applies float64-composed maps where the reference chains fp32 matrix products, so it agrees with the
+# reference to a measured band and never to the bit; contraction only moves values inside that band ("Depth fusion")
 _NO_SLP = ["-fno-slp-vectorize"]
 EXTRA = {"raster_project.hip": ["-ffp-contract=off"], "raster_project_bwd.hip": ["-ffp-contract=off"], "densify_device.hip": ["-ffp-contract=off"],
          "mesh.hip": ["-ffp-contract=off"], "mesh_simplify.hip": ["-ffp-contract=off"], "mesh_eval.hip": ["-ffp-contract=off"],

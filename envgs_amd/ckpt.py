@@ -240,3 +240,69 @@ def load_mesh_ply(path):
     vertices = np.stack([vt["x"], vt["y"], vt["z"]], axis=1).astype(np.float32)
     colors = np.stack([vt["red"], vt["green"], vt["blue"]], axis=1) if "red" in vdt.names else None
     return vertices, np.ascontiguousarray(ft["i"]).astype(np.int32).reshape(-1, 3), colors
+
+
+def save_points_ply(path, points, colors=None, normals=None):
+    """Binary little-endian PLY of a point cloud (mesh.fuse_depth_points): `x y z` float, then `nx ny nz` float when normals (N,3) are given, then
+    `red green blue` uchar = round(clamp(c, 0, 1) 255) when colors (N,3) are given -- save_mesh_ply's quantisation.  Tensors or arrays, any device."""
+    arr = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    v = arr(points).astype("<f4").reshape(-1, 3)
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if normals is not None:
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+    if colors is not None:
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    vt = np.empty(v.shape[0], dtype=fields)
+    vt["x"], vt["y"], vt["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if normals is not None:
+        n = arr(normals).astype("<f4").reshape(-1, 3)
+        if n.shape[0] != v.shape[0]:
+            raise ValueError("save_points_ply: %d normals for %d points" % (n.shape[0], v.shape[0]))
+        vt["nx"], vt["ny"], vt["nz"] = n[:, 0], n[:, 1], n[:, 2]
+    if colors is not None:
+        c = np.rint(np.clip(arr(colors).astype(np.float64).reshape(-1, 3), 0.0, 1.0) * 255.0).astype("u1")
+        if c.shape[0] != v.shape[0]:
+            raise ValueError("save_points_ply: %d colours for %d points" % (c.shape[0], v.shape[0]))
+        vt["red"], vt["green"], vt["blue"] = c[:, 0], c[:, 1], c[:, 2]
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % v.shape[0]
+              + "".join("property %s %s\n" % ("float" if ty == "<f4" else "uchar", nm) for nm, ty in fields) + "end_header\n")
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        fh.write(vt.tobytes())
+
+
+def load_points_ply(path):
+    """-> (points (N,3) float32, colors (N,3) uint8 or None, normals (N,3) float32 or None) numpy arrays, from a binary little-endian PLY whose
+    first element is `vertex` with scalar properties (what save_points_ply writes; further elements are ignored)."""
+    with open(path, "rb") as fh:
+        if fh.readline().strip() != b"ply":
+            raise ValueError("%s is not a PLY file" % path)
+        fmt, count, props, cur = None, None, [], None
+        while True:
+            line = fh.readline()
+            if not line:
+                raise ValueError("PLY header of %s is not terminated" % path)
+            w = line.decode("ascii").split()
+            if not w or w[0] == "comment":
+                continue
+            if w[0] == "format":
+                fmt = w[1]
+            elif w[0] == "element":
+                cur = w[1] if count is None else "other"
+                if cur == "vertex":
+                    count = int(w[2])
+            elif w[0] == "property" and cur == "vertex":
+                if w[1] == "list":
+                    raise ValueError("load_points_ply: list property on the vertices of %s" % path)
+                props.append((w[2], _PLY_TYPES[w[1]]))
+            elif w[0] == "end_header":
+                break
+        if fmt != "binary_little_endian" or count is None:
+            raise ValueError("load_points_ply reads binary little-endian files whose first element is `vertex`")
+        vdt = np.dtype([(nm, ty if ty[1] == "1" else "<" + ty) for nm, ty in props])
+        vt = np.frombuffer(fh.read(vdt.itemsize * count), dtype=vdt, count=count)
+    pick = lambda names, dt: np.stack([vt[n] for n in names], axis=1).astype(dt) if all(n in vdt.names for n in names) else None
+    points = pick(("x", "y", "z"), np.float32)
+    if points is None:
+        raise ValueError("load_points_ply: %s has no x y z" % path)
+    return points, pick(("red", "green", "blue"), np.uint8), pick(("nx", "ny", "nz"), np.float32)

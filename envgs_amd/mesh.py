@@ -17,6 +17,8 @@ tests/mesh_oracle.py restates them independently.  There is no CPU path: CPU ten
                        observed=(obs_mask, origin, voxel), box=(lo, hi), plane=plane)       # the DTU protocol: thin_points() and the filters
     tnt = evaluate_tnt(mesh, scan_points, tau=0.003, init=T_colmap_to_scan, crop=load_crop_volume("Barn.json"), density=4e5)
                                                                                             # Tanks and Temples: register(), voxel_downsample(), the crop
+    cloud, maps = fuse_surfel_points(cameras, base, sh_degree=3)     # csrc/mesh_fuse.hip: depth-map fusion, the route without a volume -- PARITY
+                                                                     # PINNED by tests/golden/fuse_golden.npz (the section "depth fusion" below)
 """
 import math
 from types import SimpleNamespace
@@ -1059,3 +1061,257 @@ def evaluate_tnt(mesh_or_points, scan_points, tau, init=None, crop=None, density
     out = evaluate(moved, voxel_downsample(scan_cropped, 0.5 * tau), max_distance=tau, threshold=tau)
     out.transformation, out.registrations = T, registrations
     return out
+
+
+# ---- depth fusion (csrc/mesh_fuse.hip; include/envgs_mesh.h, "depth fusion") ----------------------------------------------------------------------------
+# PARITY PINNED by tests/golden/fuse_golden.npz: the second route from a trained scene to a point cloud, the reference's scripts/fusion/depth_fusion.py
+# (fusion_utils.py: depth_reprojection, depth_geometry_consistency, compute_consistency).  No voxel size and no iso-surface: every view's depth is checked
+# against its nearest views, the agreeing depths are averaged and the surviving pixels are back-projected.
+FUSE_MAX_SOURCES = 255        # the count is a byte
+
+
+def _fuse_cameras(cameras, what):
+    """-> (K, R, T) float64 arrays (V,3,3), (V,3,3), (V,3) on the host."""
+    cameras = list(cameras)
+    if not cameras:
+        raise ValueError("%s: at least one camera is needed" % what)
+    host = lambda name, shape: torch.stack([torch.as_tensor(getattr(c, name)).reshape(shape) for c in cameras]).detach().cpu().double().numpy()
+    K, R, T = host("K", (3, 3)), host("R", (3, 3)), host("T", (3,))                  # one copy per attribute, not per camera
+    if not (np.isfinite(K).all() and np.isfinite(R).all() and np.isfinite(T).all()):
+        raise ValueError("%s: camera parameters must be finite" % what)
+    return K, R, T
+
+
+def nearest_views(cameras, n):
+    """For each camera the min(n, V - 1) OTHER cameras by ascending distance between the centres -R^T T, in float64 on the host; ties go to the
+    lowest index.  -> (V, min(n, V-1)) int64 (host).  For rigs with distinct centres this is the reference's
+    compute_camera_similarity(c2ws, c2ws)[1][:, 1:1+n].  Deviation: with coincident centres the reference's sort of 1 / distance sees several
+    infinities and its [1:] may drop a camera other than the view itself; here the view itself is always the one left out."""
+    _, R, T = _fuse_cameras(cameras, "nearest_views")
+    V, n = R.shape[0], int(n)
+    if n < 0:
+        raise ValueError("nearest_views: n must not be negative")
+    C = -np.einsum("vji,vj->vi", R, T)
+    d = np.linalg.norm(C[:, None, :] - C[None, :, :], axis=-1)
+    out = np.empty((V, min(n, V - 1)), np.int64)
+    for v in range(V):
+        order = [j for j in np.argsort(d[v], kind="stable") if j != v]
+        out[v] = order[:out.shape[1]]
+    return torch.from_numpy(out)
+
+
+def fuse_min_count(geo_sum_thresh, S):
+    """The smallest integer n with n >= geo_sum_thresh * S in Python float arithmetic: the reference's `geo_mask_sum >= geo_sum_thresh * S`."""
+    return max(0, math.ceil(float(geo_sum_thresh) * S))         # math.ceil of a float is exact
+
+
+def fuse_view_maps(K, R, T):
+    """(V,12) float64: A_v = R_v^T K_v^-1 row major, then c_v = -R_v^T T_v (rule 5)."""
+    Rt = np.swapaxes(R, -1, -2)
+    return np.concatenate([(Rt @ np.linalg.inv(K)).reshape(-1, 9), -(Rt @ T[..., None])[..., 0]], axis=-1)
+
+
+def fuse_pair_maps(K, R, T, sources):
+    """The two affine maps of include/envgs_mesh.h ("depth fusion", rule 1) for every (view r, source s = sources[r, k]) of a (V,S) table, composed
+    in float64: fwd carries a pixel and depth of r into the image of s, back the other way.  -> (fwd, back), (V,S,12) each: A row major, then b."""
+    Kinv = np.linalg.inv(K)
+    Ks, Ts, Kis, col = K[sources], T[sources], Kinv[sources], lambda a: a[..., None]         # (V,S,...)
+    Rab = R[sources] @ np.swapaxes(R, -1, -2)[:, None]                                        # R_s R_r^T
+    Rba = np.swapaxes(Rab, -1, -2)
+    fwd_A = Ks @ Rab @ Kinv[:, None]
+    fwd_b = (Ks @ col(Ts - (Rab @ col(T[:, None]))[..., 0]))[..., 0]
+    back_A = K[:, None] @ Rba @ Kis
+    back_b = (K[:, None] @ col(T[:, None] - (Rba @ col(Ts))[..., 0]))[..., 0]
+    V, S = sources.shape
+    return np.concatenate([fwd_A.reshape(V, S, 9), fwd_b], axis=-1), np.concatenate([back_A.reshape(V, S, 9), back_b], axis=-1)
+
+
+_FUSE_SOURCE_DT = np.dtype([("depth", "<u8"), ("H", "<i4"), ("W", "<i4"), ("fwd", "<f4", (12,)), ("back", "<f4", (12,))])
+_FUSE_SOURCES_DT = np.dtype([("count", "<i4"), ("reserved0", "<i4"), ("v", _FUSE_SOURCE_DT, (MAX_VIEWS,))])
+
+
+def _fuse_packs(K, R, T, src, depth_ptr, H, W):
+    """The envgs_fuse_sources structs of a call, filled at once: (V, launches per view) records that _lib.FuseSources reads in place."""
+    assert _FUSE_SOURCES_DT.itemsize == _lib.ctypes.sizeof(_lib.FuseSources)
+    V, S = src.shape
+    packs = np.zeros((V, max(1, -(-S // MAX_VIEWS))), _FUSE_SOURCES_DT)
+    if S:
+        fwd, back = fuse_pair_maps(K, R, T, src)
+        for q in range(packs.shape[1]):
+            cols = slice(q * MAX_VIEWS, min(S, (q + 1) * MAX_VIEWS))
+            n = cols.stop - cols.start
+            packs["count"][:, q] = n
+            v = packs["v"][:, q, :n]
+            v["depth"] = depth_ptr + src[:, cols].astype(np.uint64) * np.uint64(4 * H * W)
+            v["H"], v["W"] = H, W
+            v["fwd"], v["back"] = fwd[:, cols], back[:, cols]
+    return packs
+
+
+def _fuse_thresholds(geo_abs_thresh, geo_rel_thresh, geo_sum_thresh, pho_abs_thresh, what):
+    th = [float(geo_abs_thresh), float(geo_rel_thresh), float(geo_sum_thresh), float(pho_abs_thresh)]
+    if not all(math.isfinite(t) and math.isfinite(_f32(t)) for t in th):
+        raise ValueError("%s: the thresholds must be finite" % what)
+    return th
+
+
+def _fuse_depth(depth, n_cameras, what):
+    """Shape, dtype and size first, the device last.  A list of (H,W) maps is stacked, if they share one size."""
+    if isinstance(depth, (list, tuple)):
+        if not depth or not all(isinstance(d, torch.Tensor) and d.dim() == 2 for d in depth):
+            raise ValueError("%s: depth must be a (V,H,W) float32 tensor or a list of (H,W) maps" % what)
+        if len({tuple(d.shape) for d in depth}) != 1:
+            raise ValueError("%s: all views of a call must share one size" % what)
+        depth = torch.stack(list(depth))
+    if not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32 or depth.dim() != 3:
+        raise ValueError("%s: depth must be a (V,H,W) float32 tensor; all views of a call share one size" % what)
+    V, H, W = depth.shape
+    if V != n_cameras or H < 1 or W < 1:
+        raise ValueError("%s: depth must hold one non-empty (H,W) map per camera" % what)
+    if V * H * W >= 2 ** 31:
+        raise ValueError("%s: V H W must be below 2^31" % what)
+    return depth
+
+
+def _fuse_sources(sources, V, what):
+    src = np.asarray(sources.detach().cpu().numpy() if isinstance(sources, torch.Tensor) else sources)
+    if src.size == 0:
+        src = np.zeros((V, 0), np.int64)
+    if src.ndim != 2 or src.shape[0] != V or src.dtype.kind not in "iu":
+        raise ValueError("%s: sources must be a (V,S) table of view indices" % what)
+    if src.shape[1] > FUSE_MAX_SOURCES:
+        raise ValueError("%s: at most %d sources per view" % (what, FUSE_MAX_SOURCES))
+    src = src.astype(np.int64)
+    if ((src < 0) | (src >= V)).any():
+        raise ValueError("%s: a source index is out of range" % what)
+    if (src == np.arange(V)[:, None]).any():
+        raise ValueError("%s: a view cannot be its own source" % what)
+    return src
+
+
+def _consistency(depth, cameras, sources, n_srcs, geo_abs_thresh, geo_rel_thresh, geo_sum_thresh, pho_abs_thresh, what):
+    cameras = list(cameras)
+    K, R, T = _fuse_cameras(cameras, what)
+    depth = _fuse_depth(depth, len(cameras), what)
+    V, H, W = depth.shape
+    abs_t, rel_t, sum_t, pho_t = _fuse_thresholds(geo_abs_thresh, geo_rel_thresh, geo_sum_thresh, pho_abs_thresh, what)
+    src = _fuse_sources(nearest_views(cameras, n_srcs) if sources is None else sources, V, what)
+    S = src.shape[1]
+    if depth.device.type != "cuda":
+        raise ValueError("%s: depth must be on the GPU; there is no CPU path" % what)
+    depth = depth.contiguous()
+    lib = _lib.load()
+    dev, p, s = depth.device, _lib.ptr, _stream(depth.device)
+    count = torch.empty(V, H, W, dtype=torch.uint8, device=dev)
+    total = torch.empty(V, H, W, dtype=torch.float32, device=dev)
+    packs = _fuse_packs(K, R, T, src, depth.data_ptr(), H, W)
+    for r in range(V):
+        for q in range(packs.shape[1]):
+            pack = _lib.FuseSources.from_buffer(packs[r, q:q + 1])
+            _lib.check(lib.envgs_fuse_consistency(H, W, p(depth[r]), pack, abs_t, rel_t, int(q > 0), p(count[r]), p(total[r]), s),
+                       "envgs_fuse_consistency")
+    min_count = fuse_min_count(sum_t, S)
+    tb = lib.envgs_fuse_temp_bytes(V, H, W)
+    temp = torch.empty(tb, dtype=torch.uint8, device=dev)
+    depth_avg = torch.empty(V, H, W, dtype=torch.float32, device=dev)
+    final = torch.empty(V, H, W, dtype=torch.bool, device=dev)
+    n = torch.empty(1, dtype=torch.int64, device=dev)
+    _lib.check(lib.envgs_fuse_count(V, H, W, p(depth), p(count), p(total), min(min_count, 2 ** 32 - 1), pho_t, p(depth_avg), p(final), p(temp), tb, p(n), s),
+               "envgs_fuse_count")
+    out = SimpleNamespace(depth_avg=depth_avg, count=count, photo_mask=None, geo_mask=None, final_mask=final)
+    return out, SimpleNamespace(depth=depth, K=K, R=R, T=T, temp=temp, tb=tb, n=n, min_count=min_count, pho=pho_t)
+
+
+def depth_consistency(depth, cameras, sources=None, n_srcs=4, geo_abs_thresh=1.0, geo_rel_thresh=0.01, geo_sum_thresh=0.75, pho_abs_thresh=0.0):
+    """The multi-view consistency check of the reference's depth fusion (include/envgs_mesh.h, "depth fusion"; the defaults are those of
+    scripts/fusion/depth_fusion.py).  depth: (V,H,W) float32 device tensor of z-depths, <= 0 = no depth; cameras: V namespaces with K (3,3),
+    R (3,3) world -> camera and T (synth.make_camera); sources: a (V,S) index tensor or list of lists, S <= 255, default nearest_views(cameras,
+    n_srcs).  Each pixel of each view is projected into its sources with its depth, the source depth is sampled there as grid_sample does
+    (bilinear, border) and brought back; a source agrees iff the pixel returns within geo_abs_thresh pixels, the returned depth is within
+    geo_rel_thresh relative and the sample is positive.
+    -> namespace(depth_avg (V,H,W) f32: the mean of the pixel's depth and the agreeing returned depths; count (V,H,W) u8: the agreeing sources;
+       geo_mask: count >= geo_sum_thresh S; photo_mask: depth > pho_abs_thresh; final_mask: both), the masks bool.
+    S = 0 gives depth_avg = depth and geo_mask all true, as the reference's expressions do.  All views share one size.  A pixel whose depth is not
+    finite or not positive agrees with nothing.  No host sync: the camera parameters are read on the host, where synth.make_camera keeps them
+    (a K, R or T that lives on the device is copied, which waits for it)."""
+    out, ctx = _consistency(depth, cameras, sources, n_srcs, geo_abs_thresh, geo_rel_thresh, geo_sum_thresh, pho_abs_thresh, "depth_consistency")
+    if 0 < ctx.min_count <= 255:
+        out.geo_mask = out.count >= ctx.min_count
+    else:                                                       # nothing to reach, or more than a byte can count
+        out.geo_mask = torch.full_like(out.final_mask, ctx.min_count <= 0)
+    out.photo_mask = ctx.depth > _f32(ctx.pho)
+    return out
+
+
+def _fuse_map(t, shape, like, name, what):
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or t.device != like.device or t.dtype != torch.float32 or tuple(t.shape) != shape:
+        raise ValueError("%s: %s must be a (V,3,H,W) float32 tensor on the depth's device" % (what, name))
+    return t.contiguous()
+
+
+def fuse_depth_points(depth, cameras, rgb=None, normal=None, return_index=False, **thresholds):
+    """depth_consistency() followed by the back-projection of the pixels of final_mask, in ascending (view, row, column) order -- the order of the
+    reference's torch.cat over views of final_mask.view(-1).nonzero():  point = c_v + depth_avg (R_v^T K_v^-1 (x + 0.5, y + 0.5, 1)).
+    rgb, normal: (V,3,H,W) float32 maps gathered at the kept pixels, or None.  thresholds: the keyword arguments of depth_consistency().
+    -> (points (N,3), colors (N,3) or None, normals (N,3) or None), plus index (N,) int64, the flat (view H + row) W + column, with return_index.
+    One host sync per call: the read-back of N (the reference's loop makes one per view)."""
+    known = dict(sources=None, n_srcs=4, geo_abs_thresh=1.0, geo_rel_thresh=0.01, geo_sum_thresh=0.75, pho_abs_thresh=0.0)
+    if set(thresholds) - set(known):
+        raise TypeError("fuse_depth_points: unknown arguments %s" % sorted(set(thresholds) - set(known)))
+    out, ctx = _consistency(depth, cameras, what="fuse_depth_points", **dict(known, **thresholds))
+    V, H, W = ctx.depth.shape
+    rgb = _fuse_map(rgb, (V, 3, H, W), ctx.depth, "rgb", "fuse_depth_points")
+    normal = _fuse_map(normal, (V, 3, H, W), ctx.depth, "normal", "fuse_depth_points")
+    dev = ctx.depth.device
+    view_maps = torch.from_numpy(fuse_view_maps(ctx.K, ctx.R, ctx.T).astype(np.float32)).to(dev)
+    N = int(ctx.n.item())                                       # the one host sync
+    new = lambda dt: torch.empty(N, 3, dtype=dt, device=dev)
+    points = new(torch.float32)
+    colors = new(torch.float32) if rgb is not None else None
+    normals = new(torch.float32) if normal is not None else None
+    index = torch.empty(N, dtype=torch.int64, device=dev) if return_index else None
+    p = _lib.ptr
+    _lib.check(_lib.load().envgs_fuse_emit(V, H, W, p(out.depth_avg), p(out.final_mask), p(ctx.temp), ctx.tb, p(view_maps), p(rgb), p(normal), N,
+                                           p(points), p(colors), p(normals), p(index), _stream(dev)), "envgs_fuse_emit")
+    return (points, colors, normals, index) if return_index else (points, colors, normals)
+
+
+def render_surface_maps(cameras, base, sh_degree, depth_ratio=0.0, scale_modifier=1.0):
+    """Renders `base` from every camera as fuse_surfels() does (the same rasterizer call under no_grad) and returns the per-view maps
+    [namespace(depth (H,W), alpha (H,W), rgb (3,H,W), normal (3,H,W))]: normal is the rendered normal allmap[2:5] rotated from view to world space,
+    the expression of envgs_step.base_pass."""
+    import diff_surfel_rasterization_wet as pkg
+    _need_gpu(base["means3D"], "render_surface_maps")
+    dev = base["means3D"].device
+    maps = []
+    with torch.no_grad():
+        bg = torch.zeros(3, dtype=torch.float32, device=dev)
+        for cam in cameras:
+            st = pkg.GaussianRasterizationSettings(
+                image_height=cam.image_height, image_width=cam.image_width, tanfovx=cam.tanfovx, tanfovy=cam.tanfovy, bg=bg,
+                scale_modifier=scale_modifier, viewmatrix=cam.world_view_transform.to(dev), projmatrix=cam.full_proj_transform.to(dev),
+                sh_degree=sh_degree, campos=cam.camera_center.to(dev), prefiltered=False, debug=False)
+            color, _, allmap, _ = pkg.GaussianRasterizer(raster_settings=st)(
+                means3D=base["means3D"], means2D=torch.zeros_like(base["means3D"]), shs=base["shs"], colors_precomp=None,
+                opacities=base["opacities"], scales=base["scales"], rotations=base["rotations"], cov3D_precomp=None)
+            normal = (allmap[2:5].permute(1, 2, 0) @ (cam.world_view_transform.to(dev)[:3, :3].T)).permute(2, 0, 1).contiguous()
+            maps.append(SimpleNamespace(depth=surface_depth(allmap, depth_ratio), alpha=allmap[1], rgb=color[:3].contiguous(), normal=normal))
+    return maps
+
+
+def fuse_surfel_points(cameras, base, sh_degree, alpha_min=0.5, depth_ratio=0.0, scale_modifier=1.0, **thresholds):
+    """From surfels to a fused cloud: render_surface_maps(), the depth zeroed where alpha <= alpha_min (zero is the reference's "no depth" and
+    fails the photometric mask), then fuse_depth_points() with the rendered colour and normal.  All cameras must share one image size.
+    -> (namespace(points, colors, normals, index), maps): the cloud goes straight into evaluate_dtu(), evaluate_tnt(), thin_points() and
+    voxel_downsample(); maps are the rendered maps, with the depth as it was fused."""
+    cameras = list(cameras)
+    maps = render_surface_maps(cameras, base, sh_degree, depth_ratio, scale_modifier)
+    if len({tuple(m.depth.shape) for m in maps}) != 1:
+        raise ValueError("fuse_surfel_points: all cameras must share one image size")
+    for m in maps:
+        m.depth = torch.where(m.alpha > alpha_min, m.depth, torch.zeros_like(m.depth))
+    points, colors, normals, index = fuse_depth_points(torch.stack([m.depth for m in maps]), cameras, rgb=torch.stack([m.rgb for m in maps]),
+                                                       normal=torch.stack([m.normal for m in maps]), return_index=True, **thresholds)
+    return SimpleNamespace(points=points, colors=colors, normals=normals, index=index), maps

@@ -413,6 +413,64 @@ ENVGS_API int envgs_points_voxel_finish(uint32_t N, const float *points, float o
 ENVGS_API int envgs_points_in_polygon(uint32_t N, const float *points, int32_t axis, double axis_min, double axis_max, uint32_t M, const double *polygon,
                                       uint8_t *inside, void *stream);
 
+/* ---- depth fusion: consistency-filtered point clouds from depth maps (csrc/mesh_fuse.hip) -----------------------------------------------------------
+ * PARITY PINNED by tests/golden/fuse_golden.npz: the rules are those of the reference's scripts/fusion/depth_fusion.py and
+ * easyvolcap/utils/fusion_utils.py (depth_reprojection, depth_geometry_consistency, compute_consistency), whose recorded outputs the tests compare
+ * with; tests/mesh_fuse_oracle.py restates them in NumPy float64.  The kernel applies transformations composed on the host in float64 instead of
+ * the reference's chain of matrix products, so it agrees with the reference to rounding ("Depth fusion": the measured band), not to the bit.
+ *
+ * All views of a call share one size H x W; the centre of pixel (x, y) is (xc, yc) = (x + 0.5, y + 0.5).  With K, R, T of a camera (x_cam = R x + T):
+ *
+ * 1. A pair (reference r, source s) carries two affine maps of 12 floats, A (row major, 9) then b (3), composed in float64 and rounded once:
+ *      fwd:   A = K_s R_s R_r^T K_r^-1,   b = K_s (T_s - R_s R_r^T T_r)          p_src = d_ref (A (xc, yc, 1)) + b
+ *      back:  the same with r and s exchanged                                     p_ref = sampled (A (u, v, 1)) + b
+ * 2. Per pair, in fp32:  (u, v) = p_src.xy / p_src.z;  sampled = the source depth at (u, v) as torch's grid_sample gives it with its defaults
+ *    (bilinear, align_corners = False, padding_mode = 'border'):  ix = clip(u - 0.5, 0, W - 1), iy likewise; taps floor and floor + 1; the taps
+ *    inside the image are multiplied by their weights, a weight of 0 included, and added in the order (y0,x0) (y0,x1) (y1,x0) (y1,x1); a tap outside
+ *    the image can only carry the weight 0 and is not read.  z = p_ref.z, (x', y') = p_ref.xy / z.  The pair PASSES iff
+ *      sqrt((x' - xc)^2 + (y' - yc)^2) < geo_abs_thresh   and   |z - d_ref| / d_ref < geo_rel_thresh   and   sampled > 0
+ *    every comparison being false on NaN.  A reference pixel whose depth is not finite or not > 0 passes nothing (the reference lets a negative
+ *    depth pass the relative test; its photometric mask drops the pixel afterwards), and a pair whose u, v or sampled depth is not finite fails.
+ * 3. Per reference pixel: count = the passing sources (saturating at 255), sum = the sum of their z in source order.
+ * 4. depth_avg = (sum + d_ref) / (count + 1);  final = count >= min_count and d_ref > pho_abs_thresh.
+ * 5. The kept pixels in ascending (view, row, column) order give  point = c_v + depth_avg (A_v (xc, yc, 1)),  A_v = R_v^T K_v^-1 and c_v = -R_v^T T_v
+ *    composed in float64 (12 floats per view ON THE DEVICE: A_v row major, then c_v). */
+typedef struct envgs_fuse_source {
+    const float *depth;                       /* (H,W) z-depth of the source view; <= 0 = no measurement */
+    int32_t H, W;                             /* must equal the reference's */
+    float fwd[12];                            /* reference pixel and depth -> source image: A (9), b (3) */
+    float back[12];                           /* source pixel and sampled depth -> reference image */
+} envgs_fuse_source;
+
+typedef struct envgs_fuse_sources {
+    int32_t count;                            /* 0 .. ENVGS_TSDF_MAX_VIEWS */
+    int32_t reserved0;
+    envgs_fuse_source v[ENVGS_TSDF_MAX_VIEWS];
+} envgs_fuse_sources;
+
+/* Rules 2 and 3 for one reference map depth_ref (H,W): count (H,W) uint8 and sum (H,W) float.  accumulate = 0: from zero; != 0: added to what is
+ * there, so that more than ENVGS_TSDF_MAX_VIEWS sources take several calls and the sum stays in source order.  A count outside 0 .. 8, a NULL
+ * pointer, an empty image, a source whose size differs from H x W and H W >= 2^31 return ENVGS_ERR_BAD_ARG and write nothing. */
+ENVGS_API int envgs_fuse_consistency(int32_t H, int32_t W, const float *depth_ref, const envgs_fuse_sources *sources, float geo_abs_thresh,
+                                     float geo_rel_thresh, int32_t accumulate, uint8_t *count, float *sum, void *stream);
+
+/* Scratch bytes of envgs_fuse_count / envgs_fuse_emit: the per-workgroup totals and the scan's scratch (0 unless V, H, W >= 1 and V H W < 2^31). */
+ENVGS_API size_t envgs_fuse_temp_bytes(int32_t V, int32_t H, int32_t W);
+
+/* Rule 4 over all V H W pixels of depth, count, sum (V,H,W): writes depth_avg (V,H,W) float and final_mask (V,H,W) uint8, scans the kept pixels per
+ * workgroup of 256 and leaves total[0] = N as a 64-bit integer on the device; the caller reads it back (the one host sync) and sizes the outputs.
+ * `temp` (16-byte aligned) carries the plan to envgs_fuse_emit and must not be touched in between.  Bad arguments: ENVGS_ERR_BAD_ARG before any GPU
+ * work; a short `temp`: ENVGS_ERR_TEMP_TOO_SMALL. */
+ENVGS_API int envgs_fuse_count(int32_t V, int32_t H, int32_t W, const float *depth, const uint8_t *count, const float *sum, uint32_t min_count,
+                               float pho_abs_thresh, float *depth_avg, uint8_t *final_mask, void *temp, size_t temp_bytes, int64_t *total, void *stream);
+
+/* Rule 5: points (N,3); colors (N,3) gathered from rgb (V,3,H,W) and normals (N,3) from normal (V,3,H,W) (NULL: none, else the map must be given);
+ * index (N) int64, the flat (view H + row) W + column of each point (NULL: not wanted).  N <= V H W is the total read back; nothing at or beyond row
+ * N is written.  No atomics: two runs give identical bytes. */
+ENVGS_API int envgs_fuse_emit(int32_t V, int32_t H, int32_t W, const float *depth_avg, const uint8_t *final_mask, const void *temp, size_t temp_bytes,
+                              const float *view_maps, const float *rgb, const float *normal, uint32_t N, float *points, float *colors, float *normals,
+                              int64_t *index, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
