@@ -24,7 +24,7 @@
 
 namespace envgs {
 
-constexpr uint8_t CLS_CLONE = 1, CLS_SPLIT = 2, CLS_PRUNE_1 = 4, CLS_PRUNE_S = 8;
+constexpr uint8_t CLS_CLONE = ENVGS_GROW_CLS_CLONE, CLS_SPLIT = ENVGS_GROW_CLS_SPLIT, CLS_PRUNE_1 = ENVGS_GROW_CLS_PRUNE_1, CLS_PRUNE_S = ENVGS_GROW_CLS_PRUNE_S;
 
 // ---- per-step statistics ----------------------------------------------------------------------------------------------------------------
 template <int COLS>

@@ -70,6 +70,17 @@ ENVGS_API int envgs_densify_stats(int64_t P, int32_t cols, const float *grad, co
 #define ENVGS_PLAN_MIN_GRADIENT 2u
 #define ENVGS_PLAN_SPLIT_SCREEN 4u
 
+/* the bits of a surfel's byte in `cls`.  With avg(x) = x / denom in fp32, NaN -> 0:
+ *   high = avg(ga) >= grad_threshold;  small = max(scal) <= size_limit;
+ *   CLONE = small && high;  SPLIT = high && (!small || (SPLIT_SCREEN given && mr > split_screen_threshold));
+ *   PRUNE_1 = (MIN_OPACITY given && opac < min_opacity) || (MIN_GRADIENT given && avg(ga) <= min_gradient && denom != 0): the surfel as it is;
+ *   PRUNE_S = the same with avg(fl(ga * r)): its split children.  Only the one of the two that SPLIT selects is acted on.
+ * The flag arrays: A = !SPLIT && !PRUNE_1;  B = CLONE && A;  D = SPLIT && !PRUNE_S;  E = CLONE && D;  S1 = SPLIT;  S2 = CLONE && SPLIT. */
+#define ENVGS_GROW_CLS_CLONE 1u
+#define ENVGS_GROW_CLS_SPLIT 2u
+#define ENVGS_GROW_CLS_PRUNE_1 4u
+#define ENVGS_GROW_CLS_PRUNE_S 8u
+
 /* the words of `counters` (device; the host reads them back once) */
 #define ENVGS_GROW_N_A 0                      /* originals kept as they are */
 #define ENVGS_GROW_N_B 1                      /* clone children kept */

@@ -46,27 +46,36 @@ def _golden(name):
     return sc, args
 
 
-def _build(before, cfg, device_schedule, seed=1234, dev="cuda:0"):
-    params = {k: torch.nn.Parameter(before["params"][k].to(dev).clone()) for k in NAMES}
-    opt = torch.optim.Adam([{"params": [params[k]], "lr": 1e-3, "name": PREFIX + k} for k in NAMES], lr=0.0, eps=1e-15)
-    for k in NAMES:
-        opt.state[params[k]] = {"step": torch.tensor(2.0), "exp_avg": before["m"][k].to(dev).clone(), "exp_avg_sq": before["v"][k].to(dev).clone()}
+def _build(before, cfg, device_schedule, seed=1234, dev="cuda:0", names=NAMES, optimizer="state", row_ops=None):
+    """optimizer: "state" (Adam with both moments on every parameter), "empty" (Adam that has not stepped yet: no state) or None (no optimizer)."""
+    params = {k: torch.nn.Parameter(before["params"][k].to(dev).clone()) for k in names}
+    opt = None
+    if optimizer is not None:
+        opt = torch.optim.Adam([{"params": [params[k]], "lr": 1e-3, "name": PREFIX + k} for k in names], lr=0.0, eps=1e-15)
+    if optimizer == "state":
+        for k in names:
+            opt.state[params[k]] = {"step": torch.tensor(2.0), "exp_avg": before["m"][k].to(dev).clone(), "exp_avg_sq": before["v"][k].to(dev).clone()}
     gen = torch.Generator(device=dev).manual_seed(seed)
     s = densify.SurfelSet(params, opt, PREFIX, spatial_scale=cfg.get("spatial_scale", 1.0), max_gs=cfg.get("max_gs"), max_gs_threshold=cfg.get("max_gs_threshold", 1.0),
-                          row_ops=None, generator=gen, device_schedule=device_schedule)
+                          row_ops=row_ops, generator=gen, device_schedule=device_schedule)
     for k in s.STATS:
         s.stats[k] = before["stats"][k].to(dev).clone()
     return s, opt
 
 
-def _state(s, opt):
-    out = {"params": {k: s.p[k].detach().clone() for k in NAMES}, "m": {}, "v": {}, "stats": {k: v.clone() for k, v in s.stats.items()}}
+def _state(s, opt, names=NAMES, optimizer="state"):
+    out = {"params": {k: s.p[k].detach().clone() for k in names}, "m": {}, "v": {}, "stats": {k: v.clone() for k, v in s.stats.items()}}
+    assert tuple(s.p) == tuple(names)
+    if optimizer is None:
+        assert opt is None and s.optimizer is None
+        return out
     for g in opt.param_groups:
         k = g["name"][len(PREFIX):]
         assert g["params"][0] is s.p[k]                                    # the optimizer trains the surfel set's current parameters
-        st = opt.state[g["params"][0]]
-        out["m"][k], out["v"][k] = st["exp_avg"], st["exp_avg_sq"]
-    assert len(opt.state) == len(NAMES)                                    # no stale entries of replaced parameters
+        if optimizer == "state":
+            st = opt.state[g["params"][0]]
+            out["m"][k], out["v"][k] = st["exp_avg"], st["exp_avg_sq"]
+    assert len(opt.state) == (len(names) if optimizer == "state" else 0)   # no stale entries of replaced parameters; an empty state stays empty
     return out
 
 
@@ -170,7 +179,9 @@ def test_statistics_launch_has_no_host_sync():
 
 
 # ---- grow and prune ----------------------------------------------------------------------------------------------------------------------
-def _check_grow(before, cfg, a, synthetic=False, N=2, ratio=0.8, seed=77):
+def _check_grow(before, cfg, a, synthetic=False, N=2, ratio=0.8, seed=77, names=NAMES, optimizer="state", device_set=None, gen_state=None):
+    """device_set: a (SurfelSet, optimizer) in device mode that holds `before` already, e.g. the result of an earlier pass; gen_state: the state
+    of its generator, which the staged twin and the float64 children then start from instead of `seed`."""
     dev = "cuda:0"
     c = _classes(before, cfg, a, dev, N, ratio)
     clone, split, pr_1, pr_s = c["clone"], c["split"], c["pr_1"], c["pr_s"]
@@ -178,33 +189,39 @@ def _check_grow(before, cfg, a, synthetic=False, N=2, ratio=0.8, seed=77):
         assert int((clone & split).sum()) > 0
         for seg in (~split & pr_1, clone & ~split & pr_1, split & pr_s, clone & split & pr_s):
             assert int(seg.sum()) > 0
-    dv, do = _build(before, cfg, True, seed)
-    sg, so = _build(before, cfg, False, seed)
+    dv, do = device_set if device_set is not None else _build(before, cfg, True, seed, names=names, optimizer=optimizer)
+    sg, so = _build(before, cfg, False, seed, names=names, optimizer=optimizer)
+    if gen_state is not None:
+        sg.generator.set_state(gen_state.clone())
     dv.grow_and_prune(a["min_opacity"], a["min_gradient"], a["grad_threshold"], a["size_threshold"], a["split_screen_threshold"], N, ratio)
     _staged_three(sg, a, N)
     assert dv.log == sg.log
-    D, S = _state(dv, do), _state(sg, so)
+    D, S = _state(dv, do, names, optimizer), _state(sg, so, names, optimizer)
     nA, nB = int((~split & ~pr_1).sum()), int((clone & ~split & ~pr_1).sum())
     keepD, keepE = split & ~pr_s, clone & split & ~pr_s
     nD, nE, nS = int(keepD.sum()), int(keepE.sum()), int(split.sum()) + int((clone & split).sum())
     total = nA + nB + N * (nD + nE)
     assert dict(dv.log) == {"clone": int(clone.sum()), "split": nS, "prune_occ_grad": clone.shape[0] + int(clone.sum()) + (N - 1) * nS - total}
-    for k in NAMES:
+    for k in names:
         assert D["params"][k].shape == S["params"][k].shape and D["params"][k].shape[0] == total, k
-        assert torch.equal(D["m"][k], S["m"][k]) and torch.equal(D["v"][k], S["v"][k]), k
+        if D["m"]:
+            assert torch.equal(D["m"][k], S["m"][k]) and torch.equal(D["v"][k], S["v"][k]), k
         if k in ("_xyz", "_scaling"):
             assert torch.equal(D["params"][k][:nA + nB], S["params"][k][:nA + nB]), k
         else:
             assert torch.equal(D["params"][k], S["params"][k]), k
     for k in dv.STATS:
         assert D["stats"][k].shape == S["stats"][k].shape and torch.equal(D["stats"][k], S["stats"][k]), k
-    if nS == 0:
+    if nS == 0 or nD + nE == 0:                                            # no split, or no child of one survives: no child to evaluate
         return dv, sg
     # the children, from the same fp32 inputs and the same samples in float64
     sel = torch.cat((torch.nonzero(split)[:, 0], torch.nonzero(clone & split)[:, 0]))            # S, in the staged order
     kept = torch.cat((keepD[split], keepE[clone & split]))
     stds = torch.cat((c["scal"][sel], torch.zeros(nS, 1, device=dev)), dim=-1).repeat(N, 1)
-    samples = torch.normal(torch.zeros_like(stds), stds, generator=torch.Generator(device=dev).manual_seed(seed))
+    gen = torch.Generator(device=dev).manual_seed(seed)
+    if gen_state is not None:
+        gen.set_state(gen_state.clone())
+    samples = torch.normal(torch.zeros_like(stds), stds, generator=gen)
     par = sel.repeat(N)[kept.repeat(N)]
     smp = samples[kept.repeat(N)].double()
     q = before["params"]["_rotation"].to(dev)[par].double()
