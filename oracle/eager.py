@@ -88,8 +88,11 @@ def project(means3D, scales, rotations, opacities, viewmatrix, projmatrix, W, H,
 
 def rasterize(means3D, opacities, viewmatrix, projmatrix, campos, W, H, *, scales=None, rotations=None,
               transmat_precomp=None, shs=None, colors_precomp=None, sh_degree=0, bg=None, scale_modifier=1.0,
-              pix_chunk=4096):
-    """Returns (out_color (C,H,W), radii (P), allmap (7,H,W), weight (P)).  Differentiable."""
+              pix_chunk=4096, stats=None):
+    """Returns (out_color (C,H,W), radii (P), allmap (7,H,W), weight (P)).  Differentiable.
+    stats: an optional dict that is filled with per-pixel (H*W,) counts of what the compositing did -- `blends` (composited hits), `capped` (blends with
+    opacity * G > 0.99: the alpha cap was taken), `lowpass` (blends on the low-pass branch rho2d < rho3d), `accepted` (hits passing every test, termination
+    ignored) and `stopped` (bool: the pixel ended on T (1 - alpha) < 1e-4).  The results do not depend on it."""
     dt = means3D.dtype
     pr = project(means3D, scales, rotations, opacities, viewmatrix, projmatrix, W, H, scale_modifier, transmat_precomp)
     if shs is not None:
@@ -113,6 +116,8 @@ def rasterize(means3D, opacities, viewmatrix, projmatrix, campos, W, H, *, scale
     out_color = torch.zeros(C, HW, dtype=dt); allmap = torch.zeros(7, HW, dtype=dt)
     weight = torch.zeros(means3D.shape[0], dtype=dt)
     pix_all = torch.arange(HW)
+    if stats is not None:
+        stats.update({k: torch.zeros(HW, dtype=torch.int64) for k in ("blends", "capped", "lowpass", "accepted")}, stopped=torch.zeros(HW, dtype=torch.bool))
     for s in range(0, HW, pix_chunk):
         pid = pix_all[s:s + pix_chunk]
         px = (pid % W).to(dt)[None]; py = (pid // W).to(dt)[None]
@@ -152,6 +157,12 @@ def rasterize(means3D, opacities, viewmatrix, projmatrix, campos, W, H, *, scale
         M2 = torch.cumsum(m * m * w, 0) - m * m * w
         dist = ((m * m * A + M2 - 2 * m * M1) * w).sum(0)
         contrib = (alpha.detach() > 0)
+        if stats is not None:
+            stats["blends"][pid] = contrib.sum(0)
+            stats["capped"][pid] = (contrib & (a_raw.detach() > 0.99)).sum(0)
+            stats["lowpass"][pid] = (contrib & ~use3d).sum(0)
+            stats["accepted"][pid] = ok.sum(0)
+            stats["stopped"][pid] = stop.any(0)
         medsel = contrib & (Texcl.detach() > 0.5)
         ar = torch.arange(G)[:, None].expand_as(medsel)
         medidx = torch.where(medsel, ar, torch.full_like(ar, -1)).max(0).values

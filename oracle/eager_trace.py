@@ -23,9 +23,11 @@ def _sh_basis(deg, d):
 
 
 def trace(ray_o, ray_d, means3D, scales, rotations, opacities, *, shs=None, colors_precomp=None, others=None, sh_degree=0,
-          bg=None, start_from_first=True, scale_modifier=1.0, tmin=None):
+          bg=None, start_from_first=True, scale_modifier=1.0, tmin=None, stats=None):
     """One stage of tracing.  Returns rgb (R,3), dpt (R), acc (R), norm (R,3), aux (R,2), wet (P).  tmin overrides the start_from_first rule
-    (bounce stages start at 1e-3)."""
+    (bounce stages start at 1e-3).  stats: an optional dict that is filled with per-ray (R,) counts -- `blends` (composited hits), `capped` (blends with
+    opacity * G > 0.99: the alpha cap was taken), `accepted` (hits passing every test, termination ignored) and `stopped` (bool: the ray ended on
+    T (1 - alpha) < 1e-4).  The results do not depend on it."""
     dt = means3D.dtype
     R_, P = ray_o.shape[0], means3D.shape[0]
     Rm = _rotmat(rotations)
@@ -53,6 +55,9 @@ def trace(ray_o, ray_d, means3D, scales, rotations, opacities, *, shs=None, colo
     stop = ok_s & (Tin.detach() < 1e-4)
     alive = torch.cumsum(stop.to(torch.int32), dim=1) == 0
     al_s = al_s * alive.to(dt)
+    if stats is not None:
+        blended = al_s.detach() > 0
+        stats.update(blends=blended.sum(1), capped=(blended & (gat(araw).detach() > 0.99)).sum(1), accepted=ok_s.sum(1), stopped=stop.any(1))
     Tin = torch.cumprod(1 - al_s, dim=1)
     Tex = torch.cat([torch.ones_like(Tin[:, :1]), Tin[:, :-1]], dim=1)
     w = al_s * Tex                                                      # (R,P) in sorted order

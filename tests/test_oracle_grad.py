@@ -9,10 +9,14 @@ from oracle import eager, raster as orc
 from tests.util import scene_for, cam_args, rel_err, record, record_fragile, small_fx, SMALL_IMAGES, FRAGILE_PX_MAX
 
 
-def _run(sh, C, precomp_T, seed, camera="orbit", scale_modifier=1.0, HW=(48, 64), P=300, fx=None, mask_fragile=False):
-    """mask_fragile: zero the upstream gradient at the pixels the oracle's audit marks (a threshold inside fp32 noise flips a contributor between the
+def _run(sh, C, precomp_T, seed, camera="orbit", scale_modifier=1.0, HW=(48, 64), P=300, fx=None, mask_fragile=False, saturated=False):
+    """saturated: tests/saturated_scenes.py:surface_object instead of the random cloud (surfels on a sphere, 40 % of them at opacity 1.0f).  mask_fragile: zero the upstream gradient at the pixels the oracle's audit marks (a threshold inside fp32 noise flips a contributor between the
     fp32 oracle and float64), as the GPU parity tests do; the mask is returned so that the values are compared on the other pixels."""
-    g, cam = scene_for(camera, P=P, H=HW[0], W=HW[1], seed=seed, C=C, sh=sh, fx=fx)
+    if saturated:
+        from tests.saturated_scenes import raster_case
+        g, cam = raster_case(P, HW[0], HW[1], seed, C=C, fx=fx)
+    else:
+        g, cam = scene_for(camera, P=P, H=HW[0], W=HW[1], seed=seed, C=C, sh=sh, fx=fx)
     ca = cam_args(cam)
     W, H = ca["W"], ca["H"]
     bg = torch.tensor([0.3, 0.6, 0.1])
@@ -125,6 +129,25 @@ def test_oracle_vs_autograd_on_other_cameras_modifiers_and_small_images(kw, min_
     ev, eg = _compare(g, fwd, bwd, outs, leaves, kw["sh"], kw["precomp_T"], ok=~frag, clean=~tainted)
     test = "oracle_cpu.raster." + request.node.callspec.id
     record_fragile(test, "fragile_px", frag, FRAGILE_PX_MAX)
+    record(test, "values", ev, "(C oracle against float64 eager, max over the outputs)")
+    record(test, "gradients", eg, "(C oracle against float64 autograd, max over the leaves)")
+
+
+@pytest.mark.parametrize("kw", [pytest.param(dict(sh=True, C=3, precomp_T=False, P=300, seed=3), id="sphere300"),
+                                pytest.param(dict(sh=False, C=5, precomp_T=False, P=600, seed=2), id="sphere600")])
+def test_oracle_vs_autograd_on_a_saturated_surface(kw, request):
+    """tests/saturated_scenes.py:surface_object (surfels on a sphere, 40 % at opacity 1.0f): blends that take the alpha cap, whose backward is the straight-through
+    one, and pixels that end after two or three hits -- the random clouds above reach neither.  Measured: values <= 1.3e-5, gradients <= 8.4e-5 (asserted at the
+    file's 2e-4 / 2e-3); no audited pixel at these seeds."""
+    from tests.saturated_scenes import census_raster, raster_case
+    g, fwd, bwd, outs, leaves, (frag, tainted) = _run(mask_fragile=True, saturated=True, **kw)
+    c = census_raster(*raster_case(kw["P"], 48, 64, kw["seed"], C=kw["C"]), sh=kw["sh"], exclude=frag)
+    assert c["capped"] >= 20 and c["stopped_px"] >= 20, c
+    assert frag.mean() <= FRAGILE_PX_MAX
+    ev, eg = _compare(g, fwd, bwd, outs, leaves, kw["sh"], kw["precomp_T"], ok=~frag, clean=~tainted)
+    test = "oracle_cpu.raster.saturated_" + request.node.callspec.id
+    record_fragile(test, "fragile_px", frag, FRAGILE_PX_MAX)
+    record(test, "capped_blends", c["capped"], "(float64 twin; %d of %d pixels end early)" % (c["stopped_px"], c["pixels"]))
     record(test, "values", ev, "(C oracle against float64 eager, max over the outputs)")
     record(test, "gradients", eg, "(C oracle against float64 autograd, max over the leaves)")
 

@@ -9,7 +9,8 @@ from envgs_amd import synth
 
 
 def small_scene(P=400, H=64, W=80, seed=0, view=1, C=3, sh=True, spread=1.0, scale_mul=4.0):
-    """A small scene whose surfels are big enough on a tiny image to overlap heavily."""
+    """A small scene whose surfels are big enough on a tiny image to overlap heavily.
+    (A random cloud: no blend reaches the alpha cap.  Opaque, surface-aligned scenes are in tests/saturated_scenes.py.)"""
     g = synth.base_gaussians(P, seed=seed)
     g["means3D"] = g["means3D"] * spread
     g["scales"] = g["scales"] * scale_mul
