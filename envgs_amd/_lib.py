@@ -252,6 +252,8 @@ SYMBOLS = {
     "envgs_l1_ssim_partial_count": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "envgs_l1_ssim_forward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P]),
     "envgs_l1_ssim_backward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, ctypes.c_float, ctypes.c_float, _P, _P]),
+    "envgs_image_metrics_partial_count": (ctypes.c_int64, [ctypes.c_int32] * 4),
+    "envgs_image_metrics": (c_int, [ctypes.c_int32] * 4 + [_P, ctypes.POINTER(ctypes.c_int64), _P, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32, _P, _P, _P]),
     "envgs_depth_percentiles_temp_bytes": (c_size_t, []),
     "envgs_depth_percentiles": (c_int, [ctypes.c_int64, _P, ctypes.c_int64, _P, _P, c_size_t, _P]),
     "envgs_supervisor_partial_count": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64]),
