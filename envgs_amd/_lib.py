@@ -152,6 +152,19 @@ class FuseSources(ctypes.Structure):
     _fields_ = [("count", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("v", FuseSource * 8)]
 
 
+class VisMap(ctypes.Structure):
+    """struct envgs_vis_map (include/envgs_visualize.h)."""
+    _fields_ = [("ptr", ctypes.c_void_p), ("stride", ctypes.c_int64 * 4)]
+
+
+class VisPlane(ctypes.Structure):
+    """struct envgs_vis_plane (include/envgs_visualize.h)."""
+    _fields_ = ([(n, ctypes.c_int32) for n in ("kind", "weight_mode", "curve", "gt_dtype")]
+                + [("flags", ctypes.c_uint32), ("table_k", ctypes.c_int32), ("dpt_mult", ctypes.c_float), ("bg", ctypes.c_float * 3)]
+                + [(n, VisMap) for n in ("img", "weight", "acc", "gt", "msk")]
+                + [(n, ctypes.c_void_p) for n in ("M", "near_far", "table")])
+
+
 # every symbol include/*.h declares: name -> (restype, argtypes)
 _P = c_void_p
 SYMBOLS = {
@@ -254,6 +267,9 @@ SYMBOLS = {
     "envgs_l1_ssim_backward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, ctypes.c_float, ctypes.c_float, _P, _P]),
     "envgs_image_metrics_partial_count": (ctypes.c_int64, [ctypes.c_int32] * 4),
     "envgs_image_metrics": (c_int, [ctypes.c_int32] * 4 + [_P, ctypes.POINTER(ctypes.c_int64), _P, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32, _P, _P, _P]),
+    "envgs_visualize_depth_range_temp_bytes": (c_size_t, []),
+    "envgs_visualize_depth_range": (c_int, [ctypes.c_int32] * 3 + [_P, ctypes.POINTER(ctypes.c_int64), ctypes.c_int64, ctypes.c_int64, _P, _P, c_size_t, _P]),
+    "envgs_visualize_planes": (c_int, [ctypes.c_int32, ctypes.POINTER(VisPlane)] + [ctypes.c_int32] * 7 + [_P, _P]),
     "envgs_depth_percentiles_temp_bytes": (c_size_t, []),
     "envgs_depth_percentiles": (c_int, [ctypes.c_int64, _P, ctypes.c_int64, _P, _P, c_size_t, _P]),
     "envgs_supervisor_partial_count": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64]),
