@@ -142,6 +142,17 @@ class CullViews(ctypes.Structure):
     _fields_ = [("count", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("v", CullView * 8)]
 
 
+class MeshRasterView(ctypes.Structure):
+    """struct envgs_mesh_raster_view (include/envgs_mesh.h)."""
+    _fields_ = [("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("R", ctypes.c_float * 9), ("T", ctypes.c_float * 3)]
+
+
+class MeshRasterViews(ctypes.Structure):
+    """struct envgs_mesh_raster_views (include/envgs_mesh.h)."""
+    _fields_ = [("count", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("v", MeshRasterView * 8)]
+
+
 class FuseSource(ctypes.Structure):
     """struct envgs_fuse_source (include/envgs_mesh.h)."""
     _fields_ = [("depth", ctypes.c_void_p), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("fwd", ctypes.c_float * 12), ("back", ctypes.c_float * 12)]
@@ -262,6 +273,10 @@ SYMBOLS = {
     "envgs_fuse_temp_bytes": (c_size_t, [ctypes.c_int32] * 3),
     "envgs_fuse_count": (c_int, [ctypes.c_int32] * 3 + [_P, _P, _P, c_uint32, ctypes.c_float, _P, _P, _P, c_size_t, _P, _P]),
     "envgs_fuse_emit": (c_int, [ctypes.c_int32] * 3 + [_P, _P, _P, c_size_t, _P, _P, _P, c_uint32] + [_P] * 4 + [_P]),
+    "envgs_mesh_raster_small_max": (ctypes.c_int32, []),
+    "envgs_mesh_raster_temp_bytes": (c_size_t, [ctypes.c_int32] * 3),
+    "envgs_mesh_raster": (c_int, [c_uint32, c_uint32, _P, _P, _P, ctypes.POINTER(MeshRasterViews), ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
+                                  ctypes.c_int32, _P, c_size_t] + [_P] * 7 + [_P]),
     "envgs_l1_ssim_partial_count": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "envgs_l1_ssim_forward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P]),
     "envgs_l1_ssim_backward": (c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, ctypes.c_float, ctypes.c_float, _P, _P]),

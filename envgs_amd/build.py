@@ -36,10 +36,12 @@ COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++20", "-fPIC", "-munsafe-fp-a
 # metrics.hip: its fused multiply-adds are written out; left to the compiler, the five filter sums of SSIM are fused unevenly and identical images
 # no longer score exactly 1
 # visualize.hip: an 8-bit image is a rounding decision per byte; one text gives one fp32 sequence, which the NumPy oracle repeats operation by operation
+# mesh_raster.hip: a z-buffer is decided by comparisons; csrc/mesh_raster.h is one text for the kernels and for a host program, and both must
+# round the projection (multiply, add, IEEE divide, rint) and the double-precision depth as the NumPy oracle does
 _NO_SLP = ["-fno-slp-vectorize"]
 EXTRA = {"raster_project.hip": ["-ffp-contract=off"], "raster_project_bwd.hip": ["-ffp-contract=off"], "densify_device.hip": ["-ffp-contract=off"],
          "mesh.hip": ["-ffp-contract=off"], "mesh_simplify.hip": ["-ffp-contract=off"], "mesh_eval.hip": ["-ffp-contract=off"],
-         "mesh_register.hip": ["-ffp-contract=off"], "metrics.hip": ["-ffp-contract=off"], "visualize.hip": ["-ffp-contract=off"],
+         "mesh_register.hip": ["-ffp-contract=off"], "mesh_raster.hip": ["-ffp-contract=off"], "metrics.hip": ["-ffp-contract=off"], "visualize.hip": ["-ffp-contract=off"],
          "trace_kbuffer.hip": _NO_SLP, "trace_collect.hip": _NO_SLP, "trace_lists.hip": _NO_SLP,
          "trace_surfel_bwd.hip": _NO_SLP, "trace_api.hip": _NO_SLP}
 

@@ -17,6 +17,8 @@ tests/mesh_oracle.py restates them independently.  There is no CPU path: CPU ten
                        observed=(obs_mask, origin, voxel), box=(lo, hi), plane=plane)       # the DTU protocol: thin_points() and the filters
     tnt = evaluate_tnt(mesh, scan_points, tau=0.003, init=T_colmap_to_scan, crop=load_crop_volume("Barn.json"), density=4e5)
                                                                                             # Tanks and Temples: register(), voxel_downsample(), the crop
+    maps = render_mesh(mesh, cameras)                               # csrc/mesh_raster.hip: exact depth, face, normal and colour maps of the mesh through
+    mesh = cull_unseen(mesh, cameras)                               # cameras (a triangle z-buffer, no clipping), and the cull of what no camera sees
     cloud, maps = fuse_surfel_points(cameras, base, sh_degree=3)     # csrc/mesh_fuse.hip: depth-map fusion, the route without a volume -- PARITY
                                                                      # PINNED by tests/golden/fuse_golden.npz (the section "depth fusion" below)
 """
@@ -674,6 +676,98 @@ def cull_to_masks(mesh, cameras, masks, return_index=False):
         _lib.check(lib.envgs_mesh_cull_vertices(V, p(v), views, int(b0 > 0), p(vertex_keep), _stream(dev)), "envgs_mesh_cull_vertices")
     _lib.check(lib.envgs_mesh_cull_faces(V, F, p(f), p(vertex_keep), p(face_keep), _stream(dev)), "envgs_mesh_cull_faces")
     return select_faces(mesh, face_keep, return_index=return_index)
+
+
+# ---- rasterisation (csrc/mesh_raster.hip, csrc/mesh_raster.h) -----------------------------------------------------------------------------------------
+RASTER_OUTPUTS = ("depth", "face", "bary", "normal", "color", "seen")
+_RASTER_MAPS = {"depth": ((), torch.float32), "face": ((), torch.int32), "bary": ((3,), torch.float32), "normal": ((3,), torch.float32),
+                "color": ((3,), torch.float32)}
+
+
+def _raster_size(cameras, size, what):
+    if size is not None:
+        H, W = (int(s) for s in size)
+    else:
+        sizes = {(int(getattr(c, "image_height", getattr(c, "H", -1))), int(getattr(c, "image_width", getattr(c, "W", -1)))) for c in cameras}
+        if len(sizes) != 1:
+            raise ValueError("%s: the cameras must share one size (got %s); pass size=(H, W)" % (what, sorted(sizes) if sizes else "no cameras"))
+        H, W = sizes.pop()
+    if H < 1 or W < 1 or H * W >= 2 ** 28:
+        raise ValueError("%s: the image size %d x %d is outside 1 .. 2^28 pixels" % (what, H, W))
+    return H, W
+
+
+def _raster(mesh, cameras, size, near, outputs, what, stats=None):
+    cameras = list(cameras)
+    outputs = tuple(outputs)
+    for o in outputs:
+        if o not in RASTER_OUTPUTS:
+            raise ValueError("%s: unknown output %r: one of %s" % (what, o, ", ".join(RASTER_OUTPUTS)))
+    H, W = _raster_size(cameras, size, what)
+    near = float(near)
+    if math.isnan(near):
+        raise ValueError("%s: near must not be NaN" % what)
+    for t, dtype, name in ((mesh.vertices, torch.float32, "vertices"), (mesh.faces, torch.int32, "faces")):
+        if not torch.is_tensor(t) or t.dtype != dtype or t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError("%s: %s must be a (N,3) %s tensor" % (what, name, dtype))
+    v, f, c = _mesh_tensors(mesh, what)
+    lib = _lib.load()
+    dev, V, F, n = v.device, v.shape[0], f.shape[0], len(cameras)
+    maps = {o: torch.empty((n, H, W) + _RASTER_MAPS[o][0], dtype=_RASTER_MAPS[o][1], device=dev) for o in outputs
+            if o in _RASTER_MAPS and (o != "color" or c is not None)}
+    seen = torch.empty(F, dtype=torch.uint8, device=dev) if "seen" in outputs else None
+    if seen is not None and n == 0:
+        seen.zero_()
+    tb = lib.envgs_mesh_raster_temp_bytes(H, W, min(n, MAX_VIEWS))
+    temp = torch.empty(tb, dtype=torch.uint8, device=dev)
+    p = _lib.ptr
+    row = lambda name, b0: _lib.c_void_p(maps[name][b0].data_ptr()) if name in maps else None
+    for b0 in range(0, n, MAX_VIEWS):
+        views = _lib.MeshRasterViews()
+        views.count = min(MAX_VIEWS, n - b0)
+        for q in range(views.count):
+            cam, cv = cameras[b0 + q], views.v[q]
+            k, r, t = _host(cam.K, (3, 3)), _host(cam.R, (3, 3)), _host(cam.T, (3,))
+            cv.fx, cv.fy, cv.cx, cv.cy = float(k[0, 0]), float(k[1, 1]), float(k[0, 2]), float(k[1, 2])
+            cv.R = (_lib.ctypes.c_float * 9)(*[float(x) for x in r.reshape(-1)])
+            cv.T = (_lib.ctypes.c_float * 3)(*[float(x) for x in t])
+        _lib.check(lib.envgs_mesh_raster(V, F, p(v), p(c) if "color" in maps else None, p(f), views, H, W, near, int(b0 == 0), p(temp), tb,
+                                         row("depth", b0), row("face", b0), row("bary", b0), row("normal", b0), row("color", b0), p(seen), p(stats),
+                                         _stream(dev)), "envgs_mesh_raster")
+    if seen is not None:
+        maps["seen"] = seen
+    return SimpleNamespace(**maps)
+
+
+def render_mesh(mesh, cameras, size=None, near=0.0, outputs=("depth", "face", "normal", "color")):
+    """The mesh through cameras: a triangle z-buffer, exact to the bit (include/envgs_mesh.h, "rasterisation"; tests/mesh_raster_oracle.py restates
+    the rule).  cameras: namespaces with K (3,3), R (3,3) world -> camera and T (3,), as cull_to_masks() takes them; size: (H, W), default the
+    cameras' image_height / image_width, which must agree; near: a corner is usable only with zc > near.  outputs, any of:
+        depth  (n,H,W) f32    the z of the nearest face under the pixel's centre, 0 where none
+        face   (n,H,W) i32    its index (of equal depths the lowest), -1 where none
+        bary   (n,H,W,3) f32  perspective-correct barycentric coordinates, in the order of the face's corners
+        normal (n,H,W,3) f32  the face's unit normal in WORLD space, oriented towards the camera whatever the winding
+        color  (n,H,W,3) f32  the vertex colours interpolated with bary; ignored for a mesh without colours
+        seen   (F,) u8        1 iff the face wins a pixel of some view
+    What is not asked for is neither computed nor written.  Both windings are drawn; a face with an index outside [0, V), a corner that is not
+    finite or not beyond `near`, or zero area on the screen is dropped whole.  DEVIATION from a graphics pipeline: there is NO CLIPPING -- a face
+    that crosses the camera plane is not drawn at all (its visible part is missing), so keep `near` small and the mesh in front of the cameras.
+    PARITY UNPINNED: the reference renders meshes only through its OpenGL viewer.
+    -> namespace of device tensors.  Views go to the device 8 per launch; no host sync; two calls give identical bytes."""
+    return _raster(mesh, cameras, size, near, outputs, "render_mesh")
+
+
+def visible_faces(mesh, cameras, size=None, near=0.0):
+    """(F,) bool device tensor: the faces that win at least one pixel of at least one camera under render_mesh()'s rule.  No maps are written; no
+    host sync."""
+    return _raster(mesh, cameras, size, near, ("seen",), "visible_faces").seen.view(torch.bool)
+
+
+def cull_unseen(mesh, cameras, size=None, near=0.0, return_index=False):
+    """Drops the faces no camera sees -- inner shells, back sides that were never observed -- and the vertices only they name:
+    select_faces(mesh, visible_faces(...)), so the order is preserved and the vertices are compacted as clean() does.
+    -> Mesh, or (Mesh, vertex_index) with return_index.  One host sync: that of select_faces()."""
+    return select_faces(mesh, visible_faces(mesh, cameras, size, near), return_index=return_index)
 
 
 def _triple(x, what):

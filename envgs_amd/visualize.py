@@ -1,5 +1,6 @@
 """Image output on the device: the visualizer's maps as finished 8-bit RGBA (include/envgs_visualize.h, csrc/visualize.hip), an asynchronous
-writer of PNG / PPM files, and a driver that renders cameras through the EnvGS forward and writes the eight pictures of configs/models/envgs.yaml.
+writer of PNG / PPM files, a driver that renders cameras through the EnvGS forward and writes the eight pictures of configs/models/envgs.yaml, and
+mesh_views(), which writes the shaded-normal, depth and colour pictures of a mesh from mesh.render_mesh()'s maps through the same planes.
 
 Semantics: the reference's VolumetricVideoVisualizer (runners/visualizers/volumetric_video_visualizer.py, generate_type :84-268) and the byte rule
 of data_utils.save_image (:1230), in float32, operation by operation; tests/visualize_oracle.py states them in NumPy and
@@ -469,6 +470,51 @@ def view_planes(out, cam, types=TYPES, image=None, mask=None, gt_bg=None, store_
         else:
             raise ValueError("unknown visualization type %r: one of %s" % (t, ", ".join(TYPES)))
     return planes, names
+
+
+MESH_TYPES = ("MESH_NORMAL", "MESH_DEPTH", "MESH_RENDER")
+MESH_GROUP = 8                                                       # cameras per render_mesh / image_planes call: one launch group of the rasteriser
+
+
+def mesh_views(mesh, cameras, writer, types=MESH_TYPES, size=None, near=0.0, labels=None, dpt_curve="normalize", dpt_mult=1.0, dpt_table=None):
+    """Pictures of a mesh (mesh.Mesh: vertices, faces, colors) through cameras with K, R, T: mesh.render_mesh()'s maps fed to the planes above, no
+    kernel of its own.  types, out of MESH_TYPES:
+        MESH_NORMAL  the shaded-normal picture: normal() of the face normals (world space, towards the camera) with M = the camera's R
+        MESH_DEPTH   depth() of the z-buffer, background included at depth 0, as DEPTH treats the surfel depth
+        MESH_RENDER  color() of the interpolated vertex colours; a mesh without colours raises
+    The alpha map of every plane is face >= 0.  Per group of 8 cameras: ONE render_mesh, ONE image_planes and ONE writer.add call; files follow
+    the writer's pattern with camera, frame = (i, 0) or labels[i].  No host synchronisation beyond the writer's waits for its own copies.
+    -> the paths in the order they were enqueued; they exist after writer.flush() / close().  The rasteriser does not clip (mesh.render_mesh)."""
+    from . import mesh as mesh_ops
+    cameras = list(cameras)
+    types = list(types)
+    for t in types:
+        if t not in MESH_TYPES:
+            raise ValueError("unknown mesh visualization type %r: one of %s" % (t, ", ".join(MESH_TYPES)))
+    if labels is not None and len(labels) != len(cameras):
+        raise ValueError("%d cameras for %d labels" % (len(cameras), len(labels)))
+    if "MESH_RENDER" in types and getattr(mesh, "colors", None) is None:
+        raise ValueError("MESH_RENDER needs a mesh with colours")
+    wanted = ("face",) + tuple(o for o, t in (("normal", "MESH_NORMAL"), ("depth", "MESH_DEPTH"), ("color", "MESH_RENDER")) if t in types)
+    opaque = not writer.store_alpha_channel
+    paths = []
+    for b0 in range(0, len(cameras) if types else 0, MESH_GROUP):
+        group = cameras[b0:b0 + MESH_GROUP]
+        r = mesh_ops.render_mesh(mesh, group, size=size, near=near, outputs=wanted)
+        acc = (r.face >= 0).to(torch.float32).unsqueeze(-1)
+        planes = []
+        for t in types:
+            if t == "MESH_NORMAL":
+                M = torch.stack([torch.as_tensor(c.R, dtype=torch.float32).reshape(3, 3) for c in group]).to(r.face.device)
+                planes.append(normal(r.normal, acc=acc, M=M, opaque=opaque))
+            elif t == "MESH_DEPTH":
+                planes.append(depth(r.depth.unsqueeze(-1), acc=acc, curve=dpt_curve, table=dpt_table, dpt_mult=dpt_mult, opaque=opaque))
+            else:
+                planes.append(color(r.color, acc=acc, opaque=opaque))
+        idx = range(b0, b0 + len(group))
+        camera, frame = ([i for i in idx], [0] * len(group)) if labels is None else ([labels[i][0] for i in idx], [labels[i][1] for i in idx])
+        paths += writer.add(image_planes(planes, tuple(r.face.shape[1:])), types, camera, frame)
+    return paths
 
 
 def visualize_views(cameras, base, env, sh_degree, bg, env_bg, writer, types=TYPES, images=None, masks=None, labels=None, gt_bg=None, dpt_curve="normalize",

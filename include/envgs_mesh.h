@@ -471,6 +471,89 @@ ENVGS_API int envgs_fuse_emit(int32_t V, int32_t H, int32_t W, const float *dept
                               const float *view_maps, const float *rgb, const float *normal, uint32_t N, float *points, float *colors, float *normals,
                               int64_t *index, void *stream);
 
+/* ---- rasterisation: exact depth, face and normal maps of a mesh, and the faces some camera sees (csrc/mesh_raster.hip, csrc/mesh_raster.h) ---------
+ * PARITY UNPINNED: the reference renders meshes only through its OpenGL viewer, which is out of scope.  The rule is this
+ * project's; tests/mesh_raster_oracle.py restates it in NumPy and Python integers.  csrc/mesh_raster.h is one text for the kernels and for the host.
+ *
+ * All views of a call share one size H x W.  The camera is the one cull_to_masks() and TSDFVolume.integrate() use: K, R world -> camera, T.  The
+ * centre of pixel (px, py) is at (px + 0.5, py + 0.5).  Cameras travel by value, 8 views per launch (MAX_VIEWS).
+ *
+ * Vertex, per view.  float32, no contraction, the sequence of the culling rule:
+ *   - xc = R00 x + R01 y + R02 z + T0, and yc, zc likewise.
+ *   - u = fx (xc / zc) + cx,  v = fy (yc / zc) + cy.
+ *   - The vertex is USABLE iff u and v are finite, zc > near, |u| < 2^21 and |v| < 2^21.  near is a float32 argument with default 0.
+ *   - Its sub-pixel position is X = (int32) rint(u * 256), Y = (int32) rint(v * 256), with ties to even.
+ *
+ * Face.
+ *   - A face is dropped whole iff one of these holds: an index is outside [0, V); a corner is not usable;
+ *     A = (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0) is 0.  A is int64, as are all edge arithmetic below.
+ *   - There is NO CLIPPING: a face that crosses the camera plane is not drawn.  This is a stated deviation from what a graphics pipeline does.
+ *   - If A < 0, corners 1 and 2 are exchanged and A is negated.  Both windings are drawn; there is no back-face culling.
+ *
+ * Coverage.
+ *   - Let P = (256 px + 128, 256 py + 128).
+ *   - For k = 0, 1, 2 let i = (k + 1) mod 3 and j = (k + 2) mod 3, in the possibly exchanged order.
+ *   - Define dx = Xj - Xi, dy = Yj - Yi, and E_k = dx (P_y - Y_i) - dy (P_x - X_i).
+ *   - The pixel is covered iff, for every k, E_k > 0 or (E_k == 0 and (dy < 0 or (dy == 0 and dx > 0))).  This is the top-left rule.
+ *   - A pixel on an edge shared by two faces belongs to exactly one of them.
+ *   - Any conservative bounding box may limit the pixels visited.  The result is defined by the rule over all H x W pixels.
+ *
+ * Depth.  In double:  l_k = (double) E_k / (double) A;  iz_k = 1.0 / (double) zc_k;  s = (l_0 iz_0 + l_1 iz_1) + l_2 iz_2;  z = (float) (1.0 / s).
+ *
+ * Winner.  The smallest 64-bit key (bits(z) << 32) | face index wins the pixel.  Equal depths go to the lowest face index.  The result does not
+ * depend on the order in which faces arrive.
+ *
+ * Outputs per view.  Each is optional; what the caller does not request is not computed or written.
+ *   depth  (n,H,W) float32     the winner's z; 0 where no face covers the pixel
+ *   face   (n,H,W) int32       the winner's index; -1 where none
+ *   bary   (n,H,W,3) float32   b_k = (float) ((l_k iz_k) / s), reported in the order of the face's ORIGINAL corners; 0 where none
+ *   normal (n,H,W,3) float32   see below
+ *   color  (n,H,W,3) float32   only for a mesh with colours: (b_0 c_0 + b_1 c_1) + b_2 c_2 per channel in float32, original corner order; 0 where none
+ *   seen   (F) uint8           1 iff the face wins at least one pixel of at least one view; accumulated over the launches of a call
+ *
+ * The normal:
+ *   - Take the world-space cross product (v1 - v0) x (v2 - v0) of the original corners in float32.  Each component is a b - c d with the two
+ *     products rounded first.
+ *   - Divide by its length: float32 sum of squares added left to right, IEEE sqrt, IEEE divide.
+ *   - ORIENT IT TOWARDS THE CAMERA: negate it iff A > 0 before the exchange.  A cross product that points along +z of this y-down, z-forward camera
+ *     faces away from it.
+ *   - A length of 0 gives (0, 0, 0).
+ *   - Where no face covers the pixel the normal is 0.
+ *
+ * Byte model.  The only scratch is the key image, 8 B per pixel and view of a launch (at most 8 views): it does not grow with F.  The raster pass
+ * reads 12 B of indices and 36 B of corners per (face, view) and issues one 64-bit integer atomic-min per covered fragment that a plain load of
+ * the key does not already rule out (keys only decrease, so a stale value costs an unnecessary atomic, never a result).  The resolve pass reads
+ * 8 B per pixel and the winner's 48 B, and writes the requested maps. */
+typedef struct envgs_mesh_raster_view {
+    float fx, fy, cx, cy;
+    float R[9];                               /* world -> camera, row major */
+    float T[3];
+} envgs_mesh_raster_view;
+
+typedef struct envgs_mesh_raster_views {
+    int32_t count;                            /* 0 .. ENVGS_TSDF_MAX_VIEWS */
+    int32_t reserved0;
+    envgs_mesh_raster_view v[ENVGS_TSDF_MAX_VIEWS];
+} envgs_mesh_raster_views;
+
+/* A face whose clamped bounding box holds at most this many pixels is walked by the lane that set it up; a larger one is handed to its whole
+ * workgroup, which strides the box together in tiles of 8 x 8 pixels. */
+ENVGS_API int32_t envgs_mesh_raster_small_max(void);
+
+/* Scratch bytes of envgs_mesh_raster: the key image, 8 B per pixel and view (0 unless H, W >= 1, H W < 2^28 and 0 <= views <= 8). */
+ENVGS_API size_t envgs_mesh_raster_temp_bytes(int32_t H, int32_t W, int32_t views);
+
+/* One launch group: the key image is set to all-ones, the raster pass fills it, the resolve pass writes the maps of views->count views (row 0 of
+ * every map pointer is the first view of THIS launch) and stores 1 to seen[f] of every winner.  first != 0: seen is cleared before; 0: it
+ * accumulates.  NULL for an output that is not wanted (colors NULL: color must be NULL too).  stats: NULL, or 2 uint64 on the device that the
+ * raster pass ADDS to: [0] fragments covered, [1] atomics issued (a measuring aid; it costs an atomic add per wavefront).  No host sync.
+ * F = 0, V = 0 and count = 0 are valid: the maps of the views given are cleared.  V or F at or above 2^31, a size out of range, a count outside
+ * 0 .. 8, a near that is NaN, a NULL array of rows and a `temp` that is NULL or not 16-byte aligned return ENVGS_ERR_BAD_ARG before any GPU work,
+ * a short `temp` ENVGS_ERR_TEMP_TOO_SMALL. */
+ENVGS_API int envgs_mesh_raster(uint32_t V, uint32_t F, const float *vertices, const float *colors, const int32_t *faces,
+                                const envgs_mesh_raster_views *views, int32_t H, int32_t W, float near, int32_t first, void *temp, size_t temp_bytes,
+                                float *depth, int32_t *face, float *bary, float *normal, float *color, uint8_t *seen, uint64_t *stats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
